@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the reach+distance hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes the outputs of the last timed step as .npy files (dump_outputs): the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 N > 1 works from this plain command (the parent starts N ranks under torch.distributed.run and stays off the GPU) and
 from `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / WORLD_SIZE in the environment).
@@ -43,6 +46,7 @@ N_SIMD, CLOCK_HZ = 256 * 4, 2.4e9  # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs, 2.4
 LO = np.array([-200, -500, -500], np.float32)
 HI = np.array([700, 500, 300], np.float32)
 CHUNK = 1_000_000
+DUMP_POINTS = 1 << 20  # --dump-outputs: points sampled from larger clouds (28 MB of .npy files)
 
 
 def committed_profile(points, mode, profiles_dir=None):
@@ -99,6 +103,31 @@ def make_shard(lo, hi, seed=42):
         out[:, a - lo:b - lo] = pts[a - c * CHUNK:b - c * CHUNK].T
         c += 1
     return out
+
+
+def dump_sample(n, k=DUMP_POINTS, seed=1234):
+    """the point indices --dump-outputs writes: all n points, or a fixed seeded sample of k of them, ascending"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, mask, field, words, n):
+    """What the timed path returned in its last step, on the points of dump_sample(n), as float32 .npy files:
+    reach_mask (the mask bytes), dist_field (3, k) and reach_bits (the ballot bit words, unpacked), beside
+    sample_index (float64).  Returns the file names."""
+    import torch
+    idx = dump_sample(n)
+    ti = torch.from_numpy(idx).to(mask.device)
+    w = words.cpu().numpy().view(np.uint64)
+    out = {"sample_index": idx.astype(np.float64),
+           "reach_mask": mask[:n].index_select(0, ti).cpu().numpy().astype(np.float32),
+           "dist_field": field[:, :n].index_select(1, ti).cpu().numpy(),
+           "reach_bits": ((w[idx >> 6] >> (idx & 63).astype(np.uint64)) & np.uint64(1)).astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(name + ".npy" for name in out)
 
 
 def cpu_baseline(sample_points, leg):
@@ -302,7 +331,12 @@ def parse_args(argv=None):
     ap.add_argument("--precondition-ms", type=float, default=100.0,
                     help="untimed GPU load before the W warm-up steps so that short runs are also measured at the "
                          "steady clocks (the first ~50 ms after idle run ~15 %% slower); 0 disables it")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's points, a fixed sample of large clouds) as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args, argv):
@@ -606,6 +640,10 @@ def main():
 
     # the gathered words of the last step: every rank holds the mask of the whole cloud
     last = loop.result((args.warmup + args.steps - 1) & 1)
+    dumped = None
+    if rank == 0 and args.dump_outputs:  # before the untimed figures below overwrite `mask` / `field`
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, mask, field, last, n),
+                  "points": int(min(n, DUMP_POINTS))}
     reachable_fraction = float(sum(bin(int(w) & (2**64 - 1)).count("1") for w in last[:4096].cpu().tolist()) / (64 * min(4096, last.numel())))
 
     # error statistics of the output the timed steps left in `mask` / `field` (before anything overwrites them)
@@ -763,6 +801,8 @@ def main():
             "kernels": extra,
             "configs": configs,
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(host, leg)
         print(json.dumps(line), flush=True)

@@ -4,6 +4,7 @@ import json
 import os
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,3 +53,36 @@ def test_committed_profile_lookup_is_tied_to_the_kernel_sources(tmp_path):
         assert 250e6 < p["traffic"] < 320e6          # algorithmic 251.25 MB + the fix-up's scattered accesses
     if p["valu_insts_per_eval"] is not None:
         assert 300 < p["valu_insts_per_eval"] < 800
+
+
+def test_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """--dump-outputs: the same sorted sample of point indices in every run, float32 / float64 files of at most 64 MB,
+    and each file holds the outputs of exactly the sampled points (the bit words unpacked in the shard.pack_bits layout)."""
+    import torch
+    from lrm_amd import shard
+    b = _bench()
+    n = b.DUMP_POINTS + 250_001  # larger than the sample
+    idx = b.dump_sample(n)
+    assert len(idx) == b.DUMP_POINTS and np.array_equal(idx, b.dump_sample(n))
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(b.dump_sample(1000), np.arange(1000))
+    rng = np.random.default_rng(0)
+    mask = (rng.random(n) < 0.3).astype(np.uint8)
+    field = rng.standard_normal((3, n)).astype(np.float32)
+    words = torch.from_numpy(shard.pack_bits(mask))
+    files = b.dump_outputs(str(tmp_path / "out"), torch.from_numpy(mask), torch.from_numpy(field), words, n)
+    assert files == ["dist_field.npy", "reach_bits.npy", "reach_mask.npy", "sample_index.npy"]
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["sample_index"], idx.astype(np.float64))
+    assert np.array_equal(got["reach_mask"], mask[idx].astype(np.float32))
+    assert np.array_equal(got["reach_bits"], mask[idx].astype(np.float32))
+    assert got["dist_field"].shape == (3, len(idx)) and np.array_equal(got["dist_field"], field[:, idx])
+
+
+def test_steps_must_be_positive():
+    b = _bench()
+    assert b.parse_args(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])

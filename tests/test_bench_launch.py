@@ -1,10 +1,14 @@
 """`python bench.py --gpus N` must start from the plain command the driver uses (no torch.distributed.run around it):
 the parent launches the ranks itself and never touches the GPU.  Rehearsed here without a GPU through
-LRM_BENCH_DRYRUN=1 (gloo, nothing evaluated: the step loop, the gathers, the rank count and the JSON relay)."""
+LRM_BENCH_DRYRUN=1 (gloo, nothing evaluated: the step loop, the gathers, the rank count and the JSON relay).
+The GPU test runs the real one-GPU bench and checks what --dump-outputs wrote."""
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -56,3 +60,28 @@ def test_rank_count_mismatch_fails_loudly():
     """under torch.distributed.run with a WORLD_SIZE that is not --gpus the bench refuses to run"""
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"], {"LRM_BENCH_DRYRUN": "1", "WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_last_timed_step(lrm, tmp_path):
+    """--dump-outputs DIR on one GPU: --steps timed steps, ms_per_step in the line, and the dumped sample of the last step
+    identical to the CPU entry points on the same seeded cloud (LRM_MODE_FAST: mask and every float bit-exact)."""
+    import importlib.util
+    from conftest import bits_equal
+    n = 1_500_000  # more than bench.DUMP_POINTS: the sampled path
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--points", str(n), "--mode", "fast", "--no-extras",
+              "--no-cpu-baseline", "--no-tolerance-check", "--precondition-ms", "0", "--dump-outputs", str(tmp_path)], {}, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    got = {f[:-4]: np.load(tmp_path / f) for f in rec["dumped_outputs"]["files"]}
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    idx = bench.dump_sample(n)
+    assert np.array_equal(got["sample_index"], idx.astype(np.float64))
+    pts = np.ascontiguousarray(bench.make_cloud(n, 42)[:, idx].T)
+    leg = lrm.get_M2_leg(0.0)
+    want_m = lrm.apply_reach_cpu(pts, leg)[0].astype(np.float32)
+    assert np.array_equal(got["reach_mask"], want_m) and np.array_equal(got["reach_bits"], want_m)
+    assert bits_equal(got["dist_field"].T, lrm.apply_dist_cpu(pts, leg)[0]).all()

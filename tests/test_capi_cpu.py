@@ -4,11 +4,12 @@ compile) reproduce the reference fixtures bit for bit through the explicit CPU e
 (apply_reach_cpu / apply_dist_cpu mirrors), and the GPU entry points fail loudly, not
 silently, when there is no device."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
 
-from conftest import bits_equal, golden_cases, load_case, random_cloud
+from conftest import GOLDEN, bits_equal, golden_cases, load_case, random_cloud
 
 
 def test_library_exports_every_declared_symbol(lrm):
@@ -20,12 +21,12 @@ def test_library_exports_every_declared_symbol(lrm):
 
 
 def test_leg_struct_layout_and_factories(lrm):
-    legs = dict(np.load("tests/golden/legs.npz"))
+    legs = dict(np.load(os.path.join(GOLDEN, "legs.npz")))
     az = legs.pop("azimuths")
     for i, a in enumerate(az):
         assert lrm.get_M2_leg(float(a)).tobytes() == legs[f"m2_{i}"].tobytes()
         assert lrm.get_moonbot_leg(float(a)).tobytes() == legs[f"moonbot_{i}"].tobytes()
-    tab = np.load("tests/golden/rotate_leg_data.npy")
+    tab = np.load(os.path.join(GOLDEN, "rotate_leg_data.npy"))
     for row in tab:
         assert lrm.rotate_leg_data(row[14:18], row[:14]).tobytes() == row[18:].tobytes()
 

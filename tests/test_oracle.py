@@ -1,10 +1,12 @@
 """The oracle against (a) the fixtures generated from the reference's own host path,
 (b) that host path itself where it is built, (c) the behavioural properties the
 reference's stale Catch2 file one_leg.cpp describes."""
+import os
+
 import numpy as np
 import pytest
 
-from conftest import bits_equal, golden_cases, load_case, random_cloud
+from conftest import GOLDEN, bits_equal, golden_cases, load_case, random_cloud
 
 
 @pytest.mark.parametrize("name", golden_cases())
@@ -18,7 +20,7 @@ def test_oracle_matches_reference_fixture(oracle, name):
 
 
 def test_oracle_leg_tables(oracle):
-    legs = dict(np.load("tests/golden/legs.npz"))
+    legs = dict(np.load(os.path.join(GOLDEN, "legs.npz")))
     az = legs.pop("azimuths")
     for i, a in enumerate(az):
         assert oracle.get_M2_leg(a).tobytes() == legs[f"m2_{i}"].tobytes()
@@ -30,7 +32,7 @@ def test_oracle_leg_tables(oracle):
 
 
 def test_oracle_rotate_leg_data(oracle):
-    tab = np.load("tests/golden/rotate_leg_data.npy")
+    tab = np.load(os.path.join(GOLDEN, "rotate_leg_data.npy"))
     for row in tab:
         leg, q, want = row[:14], row[14:18], row[18:]
         assert oracle.rotate_leg_data(q, leg).tobytes() == want.tobytes()
@@ -55,8 +57,8 @@ def test_oracle_equals_reference_build_on_random_points(oracle, ref):
 
 # ---- properties (one_leg.cpp ideas, re-expressed for the absolute-tibia-limit model) ----
 def _fk(leg, c, f, t):
-    import importlib.util, os
-    spec = importlib.util.spec_from_file_location("mk", os.path.join("tests", "golden", "make_golden.py"))
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk", os.path.join(GOLDEN, "make_golden.py"))
     mk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mk)
     return mk.fk(leg, c, f, t)

@@ -3,7 +3,11 @@ accumulation exactly; the terrain / body lattice reproduce the statistics of the
 maps.py / before.py inputs (recorded below from a run of the reference's own scripts in the build
 container: maps.ground is (65536, 3) float32, x in [-2000, 2000], y in [-6000, 2000],
 z in [-2805.0, 1025.0], std(z) = 1137.9), not its exact samples."""
+import os
+
 import numpy as np
+
+from conftest import GOLDEN
 
 
 def test_bench_grid_sizes_match_the_reference_sweep():
@@ -15,7 +19,7 @@ def test_bench_grid_sizes_match_the_reference_sweep():
     assert g[1, 0] == g[0, 0] and g[1, 2] > g[0, 2]
     gi = workloads.bench_grid(5.12, z_from_xmin=False)
     assert gi[:, 2].min() == -350
-    fix = np.load("tests/golden/grid_bench_m2_id.npz")["points"]
+    fix = np.load(os.path.join(GOLDEN, "grid_bench_m2_id.npz"))["points"]
     assert np.array_equal(workloads.bench_grid(5.12), fix)
 
 
