@@ -203,6 +203,35 @@ int lrm_reach_aos_dev(const float* xyz, size_t n, const LrmLegDimensions* leg, c
 int lrm_dist_aos_dev(const float* xyz, size_t n, const LrmLegDimensions* leg, const float* quat,
                      float* dxyz, uint8_t* valid /* may be NULL */, void* stream);
 
+/* ---- batched multi-pose queries: N (target, pose, leg) queries in one launch -------------------------------------
+ * A pose table quats[nposes][4] (the convention of every `quat` argument above), optionally body[nposes][3], and a leg
+ * table legs[nlegs] (nlegs <= LRM_MAX_LEGS, plain legs: rotate_leg_data is applied per pose, as the single-pose calls
+ * do).  Query i has the target (x[i], y[i], z[i]), the pose pose_idx[i] and the leg leg_idx[i]; with
+ * p = target - body[pose] (f32, component by component; no subtraction when body is NULL):
+ *   mask[i]  = reachability_global(p, legs[leg], quats[pose]);
+ *   valid[i], (dx, dy, dz)[i] = distance_global(p, legs[leg], quats[pose]).
+ * Every byte and every float equals what lrm_reach_dist_dev / lrm_dist_dev return in LRM_MODE_STRICT for that
+ * single (leg, quat) on p, whatever lrm_set_mode says: the tolerance modes need a plane table per (leg, orientation)
+ * and do not apply to posed queries.  pose_idx == NULL: pose 0 for every query; leg_idx == NULL: leg 0.  A query
+ * with an index out of range (pose_idx < 0 or >= nposes, leg_idx >= nlegs) gets mask 0, valid 0 and a nan field.
+ * Any of mask / valid / the field (dx, dy, dz: all three or none) may be NULL; with valid and the field NULL only
+ * the reach evaluation runs.
+ * The workspace (lrm_posed_workspace_bytes, 16-byte aligned device memory) belongs to the caller: one record per
+ * (pose, leg), written by lrm_pose_compile_dev on the call's stream from device-resident quaternions and body
+ * positions, read by lrm_reach_dist_posed_dev with the same nposes and nlegs.  Both calls only launch (no
+ * allocation, no host synchronisation): they can be captured in a graph and replayed with new poses. */
+size_t lrm_posed_workspace_bytes(size_t nposes, size_t nlegs);
+int lrm_pose_compile_dev(const float* quats /* device, nposes x 4 */, const float* body /* device, nposes x 3, may be NULL */,
+                         size_t nposes, const LrmLegDimensions* legs /* host */, size_t nlegs, void* workspace, void* stream);
+int lrm_reach_dist_posed_dev(const float* x, const float* y, const float* z, size_t n, const int32_t* pose_idx,
+                             const uint8_t* leg_idx, const void* workspace, size_t nposes, size_t nlegs, uint8_t* mask,
+                             uint8_t* valid, float* dx, float* dy, float* dz, void* stream);
+/* The same queries on the host (xyz and the field AoS float3, host quats / body): a serial loop over the same
+ * per-point code, the same out-of-range rule.  *ms = chrono milliseconds of the loop (the records' compile excluded). */
+int lrm_reach_dist_posed_cpu(const float* xyz_aos, size_t n, const int32_t* pose_idx, const uint8_t* leg_idx,
+                             const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs,
+                             size_t nlegs, uint8_t* mask, uint8_t* valid, float* dxyz_aos, double* ms);
+
 /* ---- body x target aggregation ---------------------------------------------------------
  * Replaces reach_mem_kernel + launch_opti_mem_reach_kernel (several_leg.cu:92-192) for all
  * legs in ONE launch: out[l*nb + b] = 1 iff some target t satisfies
@@ -344,6 +373,14 @@ int lrm_dbg_exact_math_dev(const float* a, const float* b, size_t n, float* at2,
  * compiler's IEEE sqrtf on ALL 2^32 float bit patterns: writes the number of patterns whose results
  * differ bitwise (nan payloads included) and the first such pattern.  Synchronous. */
 int lrm_dbg_sqrt_check_dev(uint64_t* mismatches_out, uint32_t* first_bad_out);
+
+/* The pose records lrm_pose_compile_dev writes (host quats / body here), made by the host compiler: nposes x nlegs
+ * records of lrm_posed_workspace_bytes(1, 1) bytes, each the first 480 bytes of the host's compiled leg for
+ * (leg, quat) followed by the body position.  The device's records must be the same bytes (tests/test_gpu_posed.py). */
+int lrm_dbg_pose_compile_host(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                              void* records_out);
+/* The first 480 bytes (the part the strict per-point code reads) of the leg compiler's block for (leg, quat), apply_leg_rotation = 1. */
+int lrm_dbg_compile_leg_head(const LrmLegDimensions* leg, const float* quat, void* out480);
 
 /* The filtered (LRM_MODE_FAST) per-point evaluation run on the host WITHOUT its strict
  * fallback, plus the per-point "uncertain" flags that would trigger the fallback.  Any output

@@ -101,6 +101,11 @@ def load():
         "lrm_dbg_sqrt_check_dev": [vp, vp],
         "lrm_any_in_sphere_dev": [vp, vp, vp, sz, vp, vp, vp, sz, fp, vp, vp],
         "lrm_any_in_cylinder_dev": [vp, vp, vp, sz, vp, vp, vp, sz, fp, fp, fp, vp, vp],
+        "lrm_pose_compile_dev": [vp, vp, sz, vp, sz, vp, vp],
+        "lrm_reach_dist_posed_dev": [vp, vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp],
+        "lrm_reach_dist_posed_cpu": [vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
+        "lrm_dbg_pose_compile_host": [vp, vp, sz, vp, sz, vp],
+        "lrm_dbg_compile_leg_head": [vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -135,6 +140,8 @@ def load():
     L.lrm_multi_release.restype = None
     L.lrm_release_workspaces.argtypes = []
     L.lrm_release_workspaces.restype = None
+    L.lrm_posed_workspace_bytes.argtypes = [sz, sz]
+    L.lrm_posed_workspace_bytes.restype = sz
     _lib = L
     return L
 
@@ -290,6 +297,47 @@ def apply_dist_cpu(xyz, leg, quat=None):
     check(load().lrm_dist_cpu(_ptr(xyz), len(xyz), _ptr(_f32(leg, (14,))), _ptr(_quat(quat)), _ptr(d), _ptr(v),
                               C.addressof(ms)))
     return d, v, ms.value
+
+
+POSE_RECORD_BYTES = 512  # lrm_posed_workspace_bytes(1, 1)
+
+
+def _posed_tables(quats, body, legs):
+    quats = _f32(quats).reshape(-1, 4)
+    body = None if body is None else _f32(body).reshape(-1, 3)
+    if body is not None and len(body) != len(quats):
+        raise ValueError("body: one position per pose")
+    return quats, body, _f32(legs).reshape(-1, 14)
+
+
+def apply_reach_dist_posed_cpu(xyz, pose_idx, leg_idx, quats, body, legs):
+    """lrm_reach_dist_posed_cpu: query i = (xyz[i], pose pose_idx[i], leg leg_idx[i]) on the host; pose_idx (int32) /
+    leg_idx (uint8) None = pose 0 / leg 0 for all -> (mask uint8[n], valid uint8[n], field float32[n, 3], ms)"""
+    xyz = _f32(xyz, (-1, 3))
+    n = len(xyz)
+    quats, body, legs = _posed_tables(quats, body, legs)
+    pi = None if pose_idx is None else np.ascontiguousarray(pose_idx, np.int32).reshape(n)
+    li = None if leg_idx is None else np.ascontiguousarray(leg_idx, np.uint8).reshape(n)
+    m, v, d = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros_like(xyz)
+    ms = C.c_double(0)
+    check(load().lrm_reach_dist_posed_cpu(_ptr(xyz), n, _ptr(pi), _ptr(li), _ptr(quats), _ptr(body), len(quats), _ptr(legs),
+                                          len(legs), _ptr(m), _ptr(v), _ptr(d), C.addressof(ms)))
+    return m, v, d, ms.value
+
+
+def dbg_pose_compile_host(quats, body, legs):
+    """the pose records the host compiler makes -> uint8[nposes, nlegs, POSE_RECORD_BYTES]"""
+    quats, body, legs = _posed_tables(quats, body, legs)
+    out = np.zeros((len(quats), len(legs), POSE_RECORD_BYTES), np.uint8)
+    check(load().lrm_dbg_pose_compile_host(_ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs), _ptr(out)))
+    return out
+
+
+def dbg_compile_leg_head(leg, quat=None):
+    """the first 480 bytes of lrm_compile_leg(leg, quat, 1) -> uint8[480]"""
+    out = np.zeros(480, np.uint8)
+    check(load().lrm_dbg_compile_leg_head(_ptr(_f32(leg, (14,))), _ptr(_quat(quat)), _ptr(out)))
+    return out
 
 
 def apply_rbdl_equiv(xyz, leg):

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include <utility>
 #include <vector>
 #include "lrm_compile.h"
+#include "lrm_compile_head.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
 #include "lrm_point_fast.h"
@@ -819,6 +821,121 @@ int lrm_dist_aos_dev(const float* xyz, size_t n, const LrmLegDimensions* leg, co
     LrmCompiledLeg L;
     lrm_compile_leg(*leg, quat_or_default(quat), 1, &L);
     return launch_dist_aos_mode(1, xyz, n, *leg, quat_or_default(quat), L, valid, dxyz, stream);
+}
+
+// ---- batched multi-pose queries (lrm_posed.hip) ------------------------------------------
+namespace {
+int posed_args(size_t nposes, size_t nlegs, const LrmLegDimensions* legs) {
+    if (nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "posed queries: nlegs > LRM_MAX_LEGS");
+    if (nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "posed queries: nposes does not fit the int32 pose index");
+    if (nposes * nlegs > (size_t)UINT32_MAX) return fail(LRM_EINVAL, "posed queries: more than 2^32 - 1 (pose, leg) records");
+    if (nlegs && !legs) return fail(LRM_EINVAL, "null argument");
+    return LRM_OK;
+}
+// the host pose compiler: record (pose, leg) at pose * nlegs + leg, as pose_compile_kernel writes it
+void host_pose_records(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                       LrmPoseRecord* out) {
+    for (size_t p = 0; p < nposes; p++)
+        for (size_t l = 0; l < nlegs; l++) {
+            LrmPoseRecord& r = out[p * nlegs + l];
+            std::memset(&r, 0, sizeof r);
+            lrm_compile_head(legs[l], quats + 4 * p, 1, &r.head, (LrmLegDimensions*)nullptr);
+            for (int k = 0; k < 3; k++) r.body_pos[k] = body ? body[3 * p + k] : 0.f;
+        }
+}
+} // namespace
+
+size_t lrm_posed_workspace_bytes(size_t nposes, size_t nlegs) { return nposes * nlegs * sizeof(LrmPoseRecord); }
+
+int lrm_pose_compile_dev(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                         void* workspace, void* stream) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!quats || !workspace) return fail(LRM_EINVAL, "null argument");
+    if ((uintptr_t)workspace & 15) return fail(LRM_EINVAL, "posed queries: the workspace must be 16-byte aligned");
+    HIP_TRY(lrm_launch_pose_compile(quats, body, nposes, legs, nlegs, workspace, (hipStream_t)stream), "pose compile launch");
+    return LRM_OK;
+}
+
+int lrm_reach_dist_posed_dev(const float* x, const float* y, const float* z, size_t n, const int32_t* pose_idx,
+                             const uint8_t* leg_idx, const void* workspace, size_t nposes, size_t nlegs, uint8_t* mask,
+                             uint8_t* valid, float* dx, float* dy, float* dz, void* stream) {
+    if (nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "posed queries: nlegs > LRM_MAX_LEGS");
+    if (nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "posed queries: nposes does not fit the int32 pose index");
+    if (nposes * nlegs > (size_t)UINT32_MAX) return fail(LRM_EINVAL, "posed queries: more than 2^32 - 1 (pose, leg) records");
+    if (n == 0) return LRM_OK;
+    if (nposes == 0 || nlegs == 0) return fail(LRM_EINVAL, "posed queries: no pose or no leg for n > 0 queries");
+    if (!workspace) return fail(LRM_EINVAL, "posed queries: null workspace");
+    if ((uintptr_t)workspace & 15) return fail(LRM_EINVAL, "posed queries: the workspace must be 16-byte aligned");
+    if (!x || !y || !z) return fail(LRM_EINVAL, "null argument");
+    if (!dx != !dy || !dx != !dz) return fail(LRM_EINVAL, "posed queries: give all three field components or none");
+    if (!mask && !valid && !dx) return fail(LRM_EINVAL, "posed queries: no output");
+    HIP_TRY(lrm_launch_posed(x, y, z, n, pose_idx, leg_idx, workspace, nposes, nlegs, mask, valid, dx, dy, dz,
+                             (hipStream_t)stream),
+            "posed launch");
+    return LRM_OK;
+}
+
+int lrm_reach_dist_posed_cpu(const float* xyz, size_t n, const int32_t* pose_idx, const uint8_t* leg_idx, const float* quats,
+                             const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, uint8_t* mask,
+                             uint8_t* valid, float* dxyz, double* ms) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (n == 0) return LRM_OK;
+    if (nposes == 0 || nlegs == 0) return fail(LRM_EINVAL, "posed queries: no pose or no leg for n > 0 queries");
+    if (!xyz || !quats) return fail(LRM_EINVAL, "null argument");
+    if (!mask && !valid && !dxyz) return fail(LRM_EINVAL, "posed queries: no output");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t i = 0; i < n; i++) {
+        const int32_t pi = pose_idx ? pose_idx[i] : 0;
+        const uint32_t li = leg_idx ? leg_idx[i] : 0u;
+        if (pi < 0 || (size_t)pi >= nposes || li >= nlegs) { // out of range: mask 0, valid 0, nan field
+            if (mask) mask[i] = 0;
+            if (valid) valid[i] = 0;
+            if (dxyz) dxyz[3 * i] = dxyz[3 * i + 1] = dxyz[3 * i + 2] = std::nanf("");
+            continue;
+        }
+        const LrmPoseRecord& R = recs[(size_t)pi * nlegs + li];
+        const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+        LrmVec3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+        p.x -= R.body_pos[0];
+        p.y -= R.body_pos[1];
+        p.z -= R.body_pos[2];
+        if (mask) mask[i] = lrm_reach_global(L, &R.head.lists[0][0], p);
+        if (valid || dxyz) {
+            const bool v = lrm_dist_global(L, &R.head.lists[0][0], p);
+            if (valid) valid[i] = v;
+            if (dxyz) {
+                dxyz[3 * i] = p.x;
+                dxyz[3 * i + 1] = p.y;
+                dxyz[3 * i + 2] = p.z;
+            }
+        }
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+int lrm_dbg_pose_compile_host(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                              void* records_out) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!quats || !records_out) return fail(LRM_EINVAL, "null argument");
+    host_pose_records(quats, body, nposes, legs, nlegs, (LrmPoseRecord*)records_out);
+    return LRM_OK;
+}
+
+int lrm_dbg_compile_leg_head(const LrmLegDimensions* leg, const float* quat, void* out480) {
+    if (!leg || !out480) return fail(LRM_EINVAL, "null argument");
+    LrmCompiledLeg L;
+    lrm_compile_leg(*leg, quat_or_default(quat), 1, &L);
+    std::memcpy(out480, &L, sizeof(LrmLegHead));
+    return LRM_OK;
 }
 
 // ---- body x target aggregation ---------------------------------------------------------

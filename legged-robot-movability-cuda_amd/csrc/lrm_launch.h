@@ -78,3 +78,11 @@ hipError_t lrm_pair_counts(unsigned long long out[4]);
 // leg has no table, 2 the device builder does not take this leg (use lrm_build_tol_tab), < 0 a negated hipError_t.
 int lrm_build_tol_tab_dev(const LrmTolLeg& L, hipStream_t st, uint8_t** tab_dev_out, size_t* bytes_out, float* ms_out);
 void lrm_toltab_dev_release();
+
+// Batched multi-pose queries (lrm_posed.hip).  records: nposes x nlegs LrmPoseRecord (lrm_compile_head.h), record of
+// (pose, leg) at pose * nlegs + leg.  lrm_launch_posed: op by outputs -- mask set: reach; valid or dx set: distance.
+hipError_t lrm_launch_pose_compile(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs,
+                                   size_t nlegs, void* records, hipStream_t st);
+hipError_t lrm_launch_posed(const float* x, const float* y, const float* z, size_t n, const int32_t* pose_idx,
+                            const uint8_t* leg_idx, const void* records, size_t nposes, size_t nlegs, uint8_t* mask,
+                            uint8_t* valid, float* dx, float* dy, float* dz, hipStream_t st);

@@ -206,3 +206,91 @@ def apply_oct(x, y, z, leg, settings=None, rank=0, world=1, exchange=None):
     with torch.cuda.device(x.device):
         torch.cuda.synchronize(x.device)  # the library works on the null stream
         return _capi.apply_oct_dev(_dp(x), _dp(y), _dp(z), n, leg, settings, rank, world, exchange)
+
+
+class PoseSet:
+    """A pose table for batched multi-pose queries (lrm_pose_compile_dev / lrm_reach_dist_posed_dev).
+
+    legs: up to 8 legs (14 floats each, used as given: the per-pose rotate_leg_data happens inside).  The workspace --
+    one 512-byte record per (pose, leg) for up to nposes_max poses -- is a tensor this object owns.  update() compiles the
+    records from device-resident quaternions (and body positions) on the current stream; reach_dist() answers queries
+    (target, pose, leg).  Both only launch: with check=False, reach_dist can be captured in a graph next to update()
+    and replayed after new poses were copied into the captured quaternion tensor.  The arithmetic is LRM_MODE_STRICT's,
+    whatever set_mode says."""
+
+    def __init__(self, legs, nposes_max, device=None):
+        torch = _torch()
+        self.legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+        if not 1 <= len(self.legs) <= 8:
+            raise ValueError("PoseSet: 1 to 8 legs (LRM_MAX_LEGS)")
+        self.nposes_max = int(nposes_max)
+        if self.nposes_max < 1:
+            raise ValueError("PoseSet: nposes_max >= 1")
+        self.device = torch.device(device if device is not None else "cuda")
+        nbytes = _capi.load().lrm_posed_workspace_bytes(self.nposes_max, len(self.legs))
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.nposes = 0
+
+    @property
+    def nlegs(self):
+        return len(self.legs)
+
+    def update(self, quats, body=None):
+        """(Re)compile the records of poses 0 .. len(quats) - 1 from quats (float32 [nposes, 4], the quat convention
+        of the single-pose calls) and body (float32 [nposes, 3] or None: no offset), both on this set's device."""
+        torch = _torch()
+        if quats.dim() != 2 or quats.shape[1] != 4:
+            raise ValueError("quats: expected a float32 tensor of shape (nposes, 4)")
+        nposes = quats.shape[0]
+        if not 1 <= nposes <= self.nposes_max:
+            raise ValueError(f"quats: 1 to {self.nposes_max} poses")
+        _check_out(quats, self.workspace, torch.float32, 4 * nposes, "quats")
+        _check_out(body, self.workspace, torch.float32, 3 * nposes, "body")
+        if body is not None and tuple(body.shape) != (nposes, 3):
+            raise ValueError("body: expected a float32 tensor of shape (nposes, 3)")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_pose_compile_dev(_dp(quats), _dp(body), nposes, _capi._ptr(self.legs), self.nlegs,
+                                                          _dp(self.workspace), _stream(self.workspace)))
+        self.nposes = nposes
+        return self
+
+    def reach_dist(self, x, y, z, pose_idx=None, leg_idx=None, mask=None, out=None, valid=None, want_dist=True, check=True):
+        """Query i = (x[i], y[i], z[i]) for pose pose_idx[i] (int32; None: pose 0) and leg leg_idx[i] (uint8; None:
+        leg 0) -> (mask uint8[n], field float32 (3, n), valid uint8[n]); with want_dist=False only the mask (field and
+        valid None).  check=True validates the indices on the host (one synchronisation); check=False leaves an
+        out-of-range index to the kernel (mask 0, valid 0, nan field): the form for graph capture."""
+        torch = _torch()
+        n = _check_f32(x, y, z)
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if x.device != self.workspace.device:
+            raise ValueError("queries and poses must live on one device")
+        _check_out(pose_idx, x, torch.int32, n, "pose_idx")
+        _check_out(leg_idx, x, torch.uint8, n, "leg_idx")
+        if pose_idx is not None and pose_idx.numel() != n or leg_idx is not None and leg_idx.numel() != n:
+            raise ValueError("pose_idx / leg_idx: one index per query")
+        if check and n:
+            if pose_idx is not None:
+                lo, hi = torch.aminmax(pose_idx)
+                if int(lo) < 0 or int(hi) >= self.nposes:
+                    raise ValueError(f"pose_idx outside [0, {self.nposes})")
+            if leg_idx is not None and int(leg_idx.max()) >= self.nlegs:
+                raise ValueError(f"leg_idx outside [0, {self.nlegs})")
+        if mask is None:
+            mask = torch.empty(n, dtype=torch.uint8, device=x.device)
+        _check_out(mask, x, torch.uint8, n, "mask")
+        if want_dist:
+            if out is None:
+                out = torch.empty((3, n), dtype=torch.float32, device=x.device)
+            if valid is None:
+                valid = torch.empty(n, dtype=torch.uint8, device=x.device)
+            _check_field(out, x, n)
+            _check_out(valid, x, torch.uint8, n, "validity bytes")
+        else:
+            out = valid = None
+        f = (None, None, None) if out is None else (_dp(out[0]), _dp(out[1]), _dp(out[2]))
+        with torch.cuda.device(x.device):
+            _capi.check(_capi.load().lrm_reach_dist_posed_dev(_dp(x), _dp(y), _dp(z), n, _dp(pose_idx), _dp(leg_idx),
+                                                              _dp(self.workspace), self.nposes, self.nlegs, _dp(mask),
+                                                              _dp(valid), *f, _stream(x)))
+        return mask, out, valid
