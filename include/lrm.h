@@ -232,6 +232,58 @@ int lrm_reach_dist_posed_cpu(const float* xyz_aos, size_t n, const int32_t* pose
                              const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs,
                              size_t nlegs, uint8_t* mask, uint8_t* valid, float* dxyz_aos, double* ms);
 
+/* ---- joint angles: inverse / forward kinematics of the leg ----------------------------------------------------------
+ * The reference answers "reachable?" and "how far?" without joint angles; its only IK is the RBDL benchmark
+ * (lrm_rbdl_equiv_cpu: no angles, no limits, no coxa pitch) and its forward_kine_kernel (one_leg.cu:377-414) ignores
+ * the coxa pitch.  These calls give the angles (coxa yaw, femur, tibia; radians, the reference's forward_kinematics
+ * convention) that put the tip on p, or as near to it as the joint limits allow.
+ * Frame chain as distance_global: p -> qtInvRotate(quat) -> rotate by -body_angle -> x -= body -> rotate by
+ * -coxa_pitch.  Limits: those of rotate_leg_data(quat, leg): coxa in [min, max], femur in [min, max], tibia in
+ * [min, max], femur + tibia in [tibia_absolute_neg, tibia_absolute_pos].  Every returned angle lies within its limits
+ * (femur + tibia up to the rounding of one float addition), whatever the status.
+ * Goal: p when reachability_global(p), else p - d with d = distance_global(p) (the strict evaluation, whatever
+ * lrm_set_mode says).  Of the analytic candidates (yaw direct and mirrored, two knees each, clamped into the limits;
+ * csrc/lrm_ik.h) those within 1e-3 mm of the nearest to the goal compete on the distance to the seed (sum of squared
+ * joint differences; ties: the best-residual candidate first, then direct yaw before mirrored, knee >= 0 before
+ * knee <= 0).  Seed: per point, optional (all three arrays or none); without one, the mid-range of each joint's limits.
+ * The seed only breaks ties among those near-best candidates, so it never changes a status: a seed with a nan or inf
+ * component counts as no seed (e.g. a previous frame's output where its status was 0), and a finite seed so far away
+ * that its distances overflow keeps the best-residual candidate.
+ * Quaternion: the statuses assume a unit quaternion (|q| = 1 to float32 rounding).  The reference does not normalise;
+ * for a non-unit q, qtRotate(q, .) is not the inverse of qtInvRotate(q, .), distance_global's d is then not the
+ * displacement to its nearest point, and status 4 appears at scale.  Normalise before calling.
+ * status[i]:
+ *   LRM_IK_REACHED   1  reachable (mask 1); the tip is within 2e-3 mm of p
+ *   LRM_IK_NEAREST   2  not reachable (mask 0); the tip is at most |d| + 2e-3 mm (+ 2^-22 |d|, the float32
+ *                       resolution of |d|: 1.2e-4 mm at 500 mm) from p
+ *   LRM_IK_MODEL_GAP 3  mask 1, but no candidate is within 2e-3 mm of p: the circle model calls p reachable where the
+ *                       joint limits do not reach; the angles are the best in-limit candidate
+ *   LRM_IK_FAR_GAP   4  mask 0, and no candidate is within that distance: the model's distance is shorter than any
+ *                       in-limit configuration's (with a unit quaternion; see above); the angles are the best in-limit
+ *                       candidate
+ *   LRM_IK_NONE      0  non-finite input (or coordinates beyond ~1e18 mm, where float32 overflows): nan angles
+ * So status in {1, 3} <=> reachability_global's mask.  Decided in float32; the device entry points equal the CPU ones
+ * bit for bit (angles, status bytes, FK positions).
+ * lrm_fk_*: the tip of (coxa, femur, tibia) in the caller's frame, the exact inverse of the chain above (the
+ * reference's forward_kinematics plus coxa pitch, body_angle and quat).
+ * *_dev: device pointers, SoA, only launch (no allocation, no host synchronisation: graph-capturable); `stream` a
+ * hipStream_t.  *_cpu: AoS float3 (angles {coxa, femur, tibia} per point), serial host loops, *ms = their chrono
+ * milliseconds. */
+#define LRM_IK_NONE 0
+#define LRM_IK_REACHED 1
+#define LRM_IK_NEAREST 2
+#define LRM_IK_MODEL_GAP 3
+#define LRM_IK_FAR_GAP 4
+int lrm_ik_dev(const float* x, const float* y, const float* z, size_t n, const LrmLegDimensions* leg, const float* quat,
+               const float* seed_c, const float* seed_f, const float* seed_t /* each may be NULL: all or none */,
+               float* coxa, float* femur, float* tibia, uint8_t* status, void* stream);
+int lrm_fk_dev(const float* coxa, const float* femur, const float* tibia, size_t n, const LrmLegDimensions* leg,
+               const float* quat, float* x, float* y, float* z, void* stream);
+int lrm_ik_cpu(const float* xyz_aos, size_t n, const LrmLegDimensions* leg, const float* quat,
+               const float* seed_aos /* may be NULL */, float* angles_aos, uint8_t* status, double* ms);
+int lrm_fk_cpu(const float* angles_aos, size_t n, const LrmLegDimensions* leg, const float* quat, float* xyz_aos,
+               double* ms);
+
 /* ---- body x target aggregation ---------------------------------------------------------
  * Replaces reach_mem_kernel + launch_opti_mem_reach_kernel (several_leg.cu:92-192) for all
  * legs in ONE launch: out[l*nb + b] = 1 iff some target t satisfies

@@ -106,6 +106,10 @@ def load():
         "lrm_reach_dist_posed_cpu": [vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
         "lrm_dbg_pose_compile_host": [vp, vp, sz, vp, sz, vp],
         "lrm_dbg_compile_leg_head": [vp, vp, vp],
+        "lrm_ik_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_fk_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp],
+        "lrm_ik_cpu": [vp, sz, vp, vp, vp, vp, vp, vp],
+        "lrm_fk_cpu": [vp, sz, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -338,6 +342,36 @@ def dbg_compile_leg_head(leg, quat=None):
     out = np.zeros(480, np.uint8)
     check(load().lrm_dbg_compile_leg_head(_ptr(_f32(leg, (14,))), _ptr(_quat(quat)), _ptr(out)))
     return out
+
+
+# ---- joint angles (lrm_ik_*, lrm_fk_*) ------------------------------------------------------
+IK_NONE, IK_REACHED, IK_NEAREST, IK_MODEL_GAP, IK_FAR_GAP = 0, 1, 2, 3, 4  # LRM_IK_* status bytes
+
+
+def apply_ik_cpu(xyz, leg, quat=None, seed=None):
+    """lrm_ik_cpu: joint angles that put the tip on each point, or as near as the limits allow
+    -> (angles float32[n, 3] {coxa, femur, tibia}, status uint8[n] LRM_IK_*, ms); seed None = mid-range of the limits"""
+    xyz = _f32(xyz, (-1, 3))
+    n = len(xyz)
+    if seed is not None:
+        seed = _f32(seed)
+        if seed.shape != (n, 3):
+            raise ValueError("seed: one (coxa, femur, tibia) triple per point")
+    ang = np.zeros((n, 3), np.float32)
+    st = np.zeros(n, np.uint8)
+    ms = C.c_double(0)
+    check(load().lrm_ik_cpu(_ptr(xyz), n, _ptr(_f32(leg, (14,))), _ptr(_quat(quat)), _ptr(seed), _ptr(ang), _ptr(st),
+                            C.addressof(ms)))
+    return ang, st, ms.value
+
+
+def apply_fk_cpu(angles, leg, quat=None):
+    """lrm_fk_cpu: tip positions of joint angles (float32[n, 3] {coxa, femur, tibia}) -> (xyz float32[n, 3], ms)"""
+    ang = _f32(angles, (-1, 3))
+    xyz = np.zeros_like(ang)
+    ms = C.c_double(0)
+    check(load().lrm_fk_cpu(_ptr(ang), len(ang), _ptr(_f32(leg, (14,))), _ptr(_quat(quat)), _ptr(xyz), C.addressof(ms)))
+    return xyz, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

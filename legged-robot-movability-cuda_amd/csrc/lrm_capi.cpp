@@ -18,6 +18,7 @@
 #include <vector>
 #include "lrm_compile.h"
 #include "lrm_compile_head.h"
+#include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
 #include "lrm_point_fast.h"
@@ -935,6 +936,85 @@ int lrm_dbg_compile_leg_head(const LrmLegDimensions* leg, const float* quat, voi
     LrmCompiledLeg L;
     lrm_compile_leg(*leg, quat_or_default(quat), 1, &L);
     std::memcpy(out480, &L, sizeof(LrmLegHead));
+    return LRM_OK;
+}
+
+// ---- joint angles (lrm_ik.h, lrm_ik.hip) --------------------------------------------------
+// The strict head of lrm_compile_leg(leg, quat, 1) and the IK constants of rotate_leg_data(quat, leg): the reach and
+// distance part reads the compiled leg the strict calls use, the IK part its own small block.
+namespace {
+void ik_compile(const LrmLegDimensions& leg, const float* quat, LrmCompiledLeg* L, LrmIkLeg* K) {
+    lrm_compile_leg(leg, quat_or_default(quat), 1, L);
+    LrmLegDimensions r;
+    lrm_host_rotate_leg_data(quat_or_default(quat), leg, &r);
+    lrm_ik_compile(r, *L, K);
+}
+} // namespace
+
+int lrm_ik_dev(const float* x, const float* y, const float* z, size_t n, const LrmLegDimensions* leg, const float* quat,
+               const float* seed_c, const float* seed_f, const float* seed_t, float* coxa, float* femur, float* tibia,
+               uint8_t* status, void* stream) {
+    if (!leg) return fail(LRM_EINVAL, "null argument");
+    if (!seed_c != !seed_f || !seed_c != !seed_t) return fail(LRM_EINVAL, "ik: give all three seed arrays or none");
+    if (n && (!x || !y || !z || !coxa || !femur || !tibia || !status)) return fail(LRM_EINVAL, "null argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LRM_ENODEV, "no HIP device");
+    if (n == 0) return LRM_OK;
+    LrmCompiledLeg L;
+    LrmIkLeg K;
+    ik_compile(*leg, quat, &L, &K);
+    HIP_TRY(lrm_launch_ik(x, y, z, n, L, K, seed_c, seed_f, seed_t, coxa, femur, tibia, status, (hipStream_t)stream), "ik launch");
+    return LRM_OK;
+}
+
+int lrm_fk_dev(const float* coxa, const float* femur, const float* tibia, size_t n, const LrmLegDimensions* leg,
+               const float* quat, float* x, float* y, float* z, void* stream) {
+    if (!leg || (n && (!coxa || !femur || !tibia || !x || !y || !z))) return fail(LRM_EINVAL, "null argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LRM_ENODEV, "no HIP device");
+    if (n == 0) return LRM_OK;
+    LrmCompiledLeg L;
+    LrmIkLeg K;
+    ik_compile(*leg, quat, &L, &K);
+    HIP_TRY(lrm_launch_fk(coxa, femur, tibia, n, L, K, x, y, z, (hipStream_t)stream), "fk launch");
+    return LRM_OK;
+}
+
+int lrm_ik_cpu(const float* xyz, size_t n, const LrmLegDimensions* leg, const float* quat, const float* seed,
+               float* angles, uint8_t* status, double* ms) {
+    if (!leg || (n && (!xyz || !angles || !status))) return fail(LRM_EINVAL, "null argument");
+    LrmCompiledLeg L;
+    LrmIkLeg K;
+    ik_compile(*leg, quat, &L, &K);
+    const LrmVec3 dseed{K.seed[0], K.seed[1], K.seed[2]};
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t i = 0; i < n; i++) {
+        const LrmVec3 s = seed ? LrmVec3{seed[3 * i], seed[3 * i + 1], seed[3 * i + 2]} : dseed;
+        LrmVec3 a;
+        status[i] = lrm_ik_point(L, &L.lists[0][0], K, LrmVec3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]}, s, a);
+        angles[3 * i] = a.x;
+        angles[3 * i + 1] = a.y;
+        angles[3 * i + 2] = a.z;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+int lrm_fk_cpu(const float* angles, size_t n, const LrmLegDimensions* leg, const float* quat, float* xyz, double* ms) {
+    if (!leg || (n && (!angles || !xyz))) return fail(LRM_EINVAL, "null argument");
+    LrmCompiledLeg L;
+    LrmIkLeg K;
+    ik_compile(*leg, quat, &L, &K);
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t i = 0; i < n; i++) {
+        const LrmVec3 p = lrm_fk_point(L, K, angles[3 * i], angles[3 * i + 1], angles[3 * i + 2]);
+        xyz[3 * i] = p.x;
+        xyz[3 * i + 1] = p.y;
+        xyz[3 * i + 2] = p.z;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 

@@ -117,6 +117,47 @@ def reach_dist(x, y, z, leg, quat=None, mask=None, out=None, bits=None):
     return mask, out
 
 
+def ik(x, y, z, leg, quat=None, seed=None, out=None, status=None):
+    """Joint angles (coxa, femur, tibia) that put the tip on each point, or as near as the joint limits allow, and the
+    LRM_IK_* status byte of each (include/lrm.h).  seed: None (mid-range of the limits) or three float32 tensors
+    (coxa, femur, tibia) of the points' length.  -> (angles (3, n) float32, status uint8[n]); one launch."""
+    torch = _torch()
+    n = _check_f32(x, y, z)
+    if seed is not None:
+        if len(seed) != 3:
+            raise ValueError("seed: three tensors (coxa, femur, tibia) or None")
+        if _check_f32(x, *seed) != n:
+            raise ValueError("seed: one angle per point")
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.float32, device=x.device)
+    if status is None:
+        status = torch.empty(n, dtype=torch.uint8, device=x.device)
+    _check_field(out, x, n)
+    _check_out(status, x, torch.uint8, n, "status")
+    leg = _leg(leg)
+    q = _q(quat)
+    sc, sf, st = (None, None, None) if seed is None else seed
+    with torch.cuda.device(x.device):
+        _capi.check(_capi.load().lrm_ik_dev(_dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(sc), _dp(sf),
+                                            _dp(st), _dp(out[0]), _dp(out[1]), _dp(out[2]), _dp(status), _stream(x)))
+    return out, status
+
+
+def fk(coxa, femur, tibia, leg, quat=None, out=None):
+    """Tip positions (3, n) of joint angles, the inverse of the frame chain ik() solves in; one launch."""
+    torch = _torch()
+    n = _check_f32(coxa, femur, tibia)
+    if out is None:
+        out = torch.empty((3, n), dtype=torch.float32, device=coxa.device)
+    _check_field(out, coxa, n)
+    leg = _leg(leg)
+    q = _q(quat)
+    with torch.cuda.device(coxa.device):
+        _capi.check(_capi.load().lrm_fk_dev(_dp(coxa), _dp(femur), _dp(tibia), n, _capi._ptr(leg), _capi._ptr(q),
+                                            _dp(out[0]), _dp(out[1]), _dp(out[2]), _stream(coxa)))
+    return out
+
+
 def reach_any(bx, by, bz, tx, ty, tz, legs, quat=None, out=None, all_legs=None):
     """out[l, b] = any target reachable by leg l from body b (legs used as given);
     all_legs[b] = AND over legs."""
