@@ -170,8 +170,10 @@ int lrm_rbdl_equiv_cpu(const float* xyz_aos, size_t n, const LrmLegDimensions* l
  * read-back; LRM_TOLTAB_HOST=1: the host builder, ~30 ms), and allocates the doubt
  * queues of this (device, stream); a later call with a larger n regrows the queues (hipFree + hipMalloc: a device-wide
  * synchronisation).  lrm_tol_prepare does all of that ahead of time, after which the calls only launch -- graph
- * capture and latency-critical loops call it first.  The table cache holds 64 (leg, orientation) pairs, least
- * recently used out.  lrm_release_workspaces frees every cached device buffer (queues, tables, the host pipeline's
+ * capture and latency-critical loops call it first.  Invariant: the queue words it reserves for n_max are at least what
+ * any distance / fused call on n <= n_max points of the same (device, stream) requests, in every mode, with or without the
+ * plane table (lrm_dbg_tol_grid reports both; the launch grids are not monotone in n, the requested words are).  The
+ * table cache holds 64 (leg, orientation) pairs, least recently used out.  lrm_release_workspaces frees every cached device buffer (queues, tables, the host pipeline's
  * buffers and streams, the multi-device communicators); the next call re-creates what it needs. */
 int lrm_tol_prepare(const LrmLegDimensions* leg, const float* quat, size_t n_max, void* stream);
 /* Milliseconds the most recent plane-table build of this process took (the table of a (leg, orientation) is built by the first
@@ -479,6 +481,13 @@ int lrm_dbg_pair_counts(uint64_t out[4]);
  * kernel queued for the bit-exact fix-up launch, and how many workgroups overflowed their queue segment (all their
  * points are re-evaluated).  Synchronises that device. */
 int lrm_dbg_tol_queue_counts(uint64_t* n_points, uint64_t* n_queued, uint64_t* n_overflowed);
+/* The launch grids of the distance / fused calls for n points, from the functions the launches themselves call (host only, no
+ * device needed): out[0] workgroups of the table kernels of LRM_MODE_TOL and LRM_MODE_FAST, out[1] workgroups of the table
+ * kernel of LRM_MODE_TOL_REL, out[2] workgroups of the tolerance kernel without a plane table; out[3] the queue words (uint32)
+ * a call with the plane table requests, out[4] those a call without it requests, out[5] the words lrm_tol_prepare(n) reserves
+ * (before its allocation slack).  A workgroup has 256 threads; a grid of b workgroups strides by 256 b points per round.
+ * tests/test_grid_cpu.py checks lrm_tol_prepare's invariant with it, tests/test_gpu_shapes.py aims at the grids' transitions. */
+int lrm_dbg_tol_grid(size_t n, uint64_t out[6]);
 /* 1 if (leg, quat) is eligible for LRM_MODE_TOL, else 0 */
 int lrm_dbg_tol_ok(const LrmLegDimensions* leg, const float* quat);
 /* The per-leg bounding sphere the pair kernels use to skip batches of footholds:

@@ -82,6 +82,7 @@ def load():
         "lrm_dbg_tol_host": [vp, sz, vp, vp, vp, vp, vp],
         "lrm_dbg_tol_ok": [vp, vp],
         "lrm_dbg_tol_queue_counts": [vp, vp, vp],
+        "lrm_dbg_tol_grid": [sz, vp],
         "lrm_dbg_toltab_host": [vp, sz, vp, vp, vp, vp, vp, vp],
         "lrm_dbg_toltab_bounds": [vp, sz, vp, vp, vp, vp, vp, vp],
         "lrm_dbg_xtab_host": [vp, sz, vp, vp, vp, vp, vp, vp],
@@ -595,6 +596,15 @@ def dbg_tol_queue_counts():
     a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     check(load().lrm_dbg_tol_queue_counts(C.addressof(a), C.addressof(b), C.addressof(c)))
     return int(a.value), int(b.value), int(c.value)
+
+
+def dbg_tol_grid(n):
+    """lrm_dbg_tol_grid: the launch grids and queue words for n points -- dict with the workgroups of the table kernels of
+    LRM_MODE_TOL / LRM_MODE_FAST ("tab") and of LRM_MODE_TOL_REL ("rel"), of the kernel without a table ("notab"), the queue
+    words a call with / without the table requests ("tab_words", "notab_words") and those lrm_tol_prepare(n) reserves ("prepare_words")"""
+    out = np.zeros(6, np.uint64)
+    check(load().lrm_dbg_tol_grid(n, _ptr(out)))
+    return dict(zip(("tab", "rel", "notab", "tab_words", "notab_words", "prepare_words"), (int(v) for v in out)))
 
 
 def dbg_tol_ok(leg, quat=None):

@@ -152,6 +152,9 @@ int tol_workspace(size_t words, void* stream, uint32_t** out) {
     *out = w.p;
     return LRM_OK;
 }
+// The queue words lrm_tol_prepare(n_max) reserves: at least what a call of any mode on n <= n_max points requests, with or without
+// the plane table (both word counts are monotone in n), so that those calls never regrow the workspace.
+size_t tol_prepare_words(size_t n_max) { return std::max(lrm_tol_tab_queue_words(n_max), lrm_tol_queue_words(n_max)); }
 // The table kernels (dist_tab_kernel, dist_xtab_kernel) are the default of their modes from LRM_TOLTAB_MIN_POINTS points on
 // (below, a call is launch-bound and the single launch of the kernels without a table wins); LRM_TOL_TABLE=0 in the
 // environment keeps the kernels without a table (A/B runs).
@@ -1475,6 +1478,19 @@ int lrm_dbg_tol_queue_counts(uint64_t* n_points, uint64_t* n_queued, uint64_t* n
     *n_overflowed = o;
     return LRM_OK;
 }
+// The grids and queue words of the tolerance-mode and table-guided launches for n points, from the functions the launches use
+int lrm_dbg_tol_grid(size_t n, uint64_t out[6]) {
+    if (!out) return fail(LRM_EINVAL, "null argument");
+    size_t b[3];
+    lrm_tol_grid(n, b);
+    out[0] = b[0];
+    out[1] = b[1];
+    out[2] = b[2];
+    out[3] = lrm_tol_tab_queue_words(n);
+    out[4] = lrm_tol_queue_words(n);
+    out[5] = tol_prepare_words(n);
+    return LRM_OK;
+}
 int lrm_dbg_tol_ok(const LrmLegDimensions* leg, const float* quat) {
     if (!leg) return 0;
     LrmCompiledLeg L;
@@ -1815,7 +1831,7 @@ int lrm_tol_prepare(const LrmLegDimensions* leg, const float* quat, size_t n_max
         if (rc != LRM_OK) return rc;
     }
     uint32_t* w = nullptr;
-    return tol_workspace(std::max(lrm_tol_tab_queue_words(n_max), lrm_tol_queue_words(n_max)), stream, &w);
+    return tol_workspace(tol_prepare_words(n_max), stream, &w);
 }
 
 // milliseconds the most recent plane-table build of this process took (host wall clock around the builder; -1: none yet)

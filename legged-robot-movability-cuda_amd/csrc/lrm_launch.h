@@ -37,6 +37,9 @@ hipError_t lrm_launch_dist_tol(int op, const float* x, const float* y, const flo
 // Table variant (dist_tab_kernel + the same fix-up): tab_dev = device copy of lrm_build_tol_tab's table for TL.
 size_t lrm_tol_tab_queue_words(size_t n);
 size_t lrm_tol_tab_segments(size_t n, bool rel); // the workspace starts with one count per segment (rel: LRM_MODE_TOL_REL's grid)
+// workgroups of the main kernel for n points: [0] the table kernels of LRM_MODE_TOL / LRM_MODE_FAST, [1] the table kernel of
+// LRM_MODE_TOL_REL, [2] the staged kernel without a table (lrm_dbg_tol_grid)
+void lrm_tol_grid(size_t n, size_t blocks_out[3]);
 struct LrmXtabLeg; // lrm_point_xtab.h
 hipError_t lrm_launch_dist_tab(int op, const float* x, const float* y, const float* z, size_t n, const LrmCompiledLeg& L,
                                const LrmTolLeg& TL, const LrmXtabLeg& X, const uint8_t* tab_dev, uint8_t* mask, uint64_t* bits, float* dx, float* dy,

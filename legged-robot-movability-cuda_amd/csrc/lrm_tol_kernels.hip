@@ -969,8 +969,21 @@ static size_t tab_main_blocks(size_t n) { return tab_blocks(n, 1); }
 #define LRM_SHORT_ROUNDS 5
 #endif
 static size_t tab_short_blocks(size_t n) { return tab_blocks(n, LRM_SHORT_ROUNDS); }
-size_t lrm_tol_tab_queue_words(size_t n) { return tab_main_blocks(n) * (4 * (size_t)kTabSegCap + 4); } // counts (padded to 16 bytes per workgroup) | 16-byte records; (tab_main_blocks >= tab_short_blocks)
+// counts (padded to 16 bytes per workgroup) | 16-byte records, for the largest grid of any cloud of at most n points
+// (tab_main_blocks >= tab_short_blocks).  tab_blocks is not monotone in n: need = base + 1 gives ceil(need / 2) workgroups,
+// against base at need = base.  Below LRM_TAB_ROUNDS * base a grid has at most base workgroups (rounds grow with need), so
+// max(min(need, base), tab_main_blocks(n)) bounds every n' <= n: lrm_tol_prepare(n_max) then covers every later call.
+size_t lrm_tol_tab_queue_words(size_t n) {
+    const size_t base = (size_t)256 * LRM_TAB_MIN_WAVES * LRM_TAB_GRID_MULT;
+    const size_t need = (n + kBlock - 1) / kBlock;
+    return std::max(std::min(need, base), tab_main_blocks(n)) * (4 * (size_t)kTabSegCap + 4);
+}
 size_t lrm_tol_tab_segments(size_t n, bool rel) { return rel ? tab_short_blocks(n) : tab_main_blocks(n); }
+void lrm_tol_grid(size_t n, size_t blocks_out[3]) {
+    blocks_out[0] = tab_main_blocks(n);
+    blocks_out[1] = tab_short_blocks(n);
+    blocks_out[2] = tol_main_blocks(n);
+}
 template <int kOp, bool kAoS>
 static hipError_t launch_tab(const float* x, const float* y, const float* z, size_t n, const LrmCompiledLeg& L, const LrmTolLeg& TL, const LrmXtabLeg& X,
                              const uint8_t* tab_dev, uint8_t* mask, uint64_t* bits, float* dx, float* dy, float* dz, uint32_t* workspace,
