@@ -9,13 +9,20 @@
  * lrm_last_error() then holds a message.  Nothing here ever computes a GPU entry point on
  * the CPU: without a usable HIP device the *_dev / host-buffer GPU calls fail with LRM_ENODEV.
  *
- * Threading: like the reference's harness (single host thread, cross_compiled.cu) the library is meant to be called
- * from one host thread at a time: the arithmetic mode and the caches of compiled tables are process-wide.  Device
- * workspaces (bounding boxes and compiled-leg slots of the pair kernels, doubt queues of LRM_MODE_TOL) are kept per
- * device -- the doubt queues per (device, stream) -- created on first use and reused; a compiled-leg slot is only
- * rewritten after the launch that read it has completed (an event per slot), so the *_dev entry points may be
- * queued on several streams.  The bounding boxes of the pair kernels are one buffer per device: do not run two
- * pair launches on different clouds concurrently on one device.
+ * Threading.  Streams: the *_dev entry points may be queued on several streams.  Device workspaces (bounding boxes and
+ * compiled-leg slots of the pair kernels, doubt queues of LRM_MODE_TOL) are kept per device -- the doubt queues per
+ * (device, stream) -- created on first use and reused; a compiled-leg slot is only rewritten after the launch that read
+ * it has completed (an event per slot).  The bounding boxes of the pair kernels are one buffer per device: do not run
+ * two pair launches on different clouds concurrently on one device.
+ * Host threads: these calls may overlap from several threads: the distance and fused calls in every mode, on device or
+ * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
+ * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
+ * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
+ * lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
+ * must not overlap any other call.
+ * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
+ * and until lrm_release_workspaces.
  *
  * Units: millimetres and radians, float32 arithmetic (reference convention).
  * Quaternions are float[4] = {x,y,z,w} in the reference's own (inconsistent) convention:
@@ -173,8 +180,9 @@ int lrm_rbdl_equiv_cpu(const float* xyz_aos, size_t n, const LrmLegDimensions* l
  * capture and latency-critical loops call it first.  Invariant: the queue words it reserves for n_max are at least what
  * any distance / fused call on n <= n_max points of the same (device, stream) requests, in every mode, with or without the
  * plane table (lrm_dbg_tol_grid reports both; the launch grids are not monotone in n, the requested words are).  The
- * table cache holds 64 (leg, orientation) pairs, least recently used out.  lrm_release_workspaces frees every cached device buffer (queues, tables, the host pipeline's
- * buffers and streams, the multi-device communicators); the next call re-creates what it needs. */
+ * table cache holds 64 (leg, orientation) pairs, least recently used out.  lrm_release_workspaces frees every cached device buffer (queues, tables, the device
+ * table builder's scratch, the octree's tables, the pair kernels' boxes and leg slots, the host pipeline's buffers and streams,
+ * the multi-device communicators); the next call re-creates what it needs. */
 int lrm_tol_prepare(const LrmLegDimensions* leg, const float* quat, size_t n_max, void* stream);
 /* Milliseconds the most recent plane-table build of this process took (the table of a (leg, orientation) is built by the first
  * call that needs it, or by lrm_tol_prepare, and cached); -1 when none has been built yet.  bench.py reports it as

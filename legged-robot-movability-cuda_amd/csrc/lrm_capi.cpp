@@ -52,7 +52,11 @@ const float* quat_or_default(const float* q) { return q ? q : kQuatTest; }
 
 // ---- table-guided modes: plumbing ---------------------------------------------------------------
 // One lock around the process-wide caches below (table cache with LRU eviction, queue workspaces, the statistic of the last
-// call): host threads may call the entry points concurrently; a table is never freed under a launch that is being queued.
+// call, the host pipeline's buffers), held while a call queues its launches: as lrm.h states, host threads may overlap the
+// distance and fused calls in every mode (host or device buffers), lrm_tol_prepare, lrm_apply_oct* and lrm_dbg_toltab_build,
+// and a table is never freed under a launch that is being queued.  The pair kernels' pools (g_pools) and the multi-device
+// communicators (g_multi) are not locked: those calls stay on one host thread.  lrm_release_workspaces must not overlap any
+// other call.
 std::recursive_mutex g_cache_mu;
 // The tolerance block of a (leg, quaternion) costs a few hundred microseconds of host geometry (arc
 // intersections + their verification, lrm_compile_tol): a small cache keyed by the 18 input floats.
@@ -531,8 +535,12 @@ int host_apply(int op, const float* xyz, size_t n, const LrmLegDimensions* leg, 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LRM_ENODEV, "no HIP device");
     LrmCompiledLeg L;
     lrm_compile_leg(*leg, quat_or_default(quat), 1, &L);
-    if (host_pipeline_enabled() && n >= 2 * host_pipeline_chunk())
+    if (host_pipeline_enabled() && n >= 2 * host_pipeline_chunk()) {
+        // one pipelined call at a time: its buffers, pinned slots, streams and events are per device (g_host_pipe).  Its helper
+        // threads take no library lock, and the caller's own launches take g_cache_mu again (recursive).
+        std::lock_guard<std::recursive_mutex> g(g_cache_mu);
         return host_apply_pipelined(op, xyz, n, leg, quat, mask_out, dxyz_out, ms, L);
+    }
     DevBuf d_in, d_mask, d_out;
     HIP_TRY(d_in.alloc(n * 3 * sizeof(float)), "hipMalloc gpu_in.elements");
     const bool want_mask = (op != 1) || mask_out;
@@ -1400,7 +1408,7 @@ int lrm_dbg_toltab_build(const LrmLegDimensions* leg, const float* quat, int dev
     const int rc = lrm_build_tol_tab_dev(TL, nullptr, &t, &bytes, &ms);
     if (rc < 0) return hip_fail((hipError_t)(-rc), "plane table (device build)");
     if (rc == 1) return fail(LRM_EINVAL, "leg needs more table rows than a cell code can name");
-    if (rc == 2) return fail(LRM_EINVAL, "the device builder declines this leg (too many unanswered cells)");
+    if (rc == 2) return fail(LRM_EINVAL, "the device builder declines this leg (too many unanswered cells) or has no device memory for its scratch");
     *size_out = bytes;
     if (ms_out) *ms_out = ms;
     hipError_t e = hipSuccess;
@@ -1865,6 +1873,19 @@ void lrm_release_workspaces(void) {
     }
     g_host_pipe.clear();
     lrm_toltab_dev_release();
+    lrm_octree_release();
+    for (auto& pp : g_pools) { // the pair kernels' boxes and leg slots: each slot's event first, then the buffers
+        DevicePool& P = pp.second;
+        (void)hipSetDevice(pp.first);
+        for (hipEvent_t& ev : P.slot_done) {
+            if (!ev) continue;
+            (void)hipEventSynchronize(ev);
+            (void)hipEventDestroy(ev);
+        }
+        if (P.boxes) (void)hipFree(P.boxes);
+        if (P.legs) (void)hipFree(P.legs);
+    }
+    g_pools.clear();
     multi_release();
     if (have) (void)hipSetDevice(cur);
 }

@@ -78,9 +78,12 @@ hipError_t lrm_launch_sweep_update(const uint8_t* all_legs, const uint8_t* cyl_v
 hipError_t lrm_pair_counts(unsigned long long out[4]);
 
 // The plane table built on the device (lrm_toltab_dev.hip): 0 ok (*tab_dev_out = a fresh hipMalloc-ed table, the caller's), 1 this
-// leg has no table, 2 the device builder does not take this leg (use lrm_build_tol_tab), < 0 a negated hipError_t.
+// leg has no table, 2 the device builder does not take this leg or has no memory for its scratch (use lrm_build_tol_tab), < 0 a
+// negated hipError_t.  Serialised by a lock of its own, taken after the caller's.
 int lrm_build_tol_tab_dev(const LrmTolLeg& L, hipStream_t st, uint8_t** tab_dev_out, size_t* bytes_out, float* ms_out);
 void lrm_toltab_dev_release();
+// frees the octree's table cache (lrm_octree.hip); for lrm_release_workspaces
+void lrm_octree_release();
 
 // Batched multi-pose queries (lrm_posed.hip).  records: nposes x nlegs LrmPoseRecord (lrm_compile_head.h), record of
 // (pose, leg) at pose * nlegs + leg.  lrm_launch_posed: op by outputs -- mask set: reach; valid or dx set: distance.

@@ -621,7 +621,31 @@ thread_local std::string g_oct_err;
 thread_local bool g_oct_trace = false;
 thread_local std::vector<float> g_oct_trace_recs;
 
+// The tolerance blocks and plane tables of every (orientation, leg) an octree call has met, kept across calls (apply_oct_impl);
+// freed by lrm_octree_release.  g_oct_tab_mu guards the map and is held while a call looks its pairs up or builds their tables.
+struct OctTabEntry {
+    LrmTolLeg tl;
+    std::map<int, uint8_t*> tab_dev; // per device: the plane table (lrm_build_tol_tab_dev), nullptr = this leg has none
+};
+std::mutex g_oct_tab_mu;
+std::map<std::array<float, 18>, OctTabEntry> g_oct_tab_cache;
+
 } // namespace
+
+// lrm_release_workspaces: the octree's table cache (its device tables on every device); no octree call may be running
+void lrm_octree_release() {
+    std::lock_guard<std::mutex> g(g_oct_tab_mu);
+    int cur = 0;
+    const bool have = hipGetDevice(&cur) == hipSuccess;
+    for (auto& e : g_oct_tab_cache)
+        for (auto& d : e.second.tab_dev) {
+            if (!d.second) continue;
+            (void)hipSetDevice(d.first);
+            (void)hipFree(d.second);
+        }
+    g_oct_tab_cache.clear();
+    if (have) (void)hipSetDevice(cur);
+}
 
 extern "C" {
 
@@ -850,12 +874,6 @@ static int apply_oct_impl(const float* footholds /* host AoS, or null */, const 
         const char* e = getenv("LRM_OCT_TOL");
         const bool want = fast && (e ? e[0] != '0' : nf >= 300000);
         if (want) {
-            static std::mutex mu;
-            struct Entry {
-                LrmTolLeg tl;
-                std::map<int, uint8_t*> tab_dev; // per device: the plane table (lrm_build_tol_tab_dev), nullptr = this leg has none
-            };
-            static std::map<std::array<float, 18>, Entry> cache;
             std::vector<LrmTolLeg> tols(legs.size());
             std::vector<const uint8_t*> tabs(legs.size(), nullptr);
             // the plane tables (LRM_OCT_TAB=0: without): built on the device on first use, ~0.4 ms each, kept across calls
@@ -864,7 +882,8 @@ static int apply_oct_impl(const float* footholds /* host AoS, or null */, const 
             int dev = 0;
             (void)hipGetDevice(&dev);
             bool any_tab = false;
-            std::lock_guard<std::mutex> g(mu);
+            std::lock_guard<std::mutex> g(g_oct_tab_mu);
+            auto& cache = g_oct_tab_cache;
             for (int a = 0; a < n_angles_max; a++) {
                 const Quat q = quat_from_angle_index((unsigned)a, st);
                 for (int l = 0; l < st.leg_count; l++) {
@@ -881,7 +900,7 @@ static int apply_oct_impl(const float* footholds /* host AoS, or null */, const 
                             lrm_compile_tol(legs[(size_t)a * st.leg_count + l], &tols[(size_t)a * st.leg_count + l]);
                             continue;
                         }
-                        Entry en;
+                        OctTabEntry en;
                         lrm_compile_tol(legs[(size_t)a * st.leg_count + l], &en.tl);
                         it = cache.emplace(key, en).first;
                     }
@@ -894,6 +913,9 @@ static int apply_oct_impl(const float* footholds /* host AoS, or null */, const 
                             float ms = 0.f;
                             const int rc = lrm_build_tol_tab_dev(it->second.tl, nullptr, &t, &bytes, &ms);
                             if (rc < 0) OCT_TRY((hipError_t)(-rc), "plane table (device builder)");
+                            // rc 1 or 2 (no table, the builder declines the leg, or no device memory for its scratch): this pair
+                            // goes without a table -- same results, slower -- until lrm_release_workspaces empties the cache
+
                             dt = it->second.tab_dev.emplace(dev, rc == 0 ? t : nullptr).first;
                         }
                         tabs[(size_t)a * st.leg_count + l] = dt->second;

@@ -20,6 +20,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include <mutex>
 #include <vector>
 #include "lrm_compile.h"
 #include "lrm_toltab_build.h"
@@ -41,6 +42,11 @@ struct DevScratch { // one per device, kept (17 MB)
     uint8_t* row_num = nullptr;    // [LRM_TB_ROWS + LRM_TB_VROWS]
 };
 DevScratch g_scratch[64];
+// One build at a time in this process: the scratch set of a device is shared by every build on it, and its callers hold
+// different locks (lrm_capi.cpp's g_cache_mu, the octree's table-cache lock) or none (lrm_dbg_toltab_build).  Held from the
+// first use of the scratch to the stream synchronise that ends the build, and by lrm_toltab_dev_release.  A caller takes its
+// own lock first, then this one; nothing done under it takes another lock of the library, so the order cannot deadlock.
+std::mutex g_build_mu;
 
 // the rows a lane uses, OR-ed over the wave: one lane issues the three atomics (180 000 same-address atomics would take milliseconds)
 __device__ __forceinline__ void mark_rows(uint32_t* status, bool ok, const LrmTbCell& c) {
@@ -156,20 +162,33 @@ __global__ __launch_bounds__(256) void bounds_kernel(const LrmTbInput* __restric
     }
 }
 
+void free_scratch(DevScratch& S) {
+    for (void* p : {(void*)S.in, (void*)S.coarse, (void*)S.fine, (void*)S.list, (void*)S.slot_of, (void*)S.state, (void*)S.status, (void*)S.fine_of, (void*)S.row_num})
+        if (p) (void)hipFree(p);
+    S = DevScratch{};
+}
+
+// all nine buffers, or none: a failed allocation frees the others, so the next build tries again from scratch
 hipError_t ensure_scratch(int dev, DevScratch** out) {
     DevScratch& S = g_scratch[dev];
     if (!S.in) {
-        hipError_t e;
-        auto A = [&](void** p, size_t bytes) { return hipMalloc(p, bytes); };
-        if ((e = A((void**)&S.in, sizeof(LrmTbInput))) != hipSuccess) return e;
-        if ((e = A((void**)&S.coarse, sizeof(LrmTbCell) * 2 * kCells)) != hipSuccess) return e;
-        if ((e = A((void**)&S.fine, sizeof(LrmTbCell) * 2 * (size_t)kMaxRefine * kSub2)) != hipSuccess) return e;
-        if ((e = A((void**)&S.list, sizeof(uint32_t) * 2 * kMaxRefine)) != hipSuccess) return e;
-        if ((e = A((void**)&S.slot_of, sizeof(int32_t) * 2 * kCells)) != hipSuccess) return e;
-        if ((e = A((void**)&S.state, 2 * kCells)) != hipSuccess) return e;
-        if ((e = A((void**)&S.status, 8 * sizeof(uint32_t))) != hipSuccess) return e;
-        if ((e = A((void**)&S.fine_of, sizeof(uint16_t) * 2 * kCells)) != hipSuccess) return e;
-        if ((e = A((void**)&S.row_num, LRM_TB_ROWS + LRM_TB_VROWS)) != hipSuccess) return e;
+        hipError_t e = hipSuccess;
+        auto A = [&](void** p, size_t bytes) {
+            if (e == hipSuccess) e = hipMalloc(p, bytes);
+        };
+        A((void**)&S.in, sizeof(LrmTbInput));
+        A((void**)&S.coarse, sizeof(LrmTbCell) * 2 * kCells);
+        A((void**)&S.fine, sizeof(LrmTbCell) * 2 * (size_t)kMaxRefine * kSub2);
+        A((void**)&S.list, sizeof(uint32_t) * 2 * kMaxRefine);
+        A((void**)&S.slot_of, sizeof(int32_t) * 2 * kCells);
+        A((void**)&S.state, 2 * kCells);
+        A((void**)&S.status, 8 * sizeof(uint32_t));
+        A((void**)&S.fine_of, sizeof(uint16_t) * 2 * kCells);
+        A((void**)&S.row_num, LRM_TB_ROWS + LRM_TB_VROWS);
+        if (e != hipSuccess) {
+            free_scratch(S);
+            return e;
+        }
     }
     *out = &S;
     return hipSuccess;
@@ -178,15 +197,14 @@ hipError_t ensure_scratch(int dev, DevScratch** out) {
 } // namespace
 
 void lrm_toltab_dev_release() {
+    std::lock_guard<std::mutex> g(g_build_mu);
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
     for (int d = 0; d < 64; d++) {
         DevScratch& S = g_scratch[d];
         if (!S.in) continue;
         (void)hipSetDevice(d);
-        for (void* p : {(void*)S.in, (void*)S.coarse, (void*)S.fine, (void*)S.list, (void*)S.slot_of, (void*)S.state, (void*)S.status, (void*)S.fine_of, (void*)S.row_num})
-            if (p) (void)hipFree(p);
-        S = DevScratch{};
+        free_scratch(S);
     }
     if (have) (void)hipSetDevice(cur);
 }
@@ -194,27 +212,36 @@ void lrm_toltab_dev_release() {
 // Builds the table of L on the current device, on `st`.  *tab_dev_out: a fresh hipMalloc-ed table (the caller owns it), *bytes_out
 // its size; *ms_out (optional) the device time of the build (HIP events around it, the read-back included).
 // Returns 0 ok; 1 this leg has no table (more rows than a cell code can name); 2 the device builder does not take this leg (more
-// unanswered cells than its scratch holds): use the host builder; < 0 a HIP error (hipError_t negated).
+// unanswered cells than its scratch holds, or no device memory for the scratch): use the host builder; < 0 a HIP error (hipError_t
+// negated).  Builds are serialised (g_build_mu).
 int lrm_build_tol_tab_dev(const LrmTolLeg& L, hipStream_t st, uint8_t** tab_dev_out, size_t* bytes_out, float* ms_out) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return -(int)e;
     if (dev < 0 || dev >= 64) return 2;
+    std::lock_guard<std::mutex> g(g_build_mu);
     DevScratch* S = nullptr;
-    if ((e = ensure_scratch(dev, &S)) != hipSuccess) return -(int)e;
+    if ((e = ensure_scratch(dev, &S)) != hipSuccess) {
+        if (e != hipErrorOutOfMemory) return -(int)e;
+        (void)hipGetLastError(); // the failed allocation's error is handled here: later launch checks must not see it
+        return 2;
+    }
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ms_out) {
         if ((e = hipEventCreate(&ev0)) != hipSuccess) return -(int)e;
         if ((e = hipEventCreate(&ev1)) != hipSuccess) { (void)hipEventDestroy(ev0); return -(int)e; }
         (void)hipEventRecord(ev0, st);
     }
+    bool queued = false; // work on `st` uses the scratch: every return after this drains `st` before the lock goes
     auto done = [&](int rc) {
+        if (queued && rc < 0) (void)hipStreamSynchronize(st);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         return rc;
     };
     LrmTbInput in;
     lrm_tb_make_input(L, &in);
+    queued = true;
     if ((e = hipMemcpyAsync(S->in, &in, sizeof in, hipMemcpyHostToDevice, st)) != hipSuccess) return done(-(int)e);
     if ((e = hipMemsetAsync(S->status, 0, 8 * sizeof(uint32_t), st)) != hipSuccess) return done(-(int)e);
     hipLaunchKernelGGL(classify_coarse_kernel, dim3(2 * kCells / 64), dim3(64), 0, st, S->in, S->coarse, S->list, S->slot_of, S->state, S->status);
@@ -249,7 +276,11 @@ int lrm_build_tol_tab_dev(const LrmTolLeg& L, hipStream_t st, uint8_t** tab_dev_
     const size_t bytes = sizeof hd + n_cells * 2;
     void* tab = nullptr;
     if ((e = hipMalloc(&tab, bytes)) != hipSuccess) return done(-(int)e);
-    auto fail = [&](hipError_t err) { (void)hipFree(tab); return done(-(int)err); };
+    auto fail = [&](hipError_t err) {
+        (void)hipStreamSynchronize(st); // the table's kernels first
+        (void)hipFree(tab);
+        return done(-(int)err);
+    };
     if ((e = hipMemsetAsync(tab, 0, bytes, st)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(tab, &hd, sizeof hd, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
     if ((e = hipMemcpyAsync(S->fine_of, fine_of.data(), fine_of.size() * 2, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
