@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -307,6 +307,26 @@ int lrm_reach_any_dev(const float* bx, const float* by, const float* bz, size_t 
                       const float* tx, const float* ty, const float* tz, size_t nt,
                       const LrmLegDimensions* legs, size_t nlegs, const float* quat,
                       uint8_t* out_leg_body, uint8_t* all_legs_out, void* stream);
+/* Per-leg foothold counts and choice, the step between lrm_reach_any_dev and lrm_ik_dev.  Bodies, targets, legs and quat
+ * as in lrm_reach_any_dev; pair (b, t, l) is reachable iff reachable_rotate_leg(t, body b, quat, legs[l]).  Every output
+ * has nlegs * nb entries at [l*nb + b], all written:
+ *   count_out    the number of reachable targets;
+ *   best_out     the index of the reachable target with the smallest d2 to the leg's nominal point (ties: the smaller
+ *                index), -1 when count is 0;
+ *   best_d2_out  (may be NULL) that d2, +inf when count is 0.
+ * d2 in float32 without contraction (host and device agree bit for bit): c = body + nominal[l] (one add per component),
+ * d = target - c, d2 = (dx*dx + dy*dy) + dz*dz.  nominal: host, nlegs x 3, an offset from the body in the clouds' frame
+ * (the leg's neutral foot position, already rotated by the pose); NULL = all zero (nearest the body centre).
+ * nt > INT32_MAX or nlegs outside 1..LRM_MAX_LEGS: LRM_EINVAL, checked first; then nb == 0 is a no-op.  The answers do
+ * not depend on lrm_set_mode.  lrm_footholds_cpu: AoS float3 clouds, a serial host loop over every (body, leg, target)
+ * with the strict test and no culling (the reference the GPU tests compare with); *ms = the loop's time. */
+int lrm_footholds_dev(const float* bx, const float* by, const float* bz, size_t nb,
+                      const float* tx, const float* ty, const float* tz, size_t nt,
+                      const LrmLegDimensions* legs, size_t nlegs, const float* quat,
+                      const float* nominal, int32_t* count_out, int32_t* best_out, float* best_d2_out, void* stream);
+int lrm_footholds_cpu(const float* bodies_aos, size_t nb, const float* targets_aos, size_t nt,
+                      const LrmLegDimensions* legs, size_t nlegs, const float* quat, const float* nominal,
+                      int32_t* count_out, int32_t* best_out, float* best_d2_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

@@ -75,6 +75,8 @@ def load():
         "lrm_reach_aos_dev": [vp, sz, vp, vp, vp, vp],
         "lrm_dist_aos_dev": [vp, sz, vp, vp, vp, vp, vp],
         "lrm_reach_any_dev": [vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
+        "lrm_footholds_dev": [vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
+        "lrm_footholds_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
         "lrm_positionability": [vp, sz, vp, sz, vp, sz, vp, sz, C.c_int, vp, vp],
         "lrm_morton_order": [vp, sz, vp],
         "lrm_dbg_fast_host": [vp, sz, vp, vp, vp, vp, vp, vp, vp],
@@ -640,3 +642,20 @@ def positionability(bodies, targets, legs, quats, reference_culls=False):
                                      len(legs), _ptr(quats), len(quats), int(reference_culls), _ptr(out),
                                      C.addressof(ms)))
     return out, ms.value
+
+
+def footholds_cpu(bodies, targets, legs, quat=None, nominal=None):
+    """lrm_footholds_cpu: per (leg, body) the number of reachable targets, the index of the reachable target nearest the
+    leg's nominal point (body + nominal[l], nominal None = zero; -1 if none) and its squared distance (+inf if none);
+    serial host loop -> (count int32[nlegs, nb], best int32[nlegs, nb], best_d2 float32[nlegs, nb], ms)"""
+    bodies = _f32(bodies, (-1, 3))
+    targets = _f32(targets, (-1, 3))
+    legs = _f32(legs).reshape(-1, 14)
+    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    count = np.zeros((len(legs), len(bodies)), np.int32)
+    best = np.zeros((len(legs), len(bodies)), np.int32)
+    best_d2 = np.zeros((len(legs), len(bodies)), np.float32)
+    ms = C.c_double(0)
+    check(load().lrm_footholds_cpu(_ptr(bodies), len(bodies), _ptr(targets), len(targets), _ptr(legs), len(legs),
+                                   _ptr(_quat(quat)), _ptr(nom), _ptr(count), _ptr(best), _ptr(best_d2), C.addressof(ms)))
+    return count, best, best_d2, ms.value

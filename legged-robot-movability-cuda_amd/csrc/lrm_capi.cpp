@@ -18,6 +18,7 @@
 #include <vector>
 #include "lrm_compile.h"
 #include "lrm_compile_head.h"
+#include "lrm_footholds.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -1135,6 +1136,88 @@ int reach_any_impl(const float* bx, const float* by, const float* bz, size_t nb,
     return LRM_OK;
 }
 } // namespace
+
+// ---- per-leg foothold counts and choice (lrm_footholds_dev / lrm_footholds_cpu) --------------
+namespace {
+// the argument checks of both forms, in reach_any_impl's order; the range checks come before any early return
+int footholds_args(size_t nt, const LrmLegDimensions* legs, size_t nlegs, const float* nominal, LrmFootNominal* nom) {
+    if (nt > (size_t)INT32_MAX) return fail(LRM_EINVAL, "nt must be at most INT32_MAX");
+    if (!legs || nlegs == 0 || nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "nlegs must be 1..LRM_MAX_LEGS");
+    for (int l = 0; l < LRM_MAX_LEGS; l++)
+        for (int a = 0; a < 3; a++) nom->v[l][a] = (nominal && (size_t)l < nlegs) ? nominal[3 * l + a] : 0.f;
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_footholds_dev(const float* bx, const float* by, const float* bz, size_t nb, const float* tx, const float* ty,
+                      const float* tz, size_t nt, const LrmLegDimensions* legs, size_t nlegs, const float* quat,
+                      const float* nominal, int32_t* count_out, int32_t* best_out, float* best_d2_out, void* stream) {
+    LrmFootNominal nom;
+    int rc = footholds_args(nt, legs, nlegs, nominal, &nom);
+    if (rc != LRM_OK) return rc;
+    if (!count_out || !best_out || (nb && (!bx || !by || !bz)) || (nt && (!tx || !ty || !tz)))
+        return fail(LRM_EINVAL, "null argument");
+    if (nb == 0) return LRM_OK;
+    LrmCompiledLeg host_legs[LRM_MAX_LEGS];
+    for (size_t l = 0; l < nlegs; l++) lrm_compile_leg(legs[l], quat_or_default(quat), 0, &host_legs[l]);
+    LrmCompiledLeg* dev_legs = nullptr;
+    hipEvent_t* slot_done = nullptr;
+    rc = leg_slot(&dev_legs, &slot_done);
+    if (rc != LRM_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(dev_legs, host_legs, sizeof(LrmCompiledLeg) * nlegs, hipMemcpyHostToDevice,
+                           (hipStream_t)stream), "hipMemcpyAsync legs");
+    // the filtered test gives the strict test's bit (as in reach_any_impl): the answers do not depend on the mode
+    bool fast = g_mode != LRM_MODE_STRICT;
+    for (size_t l = 0; l < nlegs; l++) fast = fast && host_legs[l].fast_ok;
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_footholds(bx, by, bz, nb, tx, ty, tz, nt, dev_legs, (int)nlegs, boxes, nom, count_out, best_out,
+                                 best_d2_out, fast, (hipStream_t)stream), "footholds launch");
+    HIP_TRY(hipEventRecord(*slot_done, (hipStream_t)stream), "hipEventRecord leg slot"); // the slot is free again after this launch
+    return LRM_OK;
+}
+
+int lrm_footholds_cpu(const float* bodies, size_t nb, const float* targets, size_t nt, const LrmLegDimensions* legs,
+                      size_t nlegs, const float* quat, const float* nominal, int32_t* count_out, int32_t* best_out,
+                      float* best_d2_out, double* ms) {
+    LrmFootNominal nom;
+    const int rc = footholds_args(nt, legs, nlegs, nominal, &nom);
+    if (rc != LRM_OK) return rc;
+    if (nb && (!bodies || !count_out || !best_out)) return fail(LRM_EINVAL, "null argument");
+    if (nt && !targets) return fail(LRM_EINVAL, "null argument");
+    LrmCompiledLeg L[LRM_MAX_LEGS];
+    for (size_t l = 0; l < nlegs; l++) lrm_compile_leg(legs[l], quat_or_default(quat), 0, &L[l]);
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t b = 0; b < nb; b++) {
+        const LrmVec3 body{bodies[3 * b], bodies[3 * b + 1], bodies[3 * b + 2]};
+        for (size_t l = 0; l < nlegs; l++) {
+            int32_t count = 0;
+            uint64_t best = kLrmFootholdNone;
+            for (size_t t = 0; t < nt; t++) {
+                const LrmVec3 p{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
+                if (!lrm_reachable_rotate_leg(L[l], &L[l].lists[0][0], p, body)) continue;
+                count++;
+                const uint64_t key = lrm_foothold_key(lrm_foothold_d2(p, body, nom.v[l]), (uint32_t)t);
+                if (key < best) best = key;
+            }
+            const size_t o = l * nb + b;
+            count_out[o] = count;
+            best_out[o] = count ? (int32_t)(uint32_t)best : -1;
+            if (best_d2_out) {
+                const uint32_t hi = (uint32_t)(best >> 32);
+                float d2;
+                std::memcpy(&d2, &hi, sizeof d2);
+                best_d2_out[o] = count ? d2 : INFINITY;
+            }
+        }
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
 
 namespace {
 int any_in_shape_impl(int shape, const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,

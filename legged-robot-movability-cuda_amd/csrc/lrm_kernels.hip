@@ -1076,6 +1076,12 @@ hipError_t lrm_launch_reach_any(const float* bx, const float* by, const float* b
     return hipGetLastError();
 }
 
+hipError_t lrm_launch_tile_boxes(const float* tx, const float* ty, const float* tz, size_t nt, float* tile_boxes, hipStream_t st) {
+    if (!nt) return hipSuccess;
+    hipLaunchKernelGGL(tile_aabb_kernel, dim3((unsigned)((nt + 1023) / 1024)), dim3(kBlock), 0, st, tx, ty, tz, nt, (nt + 1023) / 1024, tile_boxes);
+    return hipGetLastError();
+}
+
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes, bool boxes_ready, uint8_t* out,

@@ -62,6 +62,15 @@ hipError_t lrm_launch_reach_any(const float* bx, const float* by, const float* b
                                 bool boxes_ready /* the workspace already holds this cloud's boxes */,
                                 const uint8_t* body_active /* null = all */, uint8_t* out_leg_body,
                                 uint8_t* all_legs_out, bool fast, hipStream_t st);
+// tile_aabb_kernel alone: the two-level boxes of a target cloud (17 x ntiles x 6 floats of workspace, as above)
+hipError_t lrm_launch_tile_boxes(const float* tx, const float* ty, const float* tz, size_t nt, float* tile_boxes, hipStream_t st);
+// lrm_footholds_dev (lrm_footholds.hip): outputs [nlegs * nb] at l * nb + b; best_d2_out may be null; tile_boxes null =
+// no culling (small clouds), otherwise workspace that this call fills with the cloud's boxes first
+struct LrmFootNominal; // lrm_footholds.h
+hipError_t lrm_launch_footholds(const float* bx, const float* by, const float* bz, size_t nb, const float* tx,
+                                const float* ty, const float* tz, size_t nt, const LrmCompiledLeg* legs_dev, int nlegs,
+                                float* tile_boxes, const LrmFootNominal& nominal, int32_t* count_out, int32_t* best_out,
+                                float* best_d2_out, bool fast, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

@@ -181,6 +181,34 @@ def reach_any(bx, by, bz, tx, ty, tz, legs, quat=None, out=None, all_legs=None):
     return out, all_legs
 
 
+def footholds(bx, by, bz, tx, ty, tz, legs, quat=None, nominal=None, count=None, best=None, best_d2=None):
+    """lrm_footholds_dev: count[l, b] = targets leg l reaches from body b, best[l, b] = the reachable target nearest
+    body b + nominal[l] (-1 if none), best_d2[l, b] = its squared distance (+inf if none); legs used as given,
+    nominal (nlegs, 3) on the host or None = zero.  -> (count int32, best int32, best_d2 float32), each [nlegs, nb]"""
+    torch = _torch()
+    nb = _check_f32(bx, by, bz)
+    nt = _check_f32(tx, ty, tz)
+    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+    nom = None if nominal is None else np.ascontiguousarray(nominal, dtype=np.float32).reshape(len(legs), 3)
+    if count is None:
+        count = torch.empty((len(legs), nb), dtype=torch.int32, device=bx.device)
+    if best is None:
+        best = torch.empty((len(legs), nb), dtype=torch.int32, device=bx.device)
+    if best_d2 is None:
+        best_d2 = torch.empty((len(legs), nb), dtype=torch.float32, device=bx.device)
+    q = _q(quat)
+    _check_out(count, bx, torch.int32, len(legs) * nb, "per-leg counts")
+    _check_out(best, bx, torch.int32, len(legs) * nb, "per-leg choices")
+    _check_out(best_d2, bx, torch.float32, len(legs) * nb, "per-leg squared distances")
+    if nt and tx.device != bx.device:
+        raise ValueError("bodies and targets must live on one device")
+    with torch.cuda.device(bx.device):
+        _capi.check(_capi.load().lrm_footholds_dev(_dp(bx), _dp(by), _dp(bz), nb, _dp(tx), _dp(ty), _dp(tz), nt,
+                                                   _capi._ptr(legs), len(legs), _capi._ptr(q), _capi._ptr(nom), _dp(count),
+                                                   _dp(best), _dp(best_d2), _stream(bx)))
+    return count, best, best_d2
+
+
 def positionability(bx, by, bz, tx, ty, tz, legs, quats, reference_culls=0, active=None, out=None):
     """lrm_positionability_dev: the orientation sweep of robot_full_struct on device-resident clouds and masks.
     reference_culls: 0 none, 2 the per-orientation cylinder culls.  -> (accepted uint8[nb] on the device, kernel ms)"""
