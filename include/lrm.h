@@ -294,6 +294,49 @@ int lrm_ik_cpu(const float* xyz_aos, size_t n, const LrmLegDimensions* leg, cons
 int lrm_fk_cpu(const float* angles_aos, size_t n, const LrmLegDimensions* leg, const float* quat, float* xyz_aos,
                double* ms);
 
+/* ---- joint angles per (target, pose, leg): the last step after lrm_footholds_dev ------------------------------------
+ * The pose and leg tables of the batched multi-pose queries above, plus a second caller-owned device table of the IK
+ * constants: lrm_posed_ik_workspace_bytes (128 B per (pose, leg), 16-byte aligned), written by lrm_pose_ik_compile_dev
+ * from the same device-resident quaternions and host legs as lrm_pose_compile_dev, entry of (pose, leg) at
+ * pose * nlegs + leg.  Both tables must be compiled for the same nposes and nlegs before a query reads them.
+ * lrm_ik_posed_dev: query i takes target target_idx[i] of the nt targets (x, y, z); with target_idx NULL it takes
+ * target i, and n > nt is LRM_EINVAL.  p = target - body[pose_idx[i]] (one float32 subtraction per component, as
+ * lrm_reach_dist_posed_dev; body as given to lrm_pose_compile_dev).  Angles and status are those of
+ * lrm_ik_cpu(p, legs[leg_idx[i]], quats[pose_idx[i]], seed i), bit for bit: same goal, candidates, tie rules, seed
+ * rules (seed_c / seed_f / seed_t: all or none, one entry per QUERY) and status thresholds.  pose_idx NULL: pose 0;
+ * leg_idx NULL: leg 0.  A query whose pose, leg or target index is out of range (a negative target_idx, such as the -1
+ * lrm_footholds_dev writes where nothing is reachable, included) gets status LRM_IK_NONE and nan angles; the kernel
+ * clamps every index before it loads and never reads outside its tables.  So best_out of lrm_footholds_dev is a valid
+ * target_idx as it stands: with pose_idx[l*nb + b] = b and leg_idx[l*nb + b] = l, one pose per body holding the body
+ * position, and the quaternion and legs of that call's frame convention, one launch gives the angles
+ * of every chosen foothold.
+ * lrm_fk_posed_dev: lrm_fk_dev's tip for (legs[leg], quats[pose]) + body[pose] (one float32 add per component); an
+ * out-of-range pose or leg index gives a nan position.
+ * All three *_dev calls only launch (no allocation, no host synchronisation: graph-capturable) and do not depend on
+ * lrm_set_mode.  *_cpu: the same queries as serial host loops over the same per-point code (AoS float3 targets, seeds,
+ * angles and positions; host quats / body, body may be NULL), the same out-of-range rule; *ms = the loop's chrono
+ * milliseconds, the tables' compile excluded. */
+size_t lrm_posed_ik_workspace_bytes(size_t nposes, size_t nlegs);
+int lrm_pose_ik_compile_dev(const float* quats /* device, nposes x 4 */, size_t nposes, const LrmLegDimensions* legs /* host */,
+                            size_t nlegs, void* ik_workspace, void* stream);
+int lrm_ik_posed_dev(const float* x, const float* y, const float* z, size_t nt,
+                     const int32_t* target_idx /* may be NULL */, size_t n,
+                     const int32_t* pose_idx, const uint8_t* leg_idx,
+                     const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs,
+                     const float* seed_c, const float* seed_f, const float* seed_t /* all or none */,
+                     float* coxa, float* femur, float* tibia, uint8_t* status, void* stream);
+int lrm_fk_posed_dev(const float* coxa, const float* femur, const float* tibia, size_t n,
+                     const int32_t* pose_idx, const uint8_t* leg_idx,
+                     const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs,
+                     float* x, float* y, float* z, void* stream);
+int lrm_ik_posed_cpu(const float* xyz_aos, size_t nt, const int32_t* target_idx, size_t n, const int32_t* pose_idx,
+                     const uint8_t* leg_idx, const float* quats, const float* body, size_t nposes,
+                     const LrmLegDimensions* legs, size_t nlegs, const float* seed_aos, float* angles_aos,
+                     uint8_t* status, double* ms);
+int lrm_fk_posed_cpu(const float* angles_aos, size_t n, const int32_t* pose_idx, const uint8_t* leg_idx,
+                     const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                     float* xyz_aos, double* ms);
+
 /* ---- body x target aggregation ---------------------------------------------------------
  * Replaces reach_mem_kernel + launch_opti_mem_reach_kernel (several_leg.cu:92-192) for all
  * legs in ONE launch: out[l*nb + b] = 1 iff some target t satisfies
@@ -461,6 +504,11 @@ int lrm_dbg_sqrt_check_dev(uint64_t* mismatches_out, uint32_t* first_bad_out);
  * (leg, quat) followed by the body position.  The device's records must be the same bytes (tests/test_gpu_posed.py). */
 int lrm_dbg_pose_compile_host(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
                               void* records_out);
+/* The IK table lrm_pose_ik_compile_dev writes (host quats here), made on the host by the code of the single-pose calls:
+ * nposes x nlegs entries of lrm_posed_ik_workspace_bytes(1, 1) bytes.  The device's must be the same bytes
+ * (tests/test_gpu_ik_posed.py). */
+int lrm_dbg_pose_ik_compile_host(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                 void* records_out);
 /* The first 480 bytes (the part the strict per-point code reads) of the leg compiler's block for (leg, quat), apply_leg_rotation = 1. */
 int lrm_dbg_compile_leg_head(const LrmLegDimensions* leg, const float* quat, void* out480);
 

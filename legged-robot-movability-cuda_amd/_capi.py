@@ -113,6 +113,12 @@ def load():
         "lrm_fk_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp],
         "lrm_ik_cpu": [vp, sz, vp, vp, vp, vp, vp, vp],
         "lrm_fk_cpu": [vp, sz, vp, vp, vp, vp],
+        "lrm_pose_ik_compile_dev": [vp, sz, vp, sz, vp, vp],
+        "lrm_dbg_pose_ik_compile_host": [vp, sz, vp, sz, vp],
+        "lrm_ik_posed_dev": [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_fk_posed_dev": [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp],
+        "lrm_ik_posed_cpu": [vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
+        "lrm_fk_posed_cpu": [vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -149,6 +155,8 @@ def load():
     L.lrm_release_workspaces.restype = None
     L.lrm_posed_workspace_bytes.argtypes = [sz, sz]
     L.lrm_posed_workspace_bytes.restype = sz
+    L.lrm_posed_ik_workspace_bytes.argtypes = [sz, sz]
+    L.lrm_posed_ik_workspace_bytes.restype = sz
     _lib = L
     return L
 
@@ -375,6 +383,56 @@ def apply_fk_cpu(angles, leg, quat=None):
     ms = C.c_double(0)
     check(load().lrm_fk_cpu(_ptr(ang), len(ang), _ptr(_f32(leg, (14,))), _ptr(_quat(quat)), _ptr(xyz), C.addressof(ms)))
     return xyz, ms.value
+
+
+POSE_IK_RECORD_BYTES = 128  # lrm_posed_ik_workspace_bytes(1, 1)
+
+
+def _posed_indices(n, pose_idx, leg_idx):
+    pi = None if pose_idx is None else np.ascontiguousarray(pose_idx, np.int32).reshape(n)
+    li = None if leg_idx is None else np.ascontiguousarray(leg_idx, np.uint8).reshape(n)
+    return pi, li
+
+
+def apply_ik_posed_cpu(xyz, pose_idx, leg_idx, quats, body, legs, target_idx=None, seed=None):
+    """lrm_ik_posed_cpu: query i = (target target_idx[i] of xyz, or target i; pose pose_idx[i]; leg leg_idx[i]) on the
+    host, p = target - body[pose]; indices None = target i / pose 0 / leg 0; seed None or float32[n, 3] per query
+    -> (angles float32[n, 3], status uint8[n], ms); out-of-range indices (target_idx -1 included): status 0, nan"""
+    xyz = _f32(xyz, (-1, 3))
+    ti = None if target_idx is None else np.ascontiguousarray(target_idx, np.int32).reshape(-1)
+    n = len(xyz) if ti is None else len(ti)
+    quats, body, legs = _posed_tables(quats, body, legs)
+    pi, li = _posed_indices(n, pose_idx, leg_idx)
+    if seed is not None:
+        seed = _f32(seed)
+        if seed.shape != (n, 3):
+            raise ValueError("seed: one (coxa, femur, tibia) triple per query")
+    ang, st = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+    ms = C.c_double(0)
+    check(load().lrm_ik_posed_cpu(_ptr(xyz), len(xyz), _ptr(ti), n, _ptr(pi), _ptr(li), _ptr(quats), _ptr(body), len(quats),
+                                  _ptr(legs), len(legs), _ptr(seed), _ptr(ang), _ptr(st), C.addressof(ms)))
+    return ang, st, ms.value
+
+
+def apply_fk_posed_cpu(angles, pose_idx, leg_idx, quats, body, legs):
+    """lrm_fk_posed_cpu: tip of angles[i] for (legs[leg_idx[i]], quats[pose_idx[i]]) + body[pose] -> (xyz float32[n, 3], ms)"""
+    ang = _f32(angles, (-1, 3))
+    n = len(ang)
+    quats, body, legs = _posed_tables(quats, body, legs)
+    pi, li = _posed_indices(n, pose_idx, leg_idx)
+    xyz = np.zeros_like(ang)
+    ms = C.c_double(0)
+    check(load().lrm_fk_posed_cpu(_ptr(ang), n, _ptr(pi), _ptr(li), _ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs),
+                                  _ptr(xyz), C.addressof(ms)))
+    return xyz, ms.value
+
+
+def dbg_pose_ik_compile_host(quats, legs):
+    """the IK table the host makes -> uint8[nposes, nlegs, POSE_IK_RECORD_BYTES]"""
+    quats, _, legs = _posed_tables(quats, None, legs)
+    out = np.zeros((len(quats), len(legs), POSE_IK_RECORD_BYTES), np.uint8)
+    check(load().lrm_dbg_pose_ik_compile_host(_ptr(quats), len(quats), _ptr(legs), len(legs), _ptr(out)))
+    return out
 
 
 def apply_rbdl_equiv(xyz, leg):

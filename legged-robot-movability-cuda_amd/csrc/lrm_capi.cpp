@@ -959,7 +959,7 @@ void ik_compile(const LrmLegDimensions& leg, const float* quat, LrmCompiledLeg* 
     lrm_compile_leg(leg, quat_or_default(quat), 1, L);
     LrmLegDimensions r;
     lrm_host_rotate_leg_data(quat_or_default(quat), leg, &r);
-    lrm_ik_compile(r, *L, K);
+    lrm_ik_compile(r, L->inv_rot, K);
 }
 } // namespace
 
@@ -1021,6 +1021,157 @@ int lrm_fk_cpu(const float* angles, size_t n, const LrmLegDimensions* leg, const
     const auto t0 = std::chrono::high_resolution_clock::now();
     for (size_t i = 0; i < n; i++) {
         const LrmVec3 p = lrm_fk_point(L, K, angles[3 * i], angles[3 * i + 1], angles[3 * i + 2]);
+        xyz[3 * i] = p.x;
+        xyz[3 * i + 1] = p.y;
+        xyz[3 * i + 2] = p.z;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+// ---- joint angles per (target, pose, leg) (lrm_ik_posed.hip) -------------------------------
+namespace {
+int ik_posed_tables(size_t nposes, size_t nlegs) {
+    if (nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "posed queries: nlegs > LRM_MAX_LEGS");
+    if (nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "posed queries: nposes does not fit the int32 pose index");
+    if (nposes * nlegs > (size_t)UINT32_MAX) return fail(LRM_EINVAL, "posed queries: more than 2^32 - 1 (pose, leg) records");
+    return LRM_OK;
+}
+int ik_posed_targets(size_t nt, const int32_t* target_idx, size_t n) {
+    if (nt > (size_t)INT32_MAX) return fail(LRM_EINVAL, "posed ik: nt does not fit the int32 target index");
+    if (!target_idx && n > nt) return fail(LRM_EINVAL, "posed ik: n > nt without target_idx");
+    return LRM_OK;
+}
+void host_pose_ik_records(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, LrmIkLeg* out) {
+    for (size_t p = 0; p < nposes; p++)
+        for (size_t l = 0; l < nlegs; l++) lrm_ik_compile_pose(legs[l], quats + 4 * p, &out[p * nlegs + l]);
+}
+} // namespace
+
+size_t lrm_posed_ik_workspace_bytes(size_t nposes, size_t nlegs) { return nposes * nlegs * sizeof(LrmIkLeg); }
+
+int lrm_pose_ik_compile_dev(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, void* ik_workspace,
+                            void* stream) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!quats || !ik_workspace) return fail(LRM_EINVAL, "null argument");
+    if ((uintptr_t)ik_workspace & 15) return fail(LRM_EINVAL, "posed ik: the ik workspace must be 16-byte aligned");
+    HIP_TRY(lrm_launch_pose_ik_compile(quats, nposes, legs, nlegs, ik_workspace, (hipStream_t)stream), "pose ik compile launch");
+    return LRM_OK;
+}
+
+int lrm_dbg_pose_ik_compile_host(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, void* records_out) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!quats || !records_out) return fail(LRM_EINVAL, "null argument");
+    host_pose_ik_records(quats, nposes, legs, nlegs, (LrmIkLeg*)records_out);
+    return LRM_OK;
+}
+
+int lrm_ik_posed_dev(const float* x, const float* y, const float* z, size_t nt, const int32_t* target_idx, size_t n,
+                     const int32_t* pose_idx, const uint8_t* leg_idx, const void* workspace, const void* ik_workspace, size_t nposes,
+                     size_t nlegs, const float* seed_c, const float* seed_f, const float* seed_t, float* coxa, float* femur,
+                     float* tibia, uint8_t* status, void* stream) {
+    int rc = ik_posed_tables(nposes, nlegs);
+    if (rc == LRM_OK) rc = ik_posed_targets(nt, target_idx, n);
+    if (rc != LRM_OK) return rc;
+    if (!seed_c != !seed_f || !seed_c != !seed_t) return fail(LRM_EINVAL, "posed ik: give all three seed arrays or none");
+    if (n == 0) return LRM_OK;
+    if (nposes == 0 || nlegs == 0) return fail(LRM_EINVAL, "posed queries: no pose or no leg for n > 0 queries");
+    if (!workspace || !ik_workspace) return fail(LRM_EINVAL, "posed ik: null workspace");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
+    if ((nt && (!x || !y || !z)) || !coxa || !femur || !tibia || !status) return fail(LRM_EINVAL, "null argument");
+    HIP_TRY(lrm_launch_ik_posed(x, y, z, nt, target_idx, n, pose_idx, leg_idx, workspace, ik_workspace, nposes, nlegs, seed_c, seed_f,
+                                seed_t, coxa, femur, tibia, status, (hipStream_t)stream),
+            "posed ik launch");
+    return LRM_OK;
+}
+
+int lrm_fk_posed_dev(const float* coxa, const float* femur, const float* tibia, size_t n, const int32_t* pose_idx,
+                     const uint8_t* leg_idx, const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs, float* x,
+                     float* y, float* z, void* stream) {
+    int rc = ik_posed_tables(nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (n == 0) return LRM_OK;
+    if (nposes == 0 || nlegs == 0) return fail(LRM_EINVAL, "posed queries: no pose or no leg for n > 0 queries");
+    if (!workspace || !ik_workspace) return fail(LRM_EINVAL, "posed fk: null workspace");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed fk: the workspaces must be 16-byte aligned");
+    if (!coxa || !femur || !tibia || !x || !y || !z) return fail(LRM_EINVAL, "null argument");
+    HIP_TRY(lrm_launch_fk_posed(coxa, femur, tibia, n, pose_idx, leg_idx, workspace, ik_workspace, nposes, nlegs, x, y, z,
+                                (hipStream_t)stream),
+            "posed fk launch");
+    return LRM_OK;
+}
+
+int lrm_ik_posed_cpu(const float* xyz, size_t nt, const int32_t* target_idx, size_t n, const int32_t* pose_idx,
+                     const uint8_t* leg_idx, const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs,
+                     size_t nlegs, const float* seed, float* angles, uint8_t* status, double* ms) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc == LRM_OK) rc = ik_posed_targets(nt, target_idx, n);
+    if (rc != LRM_OK) return rc;
+    if (n == 0) return LRM_OK;
+    if (nposes == 0 || nlegs == 0) return fail(LRM_EINVAL, "posed queries: no pose or no leg for n > 0 queries");
+    if ((nt && !xyz) || !quats || !angles || !status) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t i = 0; i < n; i++) {
+        const int32_t pi = pose_idx ? pose_idx[i] : 0;
+        const uint32_t li = leg_idx ? leg_idx[i] : 0u;
+        const int64_t ti = target_idx ? (int64_t)target_idx[i] : (int64_t)i;
+        if (pi < 0 || (size_t)pi >= nposes || li >= nlegs || ti < 0 || (size_t)ti >= nt) { // out of range: status 0, nan angles
+            status[i] = LRM_IK_NONE;
+            angles[3 * i] = angles[3 * i + 1] = angles[3 * i + 2] = std::nanf("");
+            continue;
+        }
+        const LrmPoseRecord& R = recs[(size_t)pi * nlegs + li];
+        const LrmIkLeg& K = iks[(size_t)pi * nlegs + li];
+        LrmVec3 p{xyz[3 * ti], xyz[3 * ti + 1], xyz[3 * ti + 2]};
+        p.x -= R.body_pos[0];
+        p.y -= R.body_pos[1];
+        p.z -= R.body_pos[2];
+        const LrmVec3 s = seed ? LrmVec3{seed[3 * i], seed[3 * i + 1], seed[3 * i + 2]} : LrmVec3{K.seed[0], K.seed[1], K.seed[2]};
+        LrmVec3 a;
+        status[i] = lrm_ik_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), &R.head.lists[0][0], K, p, s, a);
+        angles[3 * i] = a.x;
+        angles[3 * i + 1] = a.y;
+        angles[3 * i + 2] = a.z;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+int lrm_fk_posed_cpu(const float* angles, size_t n, const int32_t* pose_idx, const uint8_t* leg_idx, const float* quats,
+                     const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, float* xyz, double* ms) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (n == 0) return LRM_OK;
+    if (nposes == 0 || nlegs == 0) return fail(LRM_EINVAL, "posed queries: no pose or no leg for n > 0 queries");
+    if (!angles || !quats || !xyz) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t i = 0; i < n; i++) {
+        const int32_t pi = pose_idx ? pose_idx[i] : 0;
+        const uint32_t li = leg_idx ? leg_idx[i] : 0u;
+        if (pi < 0 || (size_t)pi >= nposes || li >= nlegs) {
+            xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = std::nanf("");
+            continue;
+        }
+        const LrmPoseRecord& R = recs[(size_t)pi * nlegs + li];
+        LrmVec3 p = lrm_fk_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[(size_t)pi * nlegs + li], angles[3 * i],
+                                 angles[3 * i + 1], angles[3 * i + 2]);
+        p.x += R.body_pos[0];
+        p.y += R.body_pos[1];
+        p.z += R.body_pos[2];
         xyz[3 * i] = p.x;
         xyz[3 * i + 1] = p.y;
         xyz[3 * i + 2] = p.z;

@@ -23,6 +23,7 @@
 //     is replaced by the default one, and a seed can never select a candidate outside the near-best set;
 //   status LRM_IK_*: from the chosen tip's distance to p in the caller's frame, in float32 (LRM_IK_TOL_F).
 #pragma once
+#include "lrm_compile_head.h"
 #include "lrm_point.h"
 
 #define LRM_IK_TOL_F 0.002f  // mm: status thresholds (twice the reference's CIRCLE_MARGIN)
@@ -55,14 +56,16 @@ LRM_HD float lrm_ik_wrapf(float a) { // [-3 pi, 3 pi] -> [-pi, pi]
     return (a < -LRM_PI_F) ? a + LRM_2PI_F : a;
 }
 
-// host: the constants of the leg AFTER rotate_leg_data.  The femur range [f_lo, f_hi] is where the tibia interval
+// The constants of the leg AFTER rotate_leg_data, from that leg and the head's inv_rot.  The femur range [f_lo, f_hi] is where the tibia interval
 // [max(tmin, aneg - f), min(tmax, apos - f)] is not empty.  A leg with no in-limit configuration at all (f_lo > f_hi
 // or aneg > apos) keeps the femur's own range: its tibia is clamped into the tibia limits only, the absolute limit is
 // then not met, and every point gets status 3 or 4.
 // back: the matrix of qtInvRotate(quat, .) is I + 2 inv_rot; its inverse, in double and rounded once, takes the FK back to
 // the caller's frame.  For a unit quaternion that is qtRotate(quat, .) up to float32 rounding; the reference does not
 // normalise quaternions (several fixtures are not unit), and for those only the inverse makes FK(IK(p)) = p.
-inline void lrm_ik_compile(const LrmLegDimensions& r, const LrmCompiledLeg& L, LrmIkLeg* K) {
+// Host (the single-pose calls, lrm_capi.cpp) and device (pose_ik_compile_kernel, lrm_ik_posed.hip): float comparisons,
+// float + - * and double + - * / only, all correctly rounded on both sides, so one source gives the same bytes.
+LRM_HD void lrm_ik_compile(const LrmLegDimensions& r, const float inv_rot[9], LrmIkLeg* K) {
     K->C = r.coxa_length;
     K->F = r.femur_length;
     K->T = r.tibia_length;
@@ -90,7 +93,7 @@ inline void lrm_ik_compile(const LrmLegDimensions& r, const LrmCompiledLeg& L, L
     K->seed[1] = 0.5f * (K->fmin + K->fmax);
     K->seed[2] = 0.5f * (K->tmin + K->tmax);
     double a[9], inv[9];
-    for (int k = 0; k < 9; k++) a[k] = 2.0 * (double)L.inv_rot[k] + ((k % 4 == 0) ? 1.0 : 0.0);
+    for (int k = 0; k < 9; k++) a[k] = 2.0 * (double)inv_rot[k] + ((k % 4 == 0) ? 1.0 : 0.0);
     inv[0] = a[4] * a[8] - a[5] * a[7];
     inv[1] = a[2] * a[7] - a[1] * a[8];
     inv[2] = a[1] * a[5] - a[2] * a[4];
@@ -103,6 +106,17 @@ inline void lrm_ik_compile(const LrmLegDimensions& r, const LrmCompiledLeg& L, L
     const double det = a[0] * inv[0] + a[1] * inv[3] + a[2] * inv[6];
     for (int k = 0; k < 9; k++) K->back[k] = (float)(inv[k] / det);
     K->pad_[0] = K->pad_[1] = K->pad_[2] = K->pad_[3] = 0.f;
+}
+
+// The constants of (leg, quat) as the single-pose calls build them: lrm_rotate_leg for the limits, the inv_rot of
+// lrm_compile_head.  One entry of the posed IK table (lrm_ik_posed.hip), on the host and on the device; the device can
+// differ from the host only where lrm_rotate_leg's double asin does (lrm_compile_head.h).
+LRM_HD void lrm_ik_compile_pose(const LrmLegDimensions& leg, const float quat[4], LrmIkLeg* K) {
+    LrmLegDimensions r;
+    lrm_rotate_leg(quat, leg, &r);
+    float inv_rot[9];
+    lrm_rot_coefficients(lrm_q_invert(LrmQuat{quat[0], quat[1], quat[2], quat[3]}), inv_rot);
+    lrm_ik_compile(r, inv_rot, K);
 }
 
 // p (caller's frame) -> coxa frame: the operations of lrm_reach_global + lrm_reach_circles, in their order

@@ -101,3 +101,15 @@ hipError_t lrm_launch_pose_compile(const float* quats, const float* body, size_t
 hipError_t lrm_launch_posed(const float* x, const float* y, const float* z, size_t n, const int32_t* pose_idx,
                             const uint8_t* leg_idx, const void* records, size_t nposes, size_t nlegs, uint8_t* mask,
                             uint8_t* valid, float* dx, float* dy, float* dz, hipStream_t st);
+
+// Joint angles per (target, pose, leg) (lrm_ik_posed.hip).  ik_records: nposes x nlegs LrmIkLeg (lrm_ik.h), entry of
+// (pose, leg) at pose * nlegs + leg, next to the pose records above.  target_idx null: query i takes target i.
+hipError_t lrm_launch_pose_ik_compile(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, void* ik_records,
+                                      hipStream_t st);
+hipError_t lrm_launch_ik_posed(const float* x, const float* y, const float* z, size_t nt, const int32_t* target_idx, size_t n,
+                               const int32_t* pose_idx, const uint8_t* leg_idx, const void* records, const void* ik_records,
+                               size_t nposes, size_t nlegs, const float* seed_c, const float* seed_f, const float* seed_t,
+                               float* coxa, float* femur, float* tibia, uint8_t* status, hipStream_t st);
+hipError_t lrm_launch_fk_posed(const float* coxa, const float* femur, const float* tibia, size_t n, const int32_t* pose_idx,
+                               const uint8_t* leg_idx, const void* records, const void* ik_records, size_t nposes, size_t nlegs,
+                               float* x, float* y, float* z, hipStream_t st);

@@ -209,6 +209,17 @@ def footholds(bx, by, bz, tx, ty, tz, legs, quat=None, nominal=None, count=None,
     return count, best, best_d2
 
 
+def footholds_layout(nb, nlegs, device):
+    """(pose_idx int32, leg_idx uint8) of footholds()' [l*nb + b] order with one pose per body: entry l*nb + b is
+    (b, l), so that ps.ik(tx, ty, tz, *footholds_layout(nb, nlegs, dev), target_idx=best.view(-1)) solves every chosen
+    foothold in one launch.  footholds() uses its legs as given and measures in the clouds' frame: give the PoseSet
+    those same (already rotated) legs and, per body, the identity quaternion and the body position."""
+    torch = _torch()
+    pose = torch.arange(nb, dtype=torch.int32, device=device).repeat(nlegs)
+    leg = torch.arange(nlegs, dtype=torch.uint8, device=device).repeat_interleave(nb)
+    return pose, leg
+
+
 def positionability(bx, by, bz, tx, ty, tz, legs, quats, reference_culls=0, active=None, out=None):
     """lrm_positionability_dev: the orientation sweep of robot_full_struct on device-resident clouds and masks.
     reference_culls: 0 none, 2 the per-orientation cylinder culls.  -> (accepted uint8[nb] on the device, kernel ms)"""
@@ -285,9 +296,10 @@ class PoseSet:
     records from device-resident quaternions (and body positions) on the current stream; reach_dist() answers queries
     (target, pose, leg).  Both only launch: with check=False, reach_dist can be captured in a graph next to update()
     and replayed after new poses were copied into the captured quaternion tensor.  The arithmetic is LRM_MODE_STRICT's,
-    whatever set_mode says."""
+    whatever set_mode says.  ik=True: the set also owns the table of IK constants (128 bytes per (pose, leg)), update()
+    compiles it too on the same stream, and ik() / fk() answer joint-angle queries."""
 
-    def __init__(self, legs, nposes_max, device=None):
+    def __init__(self, legs, nposes_max, device=None, ik=False):
         torch = _torch()
         self.legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
         if not 1 <= len(self.legs) <= 8:
@@ -298,6 +310,10 @@ class PoseSet:
         self.device = torch.device(device if device is not None else "cuda")
         nbytes = _capi.load().lrm_posed_workspace_bytes(self.nposes_max, len(self.legs))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.ik_workspace = None
+        if ik:
+            nbytes = _capi.load().lrm_posed_ik_workspace_bytes(self.nposes_max, len(self.legs))
+            self.ik_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.nposes = 0
 
     @property
@@ -320,22 +336,20 @@ class PoseSet:
         with torch.cuda.device(self.device):
             _capi.check(_capi.load().lrm_pose_compile_dev(_dp(quats), _dp(body), nposes, _capi._ptr(self.legs), self.nlegs,
                                                           _dp(self.workspace), _stream(self.workspace)))
+            if self.ik_workspace is not None:
+                _capi.check(_capi.load().lrm_pose_ik_compile_dev(_dp(quats), nposes, _capi._ptr(self.legs), self.nlegs,
+                                                                 _dp(self.ik_workspace), _stream(self.workspace)))
         self.nposes = nposes
         return self
 
-    def reach_dist(self, x, y, z, pose_idx=None, leg_idx=None, mask=None, out=None, valid=None, want_dist=True, check=True):
-        """Query i = (x[i], y[i], z[i]) for pose pose_idx[i] (int32; None: pose 0) and leg leg_idx[i] (uint8; None:
-        leg 0) -> (mask uint8[n], field float32 (3, n), valid uint8[n]); with want_dist=False only the mask (field and
-        valid None).  check=True validates the indices on the host (one synchronisation); check=False leaves an
-        out-of-range index to the kernel (mask 0, valid 0, nan field): the form for graph capture."""
+    def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
-        n = _check_f32(x, y, z)
         if self.nposes == 0:
             raise ValueError("PoseSet: update() before the first query")
-        if x.device != self.workspace.device:
+        if ref.device != self.workspace.device:
             raise ValueError("queries and poses must live on one device")
-        _check_out(pose_idx, x, torch.int32, n, "pose_idx")
-        _check_out(leg_idx, x, torch.uint8, n, "leg_idx")
+        _check_out(pose_idx, ref, torch.int32, n, "pose_idx")
+        _check_out(leg_idx, ref, torch.uint8, n, "leg_idx")
         if pose_idx is not None and pose_idx.numel() != n or leg_idx is not None and leg_idx.numel() != n:
             raise ValueError("pose_idx / leg_idx: one index per query")
         if check and n:
@@ -345,6 +359,67 @@ class PoseSet:
                     raise ValueError(f"pose_idx outside [0, {self.nposes})")
             if leg_idx is not None and int(leg_idx.max()) >= self.nlegs:
                 raise ValueError(f"leg_idx outside [0, {self.nlegs})")
+
+    def ik(self, x, y, z, pose_idx=None, leg_idx=None, target_idx=None, seed=None, out=None, status=None, check=True):
+        """lrm_ik_posed_dev.  Query i takes target target_idx[i] (int32) of (x, y, z), or target i without target_idx,
+        minus the body position of pose pose_idx[i], and solves leg leg_idx[i] under that pose's quaternion.  seed:
+        None or three float32 tensors, one angle per query.  -> (angles float32 (3, n), status uint8[n]).  check=True
+        validates pose_idx and leg_idx on the host (one synchronisation); target_idx is never validated: an index
+        outside [0, len(x)), the -1 of footholds() included, gives status 0 and nan angles.  One launch."""
+        torch = _torch()
+        nt = _check_f32(x, y, z)
+        if self.ik_workspace is None:
+            raise ValueError("PoseSet: built without ik=True")
+        if target_idx is not None:
+            n = target_idx.numel()
+            _check_out(target_idx, x, torch.int32, n, "target_idx")
+        else:
+            n = nt
+        self._check_indices(x, n, pose_idx, leg_idx, check)
+        if seed is not None:
+            if len(seed) != 3:
+                raise ValueError("seed: three tensors (coxa, femur, tibia) or None")
+            if _check_f32(*seed) != n or seed[0].device != x.device:
+                raise ValueError("seed: one angle per query, on the queries' device")
+        if out is None:
+            out = torch.empty((3, n), dtype=torch.float32, device=x.device)
+        if status is None:
+            status = torch.empty(n, dtype=torch.uint8, device=x.device)
+        _check_field(out, x, n)
+        _check_out(status, x, torch.uint8, n, "status")
+        sc, sf, st = (None, None, None) if seed is None else seed
+        with torch.cuda.device(x.device):
+            _capi.check(_capi.load().lrm_ik_posed_dev(_dp(x), _dp(y), _dp(z), nt, _dp(target_idx), n, _dp(pose_idx), _dp(leg_idx),
+                                                      _dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
+                                                      _dp(sc), _dp(sf), _dp(st), _dp(out[0]), _dp(out[1]), _dp(out[2]),
+                                                      _dp(status), _stream(x)))
+        return out, status
+
+    def fk(self, coxa, femur, tibia, pose_idx=None, leg_idx=None, out=None, check=True):
+        """lrm_fk_posed_dev: the tip of angles i for leg leg_idx[i] under pose pose_idx[i], plus that pose's body
+        position -> float32 (3, n).  One launch."""
+        torch = _torch()
+        n = _check_f32(coxa, femur, tibia)
+        if self.ik_workspace is None:
+            raise ValueError("PoseSet: built without ik=True")
+        self._check_indices(coxa, n, pose_idx, leg_idx, check)
+        if out is None:
+            out = torch.empty((3, n), dtype=torch.float32, device=coxa.device)
+        _check_field(out, coxa, n)
+        with torch.cuda.device(coxa.device):
+            _capi.check(_capi.load().lrm_fk_posed_dev(_dp(coxa), _dp(femur), _dp(tibia), n, _dp(pose_idx), _dp(leg_idx),
+                                                      _dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
+                                                      _dp(out[0]), _dp(out[1]), _dp(out[2]), _stream(coxa)))
+        return out
+
+    def reach_dist(self, x, y, z, pose_idx=None, leg_idx=None, mask=None, out=None, valid=None, want_dist=True, check=True):
+        """Query i = (x[i], y[i], z[i]) for pose pose_idx[i] (int32; None: pose 0) and leg leg_idx[i] (uint8; None:
+        leg 0) -> (mask uint8[n], field float32 (3, n), valid uint8[n]); with want_dist=False only the mask (field and
+        valid None).  check=True validates the indices on the host (one synchronisation); check=False leaves an
+        out-of-range index to the kernel (mask 0, valid 0, nan field): the form for graph capture."""
+        torch = _torch()
+        n = _check_f32(x, y, z)
+        self._check_indices(x, n, pose_idx, leg_idx, check)
         if mask is None:
             mask = torch.empty(n, dtype=torch.uint8, device=x.device)
         _check_out(mask, x, torch.uint8, n, "mask")
