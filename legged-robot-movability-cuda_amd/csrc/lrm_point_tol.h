@@ -57,8 +57,9 @@
 #endif
 // all lanes of the wave agree (device) / this point (host)
 #if defined(__HIP_DEVICE_COMPILE__)
-#define LRM_TOL_ALL(c) (__all(c))
-#define LRM_TOL_ANY(c) (__any(c))
+// (the ballot compared on the scalar unit: __all / __any turn the lane mask into a 0 / 1 register and compare that, two VALU instructions)
+#define LRM_TOL_ALL(c) (__builtin_amdgcn_ballot_w64(!(c)) == 0ull)
+#define LRM_TOL_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0ull)
 #else
 #define LRM_TOL_ALL(c) (c)
 #define LRM_TOL_ANY(c) (c)
@@ -94,6 +95,13 @@
 #ifndef LRM_TOL_DIET
 #define LRM_TOL_DIET 1
 #endif
+// -DLRM_PHASE_MARKS (tools/valu_phases.py only, never shipped): an s_nop at every phase boundary of the table evaluation, named in
+// the assembly by a comment; "rare" marks open the blocks that are not on the common path.
+#if defined(LRM_PHASE_MARKS) && defined(__HIP_DEVICE_COMPILE__)
+#define LRM_PHASE(name) asm volatile("s_nop 0 ; LRM_PHASE " name ::: "memory")
+#else
+#define LRM_PHASE(name) ((void)0)
+#endif
 // min(|a|, |b|, c) and max(a, |b|) as ONE instruction each: fminf(fabsf(a), fabsf(b)) compiles to a canonicalising
 // v_max_f32 per operand in front of the v_min_f32 (IEEE mode), six instructions for a four-way minimum instead of two.
 // NaN operands are ignored, exactly as fminf / fmaxf ignore them.
@@ -111,6 +119,16 @@ __device__ __forceinline__ float lrm_max_a(float a, float b) {
 #else
 LRM_HD float lrm_min3_aa(float a, float b, float c) { return fminf(fminf(fabsf(a), fabsf(b)), c); }
 LRM_HD float lrm_max_a(float a, float b) { return fmaxf(a, fabsf(b)); }
+#endif
+// min(|a|, |b|) as one instruction (the same value as fminf(fabsf(a), fabsf(b)), nan only when both are)
+#if defined(__HIP_DEVICE_COMPILE__) && LRM_TOL_DIET
+__device__ __forceinline__ float lrm_min_aa(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+#else
+LRM_HD float lrm_min_aa(float a, float b) { return fminf(fabsf(a), fabsf(b)); }
 #endif
 
 struct LrmTolTables {
@@ -454,13 +472,15 @@ inline thread_local unsigned long long lrm_tab_host_seconds = 0; // host statist
 // the flipped candidate | 19 its vector is the offset from a yaw-limit plane (the alternative of one_leg.cu:258-274 was taken, or a
 // clamped candidate collapsed onto it) | 20 the flag.
 template <bool kInfo = false>
-LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p, uint32_t& doubt, uint32_t* info = nullptr) {
+LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p, uint32_t& doubt, uint32_t* info = nullptr, float* band_out = nullptr) {
+    LRM_PHASE("1_map_sector_operands");
     const float* a = L.aff;
     const float x = __builtin_fmaf(a[0], p.x, __builtin_fmaf(a[1], p.y, __builtin_fmaf(a[2], p.z, a[3])));
     const float y = __builtin_fmaf(a[4], p.x, __builtin_fmaf(a[5], p.y, __builtin_fmaf(a[6], p.z, a[7])));
     const float z = __builtin_fmaf(a[8], p.x, __builtin_fmaf(a[9], p.y, __builtin_fmaf(a[10], p.z, a[11])));
     // non-finite input: the band is nan/inf and every "> band" test fails closed (doubt)
     const float band = __builtin_fmaf(fabsf(p.x) + fabsf(p.y) + fabsf(p.z), L.band_slope, L.band_base);
+    if (band_out) *band_out = band; // (LRM_MODE_TOL_REL's threshold is a multiple of it: the kernel does not form |p|_1 twice)
     const float tau = band * LRM_TOL_TIE;
     const float m2 = __builtin_fmaf(y, y, x * x);
     const float rs = LRM_FAST_RSQ(m2);
@@ -473,9 +493,11 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
                          ((lrm_f2u(um) >> 28) & 8u);
     constexpr uint32_t kLutD = lrm_tol_lut(false), kLutF = lrm_tol_lut(true);
     const uint32_t codeD = (kLutD >> (pat << 1)) & 3u, codeF = (kLutF >> (pat << 1)) & 3u;
-    const bool inD = (pat & 5u) == 1u, inF = (pat & 5u) == 4u;
+    // Decisions are kept as booleans combined with & | ! (lane masks on the scalar unit), never selected with ?: or chained with
+    // && / || (which materialise 0 / 1 in registers or branch on the exec mask).
+    const bool inF = (pat & 5u) == 4u; // the flipped candidate lies inside [min, max]; the direct one when (pat & 5) == 1
     const float ymin = lrm_min3_aa(wm, um, lrm_min3_aa(wM, uM, 3.0e38f));
-    uint32_t lu = (!(ymin > band) || !(r > LRM_TOL_RMIN)) ? LRM_TD_YAW : 0u;
+    uint32_t lu = (!(ymin > band) | !(r > LRM_TOL_RMIN)) ? LRM_TD_YAW : 0u;
     const bool two = codeD != codeF;
     // plane point of a candidate kind: abscissa {r, -r, uM, um}[code], offset {0, 0, wM, wm}[code].  Every `?:` below
     // selects between values that exist already: straight-line v_cndmask code, no branches.
@@ -493,21 +515,28 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
     uint32_t cD, cF, sD, sF, fbase;
     float lbD, lbF;
     bool band_doubt;
-    if (anyfar) lrm_toltab_lookup2<true>(G, far, band, xD, xF, z, cD, cF, sD, sF, fbase, lbD, lbF, band_doubt);
-    else lrm_toltab_lookup2<false>(G, false, band, xD, xF, z, cD, cF, sD, sF, fbase, lbD, lbF, band_doubt);
+    LRM_PHASE("2_lookups_bounds");
+    if (anyfar) {
+        LRM_PHASE("rare_outer_grid");
+        lrm_toltab_lookup2<true>(G, far, band, xD, xF, z, cD, cF, sD, sF, fbase, lbD, lbF, band_doubt);
+    } else {
+        LRM_PHASE("2_lookups_bounds");
+        lrm_toltab_lookup2<false>(G, false, band, xD, xF, z, cD, cF, sD, sF, fbase, lbD, lbF, band_doubt);
+    }
+    LRM_PHASE("3_order_resolve_plane");
     lu |= band_doubt ? LRM_TD_YAW : 0u;
     // Which candidate first: the one with the smaller lower bound w^2 + lb^2 of its squared distance (lb: the cell's bound of
     // the in-plane part).  A candidate that may be valid has lb = 0; inside the yaw range (w = 0) its bound is 0 and it goes
     // first -- the reach flag is always taken from the first candidate.  Equal bounds (the two candidates are one
     // configuration): the one inside the range.
     const float bD = __builtin_fmaf(lbD, lbD, wD * wD), bF = __builtin_fmaf(lbF, lbF, wF * wF);
-    const bool firstD = inF ? (bD < bF) : (bD <= bF);
+    const bool firstD = (bD < bF) | ((bD <= bF) & !inF);
     const uint32_t code0 = firstD ? codeD : codeF;
     const float w0 = firstD ? wD : wF, x0 = firstD ? xD : xF;
     const uint32_t cell0 = lrm_toltab_resolve(G, firstD ? cD : cF, firstD ? sD : sF, fbase); // only the candidate that is evaluated
     const float b1 = firstD ? bF : bD;
     const bool lim0 = code0 >= 2u;
-    const bool in0 = firstD ? inD : inF;
+    const bool in0 = (pat & 5u) == (firstD ? 1u : 4u); // inD / inF of the first candidate: one select of constants, one compare
     // ---- first candidate ----
     float du0, dz0;
     bool valid0;
@@ -515,43 +544,44 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
     bool offW = false;
     lrm_tol_plane_tab<kInfo>(G, cell0, x0, z, band, tau, du0, dz0, valid0, lu, &row0);
     if (kInfo) row0 |= cell0;
+    LRM_PHASE("4_collapse_alternative_need");
     // A candidate clamped to a yaw limit whose plane point is valid collapses to the offset from that plane, unless
     // sqrt(du^2 + w^2 + dz^2) rounds to |w| (see lrm_dist_tol_t): q / w^2 above 2^-20 collapses, below 2^-25 stays, between: doubt
     {
         const float q = __builtin_fmaf(du0, du0, dz0 * dz0), w2 = w0 * w0;
-        const bool lv = lim0 && valid0, big = q > w2 * 9.6e-7f;
-        const bool collapse = lv && big;
+        const bool lv = lim0 & valid0, big = q > w2 * 9.6e-7f;
+        const bool collapse = lv & big;
         du0 = collapse ? 0.f : du0;
         dz0 = collapse ? 0.f : dz0;
         if (kInfo) offW = collapse;
-        lu |= (lv && !big) ? LRM_TD_LIMIT : 0u; // (below 2^-25 the reference keeps the vector: one plane point in 1e6, left to the bit-exact code too)
+        lu |= (lv & !big) ? LRM_TD_LIMIT : 0u; // (below 2^-25 the reference keeps the vector: one plane point in 1e6, left to the bit-exact code too)
     }
     const float n0 = __builtin_fmaf(du0, du0, __builtin_fmaf(w0, w0, dz0 * dz0));
-    const bool flag = valid0 && in0;
+    const bool flag = valid0 & in0;
     // ---- yaw-limit alternative (one_leg.cu:258-274) of a valid first candidate: the nearer limit plane wins when it is closer ----
     uint32_t codeW;
     float duW, wW, dzW;
     {
-        const float aM = fabsf(wM), am = fabsf(wm);
-        const float dl = fminf(aM, am), dl2 = dl * dl;
+        const float dl = lrm_min_aa(wM, wm), dl2 = dl * dl;
         const float thr = tau * __builtin_fmaf(2.0f, dl, tau);
         // in doubt: the two distances tie, or the alternative is (or may be) taken and the two limit planes tie
-        const bool tie = !(fabsf(n0 - dl2) > thr) || (!(n0 < dl2 - thr) && !(fabsf(aM - am) > tau));
-        lu |= (flag && tie) ? LRM_TD_LIMIT : 0u;
-        const bool alt = flag && (n0 > dl2);
-        const bool useM = aM < am;
+        const bool tie_n = !(fabsf(n0 - dl2) > thr), maybe_alt = !(n0 < dl2 - thr), tie_l = !(fabsf(fabsf(wM) - fabsf(wm)) > tau);
+        const bool tie = tie_n | (maybe_alt & tie_l);
+        lu |= (flag & tie) ? LRM_TD_LIMIT : 0u;
+        const bool alt = flag & (n0 > dl2);
+        const bool useM = fabsf(wM) < fabsf(wm);
         const uint32_t codeL = useM ? 2u : 3u;
         const float wL = useM ? wM : wm;
         codeW = alt ? codeL : code0;
-        if (kInfo) offW = offW || alt;
+        if (kInfo) offW = offW | alt;
         duW = alt ? 0.f : du0;
         dzW = alt ? 0.f : dz0;
         wW = alt ? wL : w0;
     }
     // ---- the second one only when it can still win: not below its lower bound by more than the tie band ----
-    const bool need = two && !flag && !(n0 < b1 - tau * __builtin_fmaf(2.0f, LRM_FAST_SQRT(n0), tau));
-    bool infoB = false;
-    uint32_t codeB = 0;
+    const bool need = two & !flag & !(n0 < b1 - tau * __builtin_fmaf(2.0f, LRM_FAST_SQRT(n0), tau));
+    uint32_t codeC = code0; // kInfo: the winning candidate's own kind (codeW names the limit plane when the alternative won)
+    bool flipC = !firstD;   //        and whether it is the flipped one
 #if defined(LRM_TAB_EXP_NO_SECOND) // timing experiment (wrong results): the second candidate is never evaluated
     if (false) {
 #else
@@ -560,6 +590,7 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
 #if !defined(__HIP_DEVICE_COMPILE__)
         lrm_tab_host_seconds++;
 #endif
+        LRM_PHASE("rare_second_candidate");
         const uint32_t code1 = firstD ? codeF : codeD; // the other candidate's operands: selected here, where they are needed
         const uint32_t cell1 = lrm_toltab_resolve(G, firstD ? cF : cD, firstD ? sF : sD, fbase);
         const float w1 = firstD ? wF : wD, x1 = firstD ? xF : xD;
@@ -570,29 +601,30 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
         uint32_t row1 = 0;
         lrm_tol_plane_tab<kInfo>(G, cell1, x1, z, band, tau, du1, dz1, valid1, bd, &row1);
         const float q = __builtin_fmaf(du1, du1, dz1 * dz1), w2 = w1 * w1;
-        const bool lv = lim1 && valid1, big = q > w2 * 9.6e-7f;
-        const bool collapse = lv && big;
+        const bool lv = lim1 & valid1, big = q > w2 * 9.6e-7f;
+        const bool collapse = lv & big;
         du1 = collapse ? 0.f : du1;
         dz1 = collapse ? 0.f : dz1;
-        bd |= (lv && !big) ? LRM_TD_LIMIT : 0u;
+        bd |= (lv & !big) ? LRM_TD_LIMIT : 0u;
         const float n1 = __builtin_fmaf(du1, du1, __builtin_fmaf(w1, w1, dz1 * dz1));
         // distance_circles' pick (one_leg.cu:334): both invalid here (a valid first candidate never asks for the second): the shorter one
         const float nmin = LRM_FAST_SQRT(fminf(n0, n1));
         const float thr = tau * __builtin_fmaf(2.0f, nmin, tau);
         bd |= !(fabsf(n0 - n1) > thr) ? LRM_TD_PICK : 0u;
         lu |= need ? bd : 0u;
-        const bool useB = need && !(n0 < n1);
+        const bool useB = need & !(n0 < n1);
         codeW = useB ? code1 : codeW;
         if (kInfo) { // the second candidate won: its row, its kind, the other flip; its vector is an offset when it collapsed
             row0 = useB ? (row1 | cell1) : row0;
-            offW = useB ? collapse : offW;
-            infoB = useB;
-            codeB = code1;
+            offW = (useB & collapse) | (!useB & offW);
+            codeC = useB ? code1 : codeC;
+            flipC = (useB & firstD) | (!useB & flipC);
         }
         duW = useB ? du1 : duW;
         wW = useB ? w1 : wW;
         dzW = useB ? dz1 : dzW;
     }
+    LRM_PHASE("5_rotate_back_info");
     // ---- back: rotate by the winner's yaw, then to the caller's frame ----
     const float cl = (codeW == 3u) ? cm : cM, sl = (codeW == 3u) ? sm : sM;
     const float cr = lrm_u2f(lrm_f2u(cu) ^ (codeW << 31)), sr = lrm_u2f(lrm_f2u(su) ^ (codeW << 31));
@@ -605,8 +637,6 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
     p.z = __builtin_fmaf(b[6], vx, __builtin_fmaf(b[7], vy, b[8] * vz));
     doubt |= lu;
     if (kInfo) {
-        const uint32_t codeC = infoB ? codeB : code0;   // the candidate's own kind (codeW names the limit plane when the alternative won)
-        const bool flipC = infoB ? firstD : !firstD;
         *info = row0 | (codeC << 16) | (flipC ? 0x40000u : 0u) | (offW ? 0x80000u : 0u) | (flag ? 0x100000u : 0u);
     }
     return flag;

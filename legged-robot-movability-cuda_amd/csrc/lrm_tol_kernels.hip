@@ -360,7 +360,7 @@ constexpr int kTabSegCap = LRM_TOL_TAB_SEG_CAP; // doubt slots per workgroup of 
 #define LRM_SHORT_TAIL_WAIT 1
 #endif
 constexpr int kShortCap = LRM_SHORT_CAP;
-static_assert(kShortCap >= 64, "an emptied segment holds one round of a wave");
+static_assert(kShortCap == 64, "an emptied segment holds exactly one round of a wave, and the in-loop flush replays one record per lane: a larger cap would drop records");
 __device__ __forceinline__ void wave_lds_fence_tol() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 constexpr int kTabBoundVecs = LRM_TT_NB * LRM_TT_NB * 4 / 16; // 16-byte pieces of the inner grid's bounds
 static_assert(kTabBoundVecs % kBlock == 0, "every thread stages the same number of pieces");
@@ -457,6 +457,7 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
         const bool live = i < n32;
         const size_t rbase = (size_t)blockIdx.x * kBlock + (size_t)round * stride;
         const uint32_t toff = lrm_opaque(toff0), tid_o = lrm_opaque(threadIdx.x);
+        LRM_PHASE("0_loop_head_prefetch");
         LrmVec3 p = p_next;
 #if LRM_TAB_PREFETCH2
         {   // the points of the next two rounds are in flight while this one is evaluated
@@ -485,16 +486,19 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
         const LrmVec3 p_in = p; // kept for the queue record (three registers; re-loading it cost a pushing wave an L2 round trip)
         uint32_t info = 0; // kShort: what the evaluation decided (the tail replays the winner's value chain from it)
 #if defined(LRM_EXP_NOINFO) // timing experiment (wrong results): the decisions are not packed
-        const bool m = lrm_tab_point<false>(L, G, p, doubt, &info) && live;
+        float band = 0.f;
+        const bool m = lrm_tab_point<false>(L, G, p, doubt, &info, &band) && live;
 #else
-        const bool m = lrm_tab_point<kShort>(L, G, p, doubt, &info) && live;
+        float band = 0.f; // the point's decision band (mm)
+        const bool m = lrm_tab_point<kShort>(L, G, p, doubt, &info, &band) && live;
 #endif
+        LRM_PHASE("6_short_test_stores_queues");
         doubt = live ? ((doubt & 0xffffu) | (selftest & 1u)) : 0u; // selftest: every point goes to the fix-up
         bool is_short = false;
         if (kShort) { // LRM_MODE_TOL_REL: a vector shorter than the threshold (and not in doubt) gets its value chain replayed strictly
             const float nn = __builtin_fmaf(p.x, p.x, __builtin_fmaf(p.y, p.y, p.z * p.z));
-            const float short_mm = lrm_tol_rel_threshold(L, p_in); // (from the point kept for the queue record: nothing more stays live across the evaluation)
-            is_short = live && doubt == 0u && !(nn >= short_mm * short_mm);
+            const float short_mm = fmaxf(LRM_TOL_REL_MM, LRM_TOL_REL_BANDS * band); // lrm_tol_rel_threshold of the point, from the band the evaluation formed
+            is_short = live & (doubt == 0u) & !(nn >= short_mm * short_mm);
         }
         if (live) {
             if (kAoS) {
@@ -530,13 +534,15 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
                 // the filtered code redo them whole, 0.71 ms per 1e7 points; profiles/r04_bench_a.json).  The earlier stores of the
                 // same points came from this wave: they are complete before the replayed ones go out.
                 if (wq + (uint32_t)__popcll(sm) > (uint32_t)kShortCap) { // wave-uniform
+                    LRM_PHASE("rare_flush");
                     __builtin_amdgcn_s_waitcnt(0); // vmcnt(0) expcnt(0) lgkmcnt(0): this wave's stores have reached the L2
                     replay_records(s_short + 5u * wave_s * (uint32_t)kShortCap, wq, (uint32_t)lane);
                     wave_lds_fence_tol();
                     wq = 0;
                 }
+                LRM_PHASE("6_short_test_stores_queues");
                 const uint32_t qs = wq + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-                if (is_short) { // (at most 64 records per round, kShortCap >= 64: they fit)
+                if (is_short) { // (at most 64 records per round, kShortCap == 64: they fit)
                     uint32_t* r = s_short + 5u * (wave_s * (uint32_t)kShortCap + qs);
                     r[0] = i;
                     r[1] = lrm_f2u(p_in.x);
@@ -549,6 +555,7 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
         }
         const uint64_t dm = __ballot(doubt != 0); // queue A: per-workgroup segment, slots from an LDS counter
         if (dm) {
+            LRM_PHASE("rare_doubt_push");
             uint32_t qb = 0;
             if (lane == 0) qb = atomicAdd(&s_qn, (uint32_t)__popcll(dm));
             qb = (uint32_t)__builtin_amdgcn_readfirstlane((int)qb);
@@ -557,7 +564,9 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
                 if (qs < (uint32_t)kTabSegCap) seg[qs] = QueueRec{i, p_in.x, p_in.y, p_in.z}; // beyond: the count tells the fix-up to redo the workgroup
             }
         }
+        LRM_PHASE("6_short_test_stores_queues");
     }
+    LRM_PHASE("end_of_loop");
     if (kShort && lane == 0) s_wcnt[wave_s] = wq;
 #if LRM_SHORT_TAIL_WAIT
     // The replayed vectors below overwrite tolerance vectors stored by OTHER waves of this workgroup: every wave first waits until
