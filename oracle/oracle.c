@@ -572,6 +572,20 @@ void orc_reach_any(const float* bodies, size_t nb, const float* targets, size_t 
         }
 }
 
+/* every (leg, body, target) bit of reachable_rotate_leg, for brute-force references:
+ * out[(leg*nb + b)*nt + t]; nothing is skipped and nothing stops early */
+void orc_reach_pairs(const float* bodies, size_t nb, const float* targets, size_t nt,
+                     const orc_leg_t* legs, size_t nlegs, const float quat[4], uint8_t* out) {
+    v4 q = ld4(quat);
+    for (size_t l = 0; l < nlegs; l++)
+        for (size_t b = 0; b < nb; b++) {
+            v3 body = ld3(bodies + 3 * b);
+            uint8_t* row = out + (l * nb + b) * nt;
+            for (size_t t = 0; t < nt; t++)
+                row[t] = (uint8_t)(reachable_rotate_leg(ld3(targets + 3 * t), body, q, &legs[l]) != 0);
+        }
+}
+
 /* in_sphere collision.cu.h:5-10 */
 int orc_in_sphere(float radius, const float c[3], const float t[3]) {
     float dx = c[0] - t[0], dy = c[1] - t[1], dz = c[2] - t[2];

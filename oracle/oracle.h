@@ -68,6 +68,10 @@ int orc_reachable_rotate_leg(const float target[3], const float body[3], const f
 void orc_reach_any(const float* bodies, size_t nb, const float* targets, size_t nt,
                    const orc_leg_t* legs, size_t nlegs, const float quat[4], uint8_t* out);
 
+/* the same test for every triple, nothing skipped: out[(leg*nb + b)*nt + t] = reachable_rotate_leg's bit */
+void orc_reach_pairs(const float* bodies, size_t nb, const float* targets, size_t nt,
+                     const orc_leg_t* legs, size_t nlegs, const float quat[4], uint8_t* out);
+
 /* in_sphere / in_cylinder, collision.cu.h:5-23 (norm3df restated as sqrtf of the sum) */
 int orc_in_sphere(float radius, const float c[3], const float t[3]);
 int orc_in_cylinder(float radius, float plus_z, float minus_z, const float c[3],

@@ -117,6 +117,17 @@ class Oracle(_Lib):
                                _ptr(_f32(quat)), _ptr(out))
         return out
 
+    def reach_pairs(self, bodies, targets, legs, quat=(1, 0, 0, 0)):
+        """out[leg, body, target] = reachable_rotate_leg's bit for every triple (nothing skipped, no early exit)."""
+        bodies = _f32(bodies, (-1, 3))
+        targets = _f32(targets, (-1, 3))
+        legs = self.leg_array(legs)
+        out = np.zeros((len(legs), len(bodies), len(targets)), np.uint8)
+        self.lib.orc_reach_pairs(_ptr(bodies), C.c_size_t(len(bodies)), _ptr(targets),
+                                 C.c_size_t(len(targets)), _ptr(legs), C.c_size_t(len(legs)),
+                                 _ptr(_f32(quat)), _ptr(out))
+        return out
+
     def in_sphere(self, radius, c, t):
         return self.lib.orc_in_sphere(C.c_float(radius), _ptr(_f32(c)), _ptr(_f32(t)))
 
