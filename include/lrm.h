@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_footholds_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -370,6 +370,59 @@ int lrm_footholds_dev(const float* bx, const float* by, const float* bz, size_t 
 int lrm_footholds_cpu(const float* bodies_aos, size_t nb, const float* targets_aos, size_t nt,
                       const LrmLegDimensions* legs, size_t nlegs, const float* quat, const float* nominal,
                       int32_t* count_out, int32_t* best_out, float* best_d2_out, double* ms);
+/* Foothold counts and choice per (pose, leg) of a pose table: lrm_footholds_dev for bodies that each have their own
+ * orientation, with the semantics of the posed calls, so that ONE pose table serves pose compile -> footholds -> IK.
+ * The pose table, the leg table and `workspace` are those of lrm_pose_compile_dev.  Pair (pose p, leg l, target t) is
+ * reachable iff reachability_global(t - body[p], legs[l], quats[p]) (one float32 subtraction per component): the mask
+ * of lrm_reach_dist_posed_cpu, the strict arithmetic whatever lrm_set_mode says.  There is no gravity gate
+ * (reachability_global has none), and the legs are used as given: rotate_leg_data happens per pose inside.
+ * A third caller-owned device table, lrm_posed_footholds_workspace_bytes (LRM_POSE_FOOTHOLD_BYTES = 32 per (pose, leg),
+ * 16-byte aligned), entry of (pose, leg) at pose * nlegs + leg, eight floats:
+ *   cull_center[3], cull_r2   a sphere, in the caller's frame relative to body[p], around everything leg l can reach
+ *                             under pose p.  Centre 0 and r2 = +inf (a sphere that excludes nothing) when |q|^2 is not 1
+ *                             within 1e-5 -- the reference does not normalise, a non-unit, nan or inf q makes qtInvRotate
+ *                             something else than a rotation -- or when the leg's numbers are not finite.  It never
+ *                             excludes a pair the strict test accepts; with +inf every target of the cloud is tested
+ *                             for that pose (nt x nlegs strict tests: one such pose in a large table becomes the
+ *                             launch's tail).  Normalise the quaternions before the compile.
+ *   nominal_w[3]              nominal[l] (host, nlegs x 3, an offset from the body in the BODY frame; NULL = 0) taken to
+ *                             the caller's frame by qtRotate(quats[p], .), the inverse of the rotation
+ *                             reachability_global applies to t - body (float32, no contraction)
+ *                             A zero nominal gives exactly 0 for every quaternion; otherwise a nan or inf quaternion
+ *                             gives nan (one bit pattern), and such a pose reaches nothing.
+ *   pad                       0
+ * lrm_pose_footholds_compile_dev writes it from the device-resident quaternions lrm_pose_compile_dev reads; it only
+ * launches.  lrm_footholds_posed_dev: every output has nlegs * nposes entries at [l*nposes + p], all written:
+ *   count_out     the number of reachable targets;
+ *   best_out      the reachable target with the smallest d2 (ties: the smaller index), -1 when count is 0;
+ *   best_d2_out   (may be NULL) that d2, +inf when count is 0; with c = body[p] + nominal_w (one add per component),
+ *                 d = t - c, d2 = (dx*dx + dy*dy) + dz*dz in float32 without contraction, as lrm_footholds_dev;
+ *   all_legs_out  (may be NULL, nposes) 1 iff every leg of the pose has count > 0.
+ * best_out is a valid target_idx of lrm_ik_posed_dev on the same tables with pose_idx[l*nposes + p] = p and
+ * leg_idx[l*nposes + p] = l.  Checked first: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX or more than
+ * 2^32 - 1 records give LRM_EINVAL; then nposes == 0 is a no-op; nt == 0 gives count 0, best -1, d2 +inf everywhere.
+ * Both tables must have been compiled for the same nposes and nlegs.
+ * Threading and streams: lrm_footholds_posed_dev is one of the pair kernels.  It uses their per-device tile-box buffer
+ * (clouds of 4096 targets or more) and inherits lrm_footholds_dev's rules: one host thread at a time, and no two pair
+ * launches on different clouds concurrently on one device.  The first call for a larger cloud than the buffer holds
+ * allocates (not capturable in a graph); every later call only launches, so after one call on a cloud of the largest
+ * size both compiles and the query can be captured and replayed with new poses.  Below 4096 targets it always only
+ * launches.  It does not use the compiled-leg slots.
+ * lrm_footholds_posed_cpu: AoS float3 targets, host quats / body (body may be NULL: 0), a serial loop over every
+ * (pose, leg, target) with the strict test and no culling: the reference the GPU tests compare with bit for bit;
+ * *ms = the loop's time. */
+#define LRM_POSE_FOOTHOLD_BYTES 32
+size_t lrm_posed_footholds_workspace_bytes(size_t nposes, size_t nlegs);
+int lrm_pose_footholds_compile_dev(const float* quats /* device, nposes x 4 */, size_t nposes, const LrmLegDimensions* legs /* host */,
+                                   size_t nlegs, const float* nominal /* host, nlegs x 3, BODY frame, NULL = 0 */,
+                                   void* fh_workspace, void* stream);
+int lrm_footholds_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                            const void* workspace, const void* fh_workspace, size_t nposes, size_t nlegs,
+                            int32_t* count_out, int32_t* best_out, float* best_d2_out /* may be NULL */,
+                            uint8_t* all_legs_out /* may be NULL, nposes */, void* stream);
+int lrm_footholds_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                            const LrmLegDimensions* legs, size_t nlegs, const float* nominal, int32_t* count_out,
+                            int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a
@@ -504,6 +557,10 @@ int lrm_dbg_sqrt_check_dev(uint64_t* mismatches_out, uint32_t* first_bad_out);
  * (leg, quat) followed by the body position.  The device's records must be the same bytes (tests/test_gpu_posed.py). */
 int lrm_dbg_pose_compile_host(const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
                               void* records_out);
+/* The foothold table lrm_pose_footholds_compile_dev writes (host quats here), made on the host by the same function
+ * (csrc/lrm_footholds_posed.h): nposes x nlegs x LRM_POSE_FOOTHOLD_BYTES bytes.  The device table equals it byte for byte. */
+int lrm_dbg_pose_footholds_compile_host(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                        const float* nominal, void* entries_out);
 /* The IK table lrm_pose_ik_compile_dev writes (host quats here), made on the host by the code of the single-pose calls:
  * nposes x nlegs entries of lrm_posed_ik_workspace_bytes(1, 1) bytes.  The device's must be the same bytes
  * (tests/test_gpu_ik_posed.py). */

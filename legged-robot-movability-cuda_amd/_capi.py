@@ -119,6 +119,10 @@ def load():
         "lrm_fk_posed_dev": [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp],
         "lrm_ik_posed_cpu": [vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
         "lrm_fk_posed_cpu": [vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp],
+        "lrm_pose_footholds_compile_dev": [vp, sz, vp, sz, vp, vp, vp],
+        "lrm_dbg_pose_footholds_compile_host": [vp, sz, vp, sz, vp, vp],
+        "lrm_footholds_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp],
+        "lrm_footholds_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -157,6 +161,8 @@ def load():
     L.lrm_posed_workspace_bytes.restype = sz
     L.lrm_posed_ik_workspace_bytes.argtypes = [sz, sz]
     L.lrm_posed_ik_workspace_bytes.restype = sz
+    L.lrm_posed_footholds_workspace_bytes.argtypes = [sz, sz]
+    L.lrm_posed_footholds_workspace_bytes.restype = sz
     _lib = L
     return L
 
@@ -433,6 +439,36 @@ def dbg_pose_ik_compile_host(quats, legs):
     out = np.zeros((len(quats), len(legs), POSE_IK_RECORD_BYTES), np.uint8)
     check(load().lrm_dbg_pose_ik_compile_host(_ptr(quats), len(quats), _ptr(legs), len(legs), _ptr(out)))
     return out
+
+
+POSE_FOOTHOLD_BYTES = 32  # lrm_posed_footholds_workspace_bytes(1, 1)
+
+
+def dbg_pose_footholds_compile_host(quats, legs, nominal=None):
+    """the foothold table the host makes -> float32[nposes, nlegs, 8]: {cull_center[3], cull_r2, nominal_w[3], pad}"""
+    quats, _, legs = _posed_tables(quats, None, legs)
+    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    out = np.zeros((len(quats), len(legs), POSE_FOOTHOLD_BYTES // 4), np.float32)
+    check(load().lrm_dbg_pose_footholds_compile_host(_ptr(quats), len(quats), _ptr(legs), len(legs), _ptr(nom), _ptr(out)))
+    return out
+
+
+def footholds_posed_cpu(targets, quats, body, legs, nominal=None):
+    """lrm_footholds_posed_cpu: per (leg, pose) the number of targets with reachability_global(t - body[pose], legs[leg],
+    quats[pose]), the index of the reachable target nearest body[pose] + nominal_w (nominal (nlegs, 3) in the BODY frame,
+    None = zero; -1 if none), its squared distance (+inf if none), and per pose whether every leg has one; serial host
+    loop, no culling -> (count int32[nlegs, nposes], best int32[nlegs, nposes], best_d2 float32[nlegs, nposes],
+    all_legs uint8[nposes], ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    shape = (len(legs), len(quats))
+    count, best, best_d2 = np.zeros(shape, np.int32), np.zeros(shape, np.int32), np.zeros(shape, np.float32)
+    all_legs = np.zeros(len(quats), np.uint8)
+    ms = C.c_double(0)
+    check(load().lrm_footholds_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs),
+                                         _ptr(nom), _ptr(count), _ptr(best), _ptr(best_d2), _ptr(all_legs), C.addressof(ms)))
+    return count, best, best_d2, all_legs, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

@@ -19,6 +19,7 @@
 #include "lrm_compile.h"
 #include "lrm_compile_head.h"
 #include "lrm_footholds.h"
+#include "lrm_footholds_posed.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -1364,6 +1365,116 @@ int lrm_footholds_cpu(const float* bodies, size_t nb, const float* targets, size
                 best_d2_out[o] = count ? d2 : INFINITY;
             }
         }
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+// ---- foothold counts and choice per (pose, leg) (lrm_footholds_posed.hip) --------------------
+namespace {
+// the range checks of the posed foothold calls, before any early return
+int footholds_posed_args(size_t nt, size_t nposes, size_t nlegs) {
+    if (nt > (size_t)INT32_MAX) return fail(LRM_EINVAL, "nt must be at most INT32_MAX");
+    if (nlegs == 0 || nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "nlegs must be 1..LRM_MAX_LEGS");
+    if (nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "posed queries: nposes does not fit the int32 pose index");
+    if (nposes * nlegs > (size_t)UINT32_MAX) return fail(LRM_EINVAL, "posed queries: more than 2^32 - 1 (pose, leg) records");
+    return LRM_OK;
+}
+void host_pose_foothold_entries(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
+                                LrmPoseFootEntry* out) {
+    for (size_t p = 0; p < nposes; p++)
+        for (size_t l = 0; l < nlegs; l++) lrm_pose_foothold_entry(legs[l], quats + 4 * p, nominal ? nominal + 3 * l : nullptr, &out[p * nlegs + l]);
+}
+} // namespace
+
+size_t lrm_posed_footholds_workspace_bytes(size_t nposes, size_t nlegs) { return nposes * nlegs * sizeof(LrmPoseFootEntry); }
+
+int lrm_pose_footholds_compile_dev(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
+                                   void* fh_workspace, void* stream) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!quats || !fh_workspace) return fail(LRM_EINVAL, "null argument");
+    if ((uintptr_t)fh_workspace & 15) return fail(LRM_EINVAL, "posed footholds: the foothold workspace must be 16-byte aligned");
+    LrmFootNominal nom;
+    for (int l = 0; l < LRM_MAX_LEGS; l++)
+        for (int a = 0; a < 3; a++) nom.v[l][a] = (nominal && (size_t)l < nlegs) ? nominal[3 * l + a] : 0.f;
+    HIP_TRY(lrm_launch_pose_footholds_compile(quats, nposes, legs, nlegs, nom, fh_workspace, (hipStream_t)stream),
+            "pose footholds compile launch");
+    return LRM_OK;
+}
+
+int lrm_dbg_pose_footholds_compile_host(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                        const float* nominal, void* entries_out) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!quats || !entries_out) return fail(LRM_EINVAL, "null argument");
+    host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, (LrmPoseFootEntry*)entries_out);
+    return LRM_OK;
+}
+
+int lrm_footholds_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                            const void* fh_workspace, size_t nposes, size_t nlegs, int32_t* count_out, int32_t* best_out,
+                            float* best_d2_out, uint8_t* all_legs_out, void* stream) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!workspace || !fh_workspace || !count_out || !best_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
+        return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_footholds_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, count_out, best_out, best_d2_out,
+                                       all_legs_out, (hipStream_t)stream), "posed footholds launch");
+    return LRM_OK;
+}
+
+int lrm_footholds_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                            const LrmLegDimensions* legs, size_t nlegs, const float* nominal, int32_t* count_out, int32_t* best_out,
+                            float* best_d2_out, uint8_t* all_legs_out, double* ms) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (!legs) return fail(LRM_EINVAL, "null argument");
+    if (nposes == 0) return LRM_OK;
+    if (!quats || !count_out || !best_out || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
+    host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t p = 0; p < nposes; p++) {
+        bool all = true;
+        for (size_t l = 0; l < nlegs; l++) {
+            const LrmPoseRecord& R = recs[p * nlegs + l];
+            const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+            const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
+            int32_t count = 0;
+            uint64_t best = kLrmFootholdNone;
+            for (size_t t = 0; t < nt; t++) { // every target: the sphere of the entry is not consulted
+                const LrmVec3 tg{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
+                const LrmVec3 rel{tg.x - b.x, tg.y - b.y, tg.z - b.z};
+                if (!lrm_reach_global(L, &R.head.lists[0][0], rel)) continue;
+                count++;
+                const uint64_t key = lrm_foothold_key(lrm_foothold_d2(tg, b, ent[p * nlegs + l].nominal_w), (uint32_t)t);
+                if (key < best) best = key;
+            }
+            const size_t o = l * nposes + p;
+            count_out[o] = count;
+            best_out[o] = count ? (int32_t)(uint32_t)best : -1;
+            if (best_d2_out) {
+                const uint32_t hi = (uint32_t)(best >> 32);
+                float d2;
+                std::memcpy(&d2, &hi, sizeof d2);
+                best_d2_out[o] = count ? d2 : INFINITY;
+            }
+            all = all && count > 0;
+        }
+        if (all_legs_out) all_legs_out[p] = all;
     }
     const auto t1 = std::chrono::high_resolution_clock::now();
     if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;

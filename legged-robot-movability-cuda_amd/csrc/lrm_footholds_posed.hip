@@ -1,0 +1,286 @@
+// lrm_footholds_posed.hip -- gfx950 kernels of lrm_pose_footholds_compile_dev and lrm_footholds_posed_dev: per
+// (pose, leg) of a pose table, how many targets the leg can reach under that pose and which reachable target lies
+// nearest the leg's nominal point.
+//
+// A pair (pose p, leg l, target t) is reachable iff reachability_global(t - body[p], legs[l], quats[p]): the strict
+// evaluation of lrm_point.h on the pose record (LrmPoseRecord, lrm_compile_head.h) that the posed queries read.
+//
+//  * pose_footholds_compile_kernel: one thread per (pose, leg) writes the 32-byte entry of lrm_footholds_posed.h
+//    (bounding sphere and nominal point in the caller's frame), the host's own arithmetic.
+//  * footholds_posed_kernel is footholds_wave_kernel (lrm_footholds.hip) with the leg constants per pose.  A wave owns
+//    one pose, walks the tile boxes (lane = tile) and, inside a near tile, the chunk boxes (lane = chunk), reads only
+//    the 64-target chunks whose box touches some leg's sphere, with the next chunk's loads in flight while the current
+//    one is tested, and queues the targets inside the pose's reach sphere in LDS with their index.  A full batch of 64
+//    is tested against every leg whose own sphere it touches; popcount(__ballot(hit)) adds to lane l's count, every
+//    hit lane folds the key (d2 bits << 32 | index, lrm_footholds.h) into its own per-leg minimum, and six __shfl_xor
+//    steps per leg reduce the keys at the end.  No atomics, no __syncthreads: every wave stages its own tables.
+//    What differs from footholds_wave_kernel:
+//      - the nlegs records and entries of the wave's pose sit at wave-uniform addresses (readfirstlane): their
+//        scalars come through s_load at the point of use (lrm_fresh), as in posed_kernel's uniform path;
+//      - the 4 x 4 circle tables, per-lane indexed by the region, are copied to the wave's LDS slot when the wave's
+//        pose changes -- all nlegs of them at once (8 x 256 B per wave), one float per lane and leg, between two
+//        wave fences -- and so are the nlegs spheres the chunk cull indexes per lane;
+//      - the tile cull and the queue use the largest reach_r2_max of the pose's records about the body position, or
+//        +inf when some leg's sphere is the one that excludes nothing (non-unit quaternion);
+//      - the point test is lrm_reach_global on t - body: strict, whatever lrm_set_mode says.
+//
+// boxes == null (clouds below the 4096-target threshold of the C ABI): every tile and every chunk counts as near.
+//
+// Compiled with -ffp-contract=off (see lrm_point.h and lrm_footholds.h).
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include "lrm_launch.h"
+#include "lrm_types.h"
+#include "lrm_compile_head.h"
+#include "lrm_point.h"
+#include "lrm_footholds.h"
+#include "lrm_footholds_posed.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kTargetTile = 1024; // the tiles of tile_aabb_kernel (lrm_kernels.hip)
+constexpr int kQueue = 128;
+constexpr unsigned kMaxGrid = 16384; // 65 536 poses in flight; a wave strides over the rest
+
+struct PosedLegs { // the legs of a compile, by value in the kernarg segment (8 x 56 B)
+    LrmLegDimensions l[LRM_MAX_LEGS];
+};
+
+__global__ __launch_bounds__(kBlock) void pose_footholds_compile_kernel(const float* __restrict__ quats, uint32_t nposes, uint32_t nlegs,
+                                                                        const PosedLegs legs, const LrmFootNominal nominal,
+                                                                        LrmPoseFootEntry* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= (size_t)nposes * nlegs) return;
+    const uint32_t pose = (uint32_t)(t / nlegs), leg = (uint32_t)(t % nlegs);
+    const float q[4] = {quats[4 * (size_t)pose], quats[4 * (size_t)pose + 1], quats[4 * (size_t)pose + 2], quats[4 * (size_t)pose + 3]};
+    const float nom[3] = {nominal.v[leg][0], nominal.v[leg][1], nominal.v[leg][2]};
+    LrmPoseFootEntry E;
+    lrm_pose_foothold_entry(legs.l[leg], q, nom, &E);
+    out[t] = E;
+}
+
+// the same helpers as lrm_footholds.hip's
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ float box_dist2(const float* bb, float x, float y, float z) {
+    const float ex = fmaxf(fmaxf(bb[0] - x, x - bb[3]), 0.f);
+    const float ey = fmaxf(fmaxf(bb[1] - y, y - bb[4]), 0.f);
+    const float ez = fmaxf(fmaxf(bb[2] - z, z - bb[5]), 0.f);
+    return ex * ex + ey * ey + ez * ez;
+}
+__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
+
+#ifndef LRM_FOOTHOLDS_POSED_MIN_WAVES
+#define LRM_FOOTHOLDS_POSED_MIN_WAVES 8 // footholds_wave_kernel's setting
+#endif
+__global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void footholds_posed_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, size_t nt,
+    const LrmPoseRecord* __restrict__ recs, const LrmPoseFootEntry* __restrict__ fh, uint32_t nposes, uint32_t nlegs,
+    const float* __restrict__ boxes /* null = every tile near */, int32_t* __restrict__ count_out, int32_t* __restrict__ best_out,
+    float* __restrict__ best_d2_out, uint8_t* __restrict__ all_legs_out) {
+    __shared__ float s_qx[kWaves][kQueue], s_qy[kWaves][kQueue], s_qz[kWaves][kQueue];
+    __shared__ uint32_t s_qi[kWaves][kQueue];
+    __shared__ LrmCircle s_lists[kWaves][LRM_MAX_LEGS][4 * LRM_N_CIRCLES]; // the circle tables of the wave's pose
+    __shared__ float s_sphere[kWaves][LRM_MAX_LEGS][4];                    // its legs' spheres: centre (relative to the body), r^2
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    float* qx = s_qx[wave];
+    float* qy = s_qy[wave];
+    float* qz = s_qz[wave];
+    uint32_t* qi = s_qi[wave];
+    LrmCircle(*my_lists)[4 * LRM_N_CIRCLES] = s_lists[wave];
+    float(*my_sphere)[4] = s_sphere[wave];
+    const size_t ntiles = (nt + kTargetTile - 1) / kTargetTile;
+
+    for (uint32_t p = blockIdx.x * kWaves + wave; p < nposes; p += gridDim.x * kWaves) { // wave-uniform
+        const uint32_t r0 = p * nlegs; // nposes * nlegs < 2^32 (checked by the C ABI)
+        // stage the pose's tables: every lane is done with the previous pose's
+        wave_lds_fence();
+        for (uint32_t l = 0; l < nlegs; l++)
+            reinterpret_cast<float*>(my_lists[l])[lane] = reinterpret_cast<const float*>(&recs[r0 + l].head.lists[0][0])[lane];
+        if ((uint32_t)lane < nlegs * 4) my_sphere[lane >> 2][lane & 3] = reinterpret_cast<const float*>(&fh[r0 + (lane >> 2)])[lane & 3];
+        wave_lds_fence();
+        const LrmPoseRecord& R0 = lrm_fresh(recs[r0]);
+        const LrmVec3 body{R0.body_pos[0], R0.body_pos[1], R0.body_pos[2]}; // the same in every record of the pose
+        float r2max = 0.f;
+        for (uint32_t l = 0; l < nlegs; l++)
+            r2max = fmaxf(r2max, lrm_fresh(fh[r0 + l]).cull_r2 < __builtin_inff() ? lrm_fresh(recs[r0 + l]).head.reach_r2_max : __builtin_inff());
+
+        int count = 0;        // survivors waiting in this wave's queue
+        uint32_t legs_n = 0;  // lane l: leg l's reachable targets
+        uint64_t key[LRM_MAX_LEGS]; // this lane's best candidate per leg (constant indices only: registers)
+#pragma unroll
+        for (int k = 0; k < LRM_MAX_LEGS; k++) key[k] = kLrmFootholdNone;
+
+        auto process = [&](int m) {
+            LrmVec3 t{0.f, 0.f, 0.f};
+            uint32_t ti = 0u;
+            if (lane < m) {
+                t = LrmVec3{qx[lane], qy[lane], qz[lane]};
+                ti = qi[lane];
+            }
+            const LrmVec3 rel{t.x - body.x, t.y - body.y, t.z - body.z};
+            for (uint32_t l = 0; l < nlegs; l++) {
+                const LrmPoseFootEntry& E = lrm_fresh(fh[r0 + l]);
+                const float ex = rel.x - E.cull_center[0], ey = rel.y - E.cull_center[1], ez = rel.z - E.cull_center[2];
+                const bool inside = (lane < m) && __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)) <= E.cull_r2;
+                if (__ballot(inside) == 0ull) continue;
+                bool hit = false;
+                if (inside) {
+                    const LrmPoseRecord& R = lrm_fresh(recs[r0 + l]);
+                    hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists[l], rel);
+                }
+                const unsigned long long hm = __ballot(hit);
+                if (hm == 0ull) continue; // wave-uniform
+                if ((uint32_t)lane == l) legs_n += (uint32_t)__builtin_popcountll(hm);
+                const uint64_t kk = hit ? lrm_foothold_key(lrm_foothold_d2(t, body, E.nominal_w), ti) : kLrmFootholdNone;
+#pragma unroll
+                for (int k = 0; k < LRM_MAX_LEGS; k++)
+                    if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+            }
+        };
+
+        for (size_t tw0 = 0; tw0 < ntiles; tw0 += 64) {
+            // lane = tile: box distance is a lower bound of every member's distance; 1e-3 relative slack for the
+            // rounding of the bound itself
+            const size_t tl = tw0 + lane;
+            unsigned long long near =
+                __ballot(tl < ntiles && (!boxes || box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f <= r2max));
+            while (near != 0ull) {
+                const int tb = __builtin_ctzll(near);
+                near &= near - 1ull;
+                const size_t tile = tw0 + tb;
+                const size_t t0 = tile * kTargetTile;
+                // lane = (chunk of this tile, one of four legs): a chunk is read when its box touches the bounding
+                // sphere of some leg (empty chunks carry an inverted box)
+                uint32_t cnear = 0u;
+                if (boxes) {
+                    const float* cb = boxes + (ntiles + tile * 16 + (lane & 15)) * 6;
+                    for (uint32_t l0 = 0; l0 < nlegs; l0 += 4) { // wave-uniform
+                        const uint32_t l = l0 + (lane >> 4);
+                        bool touch = false;
+                        if (l < nlegs)
+                            touch = box_dist2(cb, body.x + my_sphere[l][0], body.y + my_sphere[l][1], body.z + my_sphere[l][2]) * 0.999f <=
+                                    my_sphere[l][3];
+                        const unsigned long long mm = __ballot(touch);
+                        cnear |= (uint32_t)((mm | (mm >> 16) | (mm >> 32) | (mm >> 48)) & 0xffffull);
+                    }
+                } else {
+                    const size_t left = nt - t0; // > 0: tile < ntiles
+                    const int chunks = left >= (size_t)kTargetTile ? 16 : (int)((left + 63) / 64);
+                    cnear = chunks == 16 ? 0xffffu : (1u << chunks) - 1u;
+                }
+                // software pipeline: the next near chunk's loads are issued before this one is tested
+                LrmVec3 nxt{0.f, 0.f, 0.f};
+                uint32_t nxt_i = 0u;
+                bool nxt_ok = false;
+                auto fetch = [&](int chunk) {
+                    const size_t i = t0 + (size_t)chunk * 64 + lane;
+                    nxt_ok = i < nt;
+                    nxt_i = (uint32_t)i; // nt <= INT32_MAX (checked by the C ABI)
+                    if (nxt_ok) nxt = LrmVec3{tx[i], ty[i], tz[i]};
+                };
+                if (cnear) {
+                    fetch(__builtin_ctz(cnear));
+                    cnear &= cnear - 1u;
+                }
+                bool more = true;
+                while (more) {
+                    const LrmVec3 t = nxt;
+                    const uint32_t ti = nxt_i;
+                    const bool ok = nxt_ok;
+                    more = cnear != 0u;
+                    if (more) {
+                        fetch(__builtin_ctz(cnear));
+                        cnear &= cnear - 1u;
+                    }
+                    const float ddx = t.x - body.x, ddy = t.y - body.y, ddz = t.z - body.z;
+                    const bool keep = ok && __builtin_fmaf(ddz, ddz, __builtin_fmaf(ddy, ddy, ddx * ddx)) <= r2max;
+                    const unsigned long long m = __ballot(keep);
+                    if (m == 0ull) continue;
+                    if (keep) {
+                        const int pos = count + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                        qx[pos] = t.x;
+                        qy[pos] = t.y;
+                        qz[pos] = t.z;
+                        qi[pos] = ti;
+                    }
+                    count += __builtin_popcountll(m);
+                    wave_lds_fence();
+                    if (count >= 64) {
+                        process(64);
+                        count -= 64;
+                        // the (< 64) entries behind the processed batch move to the front
+                        float mx = 0.f, my = 0.f, mz = 0.f;
+                        uint32_t mi = 0u;
+                        if (lane < count) { mx = qx[64 + lane]; my = qy[64 + lane]; mz = qz[64 + lane]; mi = qi[64 + lane]; }
+                        wave_lds_fence();
+                        if (lane < count) { qx[lane] = mx; qy[lane] = my; qz[lane] = mz; qi[lane] = mi; }
+                        wave_lds_fence();
+                    }
+                }
+            }
+        }
+        if (count > 0) process(count);
+
+        // per leg: the wave's smallest key; lane l keeps leg l's
+        uint64_t best = kLrmFootholdNone;
+#pragma unroll
+        for (int k = 0; k < LRM_MAX_LEGS; k++) {
+            if ((uint32_t)k >= nlegs) break; // wave-uniform
+            uint64_t v = key[k];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
+                v = min_u64(v, ((uint64_t)hi << 32) | lo);
+            }
+            if (lane == k) best = v;
+        }
+        const bool mine = (uint32_t)lane < nlegs;
+        if (mine) {
+            const size_t o = (size_t)lane * nposes + p;
+            count_out[o] = (int32_t)legs_n;
+            best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
+            if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+        }
+        if (all_legs_out) { // wave-uniform
+            const unsigned long long have = __ballot(mine && legs_n != 0u);
+            if (lane == 0) all_legs_out[p] = have == ((1ull << nlegs) - 1ull);
+        }
+    }
+}
+
+} // namespace
+
+hipError_t lrm_launch_pose_footholds_compile(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                             const LrmFootNominal& nominal, void* fh_records, hipStream_t st) {
+    PosedLegs L{};
+    for (size_t k = 0; k < nlegs; k++) L.l[k] = legs[k];
+    const size_t total = nposes * nlegs;
+    const int grid = (int)((total + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(pose_footholds_compile_kernel, dim3(grid), dim3(kBlock), 0, st, quats, (uint32_t)nposes, (uint32_t)nlegs, L,
+                       nominal, (LrmPoseFootEntry*)fh_records);
+    return hipGetLastError();
+}
+
+hipError_t lrm_launch_footholds_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                      const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, int32_t* count_out,
+                                      int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st) {
+    if (tile_boxes && nt) {
+        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
+        if (e != hipSuccess) return e;
+    }
+    size_t g = (nposes + kWaves - 1) / kWaves;
+    if (g > kMaxGrid) g = kMaxGrid;
+    const float* boxes = nt ? tile_boxes : nullptr;
+    hipLaunchKernelGGL(footholds_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, count_out, best_out, best_d2_out,
+                       all_legs_out);
+    return hipGetLastError();
+}

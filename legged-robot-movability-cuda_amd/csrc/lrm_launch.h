@@ -71,6 +71,14 @@ hipError_t lrm_launch_footholds(const float* bx, const float* by, const float* b
                                 const float* ty, const float* tz, size_t nt, const LrmCompiledLeg* legs_dev, int nlegs,
                                 float* tile_boxes, const LrmFootNominal& nominal, int32_t* count_out, int32_t* best_out,
                                 float* best_d2_out, bool fast, hipStream_t st);
+// lrm_pose_footholds_compile_dev / lrm_footholds_posed_dev (lrm_footholds_posed.hip).  fh_records: nposes x nlegs
+// LrmPoseFootEntry (lrm_footholds_posed.h) at pose * nlegs + leg, next to the pose records of lrm_posed.hip.  Outputs
+// [nlegs * nposes] at l * nposes + p and all_legs_out[nposes]; best_d2_out and all_legs_out may be null; tile_boxes as above.
+hipError_t lrm_launch_pose_footholds_compile(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                             const LrmFootNominal& nominal, void* fh_records, hipStream_t st);
+hipError_t lrm_launch_footholds_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                      const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, int32_t* count_out,
+                                      int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

@@ -210,10 +210,14 @@ def footholds(bx, by, bz, tx, ty, tz, legs, quat=None, nominal=None, count=None,
 
 
 def footholds_layout(nb, nlegs, device):
-    """(pose_idx int32, leg_idx uint8) of footholds()' [l*nb + b] order with one pose per body: entry l*nb + b is
-    (b, l), so that ps.ik(tx, ty, tz, *footholds_layout(nb, nlegs, dev), target_idx=best.view(-1)) solves every chosen
-    foothold in one launch.  footholds() uses its legs as given and measures in the clouds' frame: give the PoseSet
-    those same (already rotated) legs and, per body, the identity quaternion and the body position."""
+    """(pose_idx int32, leg_idx uint8) of the [l*nb + b] order of both foothold calls with one pose per body: entry
+    l*nb + b is (b, l), so that ps.ik(tx, ty, tz, *footholds_layout(nb, nlegs, dev), target_idx=best.view(-1)) solves
+    every chosen foothold in one launch.  Two routes lead there:
+      * PoseSet(legs, n, ik=True, footholds=True): ps.update(quats, body); ps.footholds(tx, ty, tz) -> best; ps.ik(...)
+        on the SAME set.  Every body has its own quaternion, the legs are given unrotated, nominal is in the body frame.
+      * footholds() (lrm_footholds_dev, reachable_rotate_leg's convention: one quaternion, legs used as given, measured
+        in the clouds' frame): give a second PoseSet those same (already rotated) legs and, per body, the identity
+        quaternion and the body position."""
     torch = _torch()
     pose = torch.arange(nb, dtype=torch.int32, device=device).repeat(nlegs)
     leg = torch.arange(nlegs, dtype=torch.uint8, device=device).repeat_interleave(nb)
@@ -297,9 +301,12 @@ class PoseSet:
     (target, pose, leg).  Both only launch: with check=False, reach_dist can be captured in a graph next to update()
     and replayed after new poses were copied into the captured quaternion tensor.  The arithmetic is LRM_MODE_STRICT's,
     whatever set_mode says.  ik=True: the set also owns the table of IK constants (128 bytes per (pose, leg)), update()
-    compiles it too on the same stream, and ik() / fk() answer joint-angle queries."""
+    compiles it too on the same stream, and ik() / fk() answer joint-angle queries.  footholds=True: the set owns the
+    foothold table as well (32 bytes per (pose, leg): bounding sphere and nominal point, nominal (nlegs, 3) on the host
+    in the BODY frame or None = zero), update() compiles it on the same stream, and footholds() counts and chooses the
+    reachable targets per (pose, leg)."""
 
-    def __init__(self, legs, nposes_max, device=None, ik=False):
+    def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
         self.legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
         if not 1 <= len(self.legs) <= 8:
@@ -314,6 +321,13 @@ class PoseSet:
         if ik:
             nbytes = _capi.load().lrm_posed_ik_workspace_bytes(self.nposes_max, len(self.legs))
             self.ik_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.fh_workspace = None
+        self.nominal = None if nominal is None else np.ascontiguousarray(nominal, dtype=np.float32).reshape(len(self.legs), 3)
+        if footholds:
+            nbytes = _capi.load().lrm_posed_footholds_workspace_bytes(self.nposes_max, len(self.legs))
+            self.fh_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        elif nominal is not None:
+            raise ValueError("PoseSet: nominal without footholds=True")
         self.nposes = 0
 
     @property
@@ -339,8 +353,45 @@ class PoseSet:
             if self.ik_workspace is not None:
                 _capi.check(_capi.load().lrm_pose_ik_compile_dev(_dp(quats), nposes, _capi._ptr(self.legs), self.nlegs,
                                                                  _dp(self.ik_workspace), _stream(self.workspace)))
+            if self.fh_workspace is not None:
+                _capi.check(_capi.load().lrm_pose_footholds_compile_dev(_dp(quats), nposes, _capi._ptr(self.legs), self.nlegs,
+                                                                        _capi._ptr(self.nominal), _dp(self.fh_workspace),
+                                                                        _stream(self.workspace)))
         self.nposes = nposes
         return self
+
+    def footholds(self, tx, ty, tz, count=None, best=None, best_d2=None, all_legs=None):
+        """lrm_footholds_posed_dev: count[l, p] = targets leg l reaches under pose p (reachability_global on
+        target - body[p]), best[l, p] = the reachable target nearest body[p] + the leg's nominal point rotated by the
+        pose (-1 if none), best_d2[l, p] = its squared distance (+inf if none), all_legs[p] = 1 iff every leg has one.
+        -> (count int32, best int32, best_d2 float32, each [nlegs, nposes]; all_legs uint8[nposes]).  One launch behind
+        the cloud's bounding boxes; best.view(-1) is ik()'s target_idx with footholds_layout(nposes, nlegs, device)."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        if self.fh_workspace is None:
+            raise ValueError("PoseSet: built without footholds=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        shape, n = (self.nlegs, self.nposes), self.nlegs * self.nposes
+        if count is None:
+            count = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if best is None:
+            best = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if best_d2 is None:
+            best_d2 = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if all_legs is None:
+            all_legs = torch.empty(self.nposes, dtype=torch.uint8, device=self.device)
+        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
+        _check_out(best, self.workspace, torch.int32, n, "per-leg choices")
+        _check_out(best_d2, self.workspace, torch.float32, n, "per-leg squared distances")
+        _check_out(all_legs, self.workspace, torch.uint8, self.nposes, "per-pose bytes")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_footholds_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace), _dp(self.fh_workspace),
+                                                             self.nposes, self.nlegs, _dp(count), _dp(best), _dp(best_d2),
+                                                             _dp(all_legs), _stream(self.workspace)))
+        return count, best, best_d2, all_legs
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
