@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -423,6 +423,45 @@ int lrm_footholds_posed_dev(const float* tx, const float* ty, const float* tz, s
 int lrm_footholds_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
                             const LrmLegDimensions* legs, size_t nlegs, const float* nominal, int32_t* count_out,
                             int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, double* ms);
+/* Reachable-foothold LISTS per (pose, leg) in CSR form: the set lrm_footholds_posed_dev counts, written out.  Pose
+ * table, leg table, `workspace` and `fh_workspace` are those of lrm_footholds_posed_dev, and a pair (p, l, t) is
+ * reachable under the same rule (strict reachability_global(t - body[p], legs[l], quats[p]), whatever lrm_set_mode
+ * says).  The two-step CSR: count_out of lrm_footholds_posed_dev -> lrm_foothold_offsets_dev -> this call.
+ * lrm_foothold_offsets_dev: offsets_out[0] = 0, offsets_out[k+1] = offsets_out[k] + max(count[k], 0), n + 1 entries,
+ * all on the device.  One launch of one workgroup; it never allocates and never synchronises with the host; n up to
+ * 2^32 - 1 (more: LRM_EINVAL); n == 0 writes offsets_out[0] = 0 only; NULL pointers give LRM_EINVAL.
+ * lrm_foothold_lists_posed_dev / _cpu, with o = l*nposes + p:
+ *   segment      base = offsets[o]; room = min(offsets[o+1], (int64)capacity) - base, and 0 if that is negative or base < 0;
+ *   idx_out      the reachable targets of (p, l) in ASCENDING index; the first min(count, room) of them at idx_out[base + k];
+ *   d2_out       (may be NULL, capacity) at the same positions the d2 of lrm_footholds_posed_dev:
+ *                lrm_foothold_d2(t, body[p], nominal_w), float32, no contraction;
+ *   written_out  (may be NULL, nlegs*nposes) written_out[o] = min(count, room).
+ * No element outside [base, base + room) is ever written, and every other element of idx_out / d2_out keeps its value.
+ * ANY offsets array is memory-safe: decreasing, negative and overlapping offsets never cause a write outside the
+ * buffers, only a shorter list (overlapping segments hold one of the lists that claim them).  Offsets made by
+ * lrm_foothold_offsets_dev from count_out with capacity >= offsets[last] give every list whole; offsets[o] = o*K gives
+ * the first K by index of every list.
+ * Checked first, as in lrm_footholds_posed_dev: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX or more
+ * than 2^32 - 1 records give LRM_EINVAL; NULL offsets or NULL idx_out give LRM_EINVAL.  Then nposes == 0 is a no-op;
+ * nt == 0 or capacity == 0 writes written_out = 0 everywhere and nothing else.
+ * Threading and streams: lrm_foothold_lists_posed_dev is one of the pair kernels, with lrm_footholds_posed_dev's rules:
+ * it uses the per-device tile-box buffer from 4096 targets on, one host thread at a time, no two pair launches on
+ * different clouds concurrently on one device; the first call for a larger cloud than the buffer holds allocates, every
+ * later call (and every call below 4096 targets) only launches, so compile -> footholds -> offsets -> lists with a
+ * fixed capacity can be captured in a graph after one call on a cloud of the largest size.
+ * lrm_foothold_lists_posed_cpu: AoS float3 targets, host tables and host offsets, a serial loop over every (pose, leg,
+ * target) with the strict test and no culling, like lrm_footholds_posed_cpu: the reference the GPU tests compare with
+ * bit for bit; *ms = the loop's time. */
+int lrm_foothold_offsets_dev(const int32_t* count, size_t n, int64_t* offsets_out, void* stream);
+int lrm_foothold_lists_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                                 const void* workspace, const void* fh_workspace, size_t nposes, size_t nlegs,
+                                 const int64_t* offsets /* device, nlegs*nposes + 1 */, size_t capacity,
+                                 int32_t* idx_out /* device, capacity */, float* d2_out /* may be NULL, capacity */,
+                                 int32_t* written_out /* may be NULL, nlegs*nposes */, void* stream);
+int lrm_foothold_lists_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                                 const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
+                                 const int64_t* offsets /* host */, size_t capacity, int32_t* idx_out, float* d2_out,
+                                 int32_t* written_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

@@ -123,13 +123,16 @@ def load():
         "lrm_dbg_pose_footholds_compile_host": [vp, sz, vp, sz, vp, vp],
         "lrm_footholds_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp],
         "lrm_footholds_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
+        "lrm_foothold_offsets_dev": [vp, sz, vp, vp],
+        "lrm_foothold_lists_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp],
+        "lrm_foothold_lists_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_"):  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics may be missing
-                continue
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith("lrm_foothold_")):
+                continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
         fn.restype = C.c_int
@@ -469,6 +472,39 @@ def footholds_posed_cpu(targets, quats, body, legs, nominal=None):
     check(load().lrm_footholds_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs),
                                          _ptr(nom), _ptr(count), _ptr(best), _ptr(best_d2), _ptr(all_legs), C.addressof(ms)))
     return count, best, best_d2, all_legs, ms.value
+
+
+def foothold_lists_posed_cpu(targets, quats, body, legs, offsets, capacity=None, nominal=None, idx=None, d2=None, written=None,
+                             want_d2=True, want_written=True):
+    """lrm_foothold_lists_posed_cpu: per (leg, pose) segment o = l*nposes + p of offsets (int64[nlegs*nposes + 1], any
+    values) the reachable targets in ascending index, as far as the segment has room (include/lrm.h); serial host loop,
+    no culling.  capacity None = len(idx), or offsets[-1] without idx.  idx / d2 / written given are written in place
+    (whatever else they hold survives); want_d2 / want_written False pass NULL.
+    -> (idx int32[capacity], d2 float32[capacity] or None, written int32[nlegs, nposes] or None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    if len(offsets) != len(legs) * len(quats) + 1:
+        raise ValueError("offsets: nlegs * nposes + 1 entries")
+    if capacity is None:
+        capacity = len(idx) if idx is not None else max(int(offsets[-1]), 0)
+    if idx is None:
+        idx = np.zeros(capacity, np.int32)
+    if d2 is None and want_d2:
+        d2 = np.zeros(capacity, np.float32)
+    if written is None and want_written:
+        written = np.zeros((len(legs), len(quats)), np.int32)
+    for a, dt, n, what in ((idx, np.int32, capacity, "idx"), (d2, np.float32, capacity, "d2"),
+                           (written, np.int32, len(legs) * len(quats), "written")):
+        if a is not None and not (a.dtype == dt and a.flags.c_contiguous and a.size >= n):
+            raise ValueError(f"{what}: expected a contiguous {np.dtype(dt)} array of >= {n} elements")
+    ms = C.c_double(0)
+    check(load().lrm_foothold_lists_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs),
+                                              len(legs), _ptr(nom), _ptr(offsets), capacity, _ptr(idx),
+                                              _ptr(d2) if want_d2 else None, _ptr(written) if want_written else None,
+                                              C.addressof(ms)))
+    return idx, d2 if want_d2 else None, written if want_written else None, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

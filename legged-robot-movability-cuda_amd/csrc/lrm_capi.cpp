@@ -1481,6 +1481,85 @@ int lrm_footholds_posed_cpu(const float* targets, size_t nt, const float* quats,
     return LRM_OK;
 }
 
+// ---- reachable-foothold lists per (pose, leg) in CSR form (lrm_footholds_posed.hip) -----------
+int lrm_foothold_offsets_dev(const int32_t* count, size_t n, int64_t* offsets_out, void* stream) {
+    if (n > (size_t)UINT32_MAX) return fail(LRM_EINVAL, "foothold offsets: more than 2^32 - 1 counts");
+    if (!offsets_out || (n && !count)) return fail(LRM_EINVAL, "null argument");
+    HIP_TRY(lrm_launch_foothold_offsets(count, n, offsets_out, (hipStream_t)stream), "foothold offsets launch");
+    return LRM_OK;
+}
+
+int lrm_foothold_lists_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                                 const void* fh_workspace, size_t nposes, size_t nlegs, const int64_t* offsets, size_t capacity,
+                                 int32_t* idx_out, float* d2_out, int32_t* written_out, void* stream) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (!offsets || !idx_out) return fail(LRM_EINVAL, "null argument");
+    if (nposes == 0) return LRM_OK;
+    if (!workspace || !fh_workspace || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
+        return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
+    if (nt == 0 || capacity == 0) { // every list is empty or has no room: nothing but written_out
+        if (written_out)
+            HIP_TRY(hipMemsetAsync(written_out, 0, nposes * nlegs * sizeof(int32_t), (hipStream_t)stream), "hipMemsetAsync written_out");
+        return LRM_OK;
+    }
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_foothold_lists_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, offsets, capacity, idx_out,
+                                            d2_out, written_out, (hipStream_t)stream), "posed foothold lists launch");
+    return LRM_OK;
+}
+
+int lrm_foothold_lists_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                 const LrmLegDimensions* legs, size_t nlegs, const float* nominal, const int64_t* offsets,
+                                 size_t capacity, int32_t* idx_out, float* d2_out, int32_t* written_out, double* ms) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (!offsets || !idx_out || !legs) return fail(LRM_EINVAL, "null argument");
+    if (nposes == 0) return LRM_OK;
+    if (!quats || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    if (nt == 0 || capacity == 0) {
+        if (written_out) std::memset(written_out, 0, nposes * nlegs * sizeof(int32_t));
+        if (ms) *ms = 0.0;
+        return LRM_OK;
+    }
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
+    host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
+    const int64_t cap = capacity > (size_t)INT64_MAX ? INT64_MAX : (int64_t)capacity;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t p = 0; p < nposes; p++) {
+        for (size_t l = 0; l < nlegs; l++) {
+            const LrmPoseRecord& R = recs[p * nlegs + l];
+            const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+            const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
+            const size_t o = l * nposes + p;
+            const int64_t base = offsets[o], end = offsets[o + 1] < cap ? offsets[o + 1] : cap;
+            const int64_t room = (base >= 0 && end > base) ? end - base : 0;
+            int64_t n = 0; // reachable so far
+            for (size_t t = 0; t < nt; t++) { // every target: the sphere of the entry is not consulted
+                const LrmVec3 tg{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
+                const LrmVec3 rel{tg.x - b.x, tg.y - b.y, tg.z - b.z};
+                if (!lrm_reach_global(L, &R.head.lists[0][0], rel)) continue;
+                if (n < room) {
+                    idx_out[base + n] = (int32_t)t;
+                    if (d2_out) d2_out[base + n] = lrm_foothold_d2(tg, b, ent[p * nlegs + l].nominal_w);
+                }
+                n++;
+            }
+            if (written_out) written_out[o] = (int32_t)(n < room ? n : room);
+        }
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
 namespace {
 int any_in_shape_impl(int shape, const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,
                       const float* ty, const float* tz, size_t nt, float radius, float plus_z, float minus_z,

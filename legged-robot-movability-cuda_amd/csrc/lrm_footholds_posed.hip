@@ -24,6 +24,11 @@
 //        +inf when some leg's sphere is the one that excludes nothing (non-unit quaternion);
 //      - the point test is lrm_reach_global on t - body: strict, whatever lrm_set_mode says.
 //
+//  * foothold_lists_posed_kernel (lrm_foothold_lists_posed_dev) is the same traversal (footholds_posed_traverse<true>)
+//    without the keys: survivors reach process() in ascending target index, so a hit's rank in the list of (pose, leg)
+//    is the leg's running count plus the hits in lower lanes, and it is stored at that rank in the caller's segment.
+//  * foothold_offsets_kernel (lrm_foothold_offsets_dev): the exclusive scan between the two, one workgroup with a carry.
+//
 // boxes == null (clouds below the 4096-target threshold of the C ABI): every tile and every chunk counts as near.
 //
 // Compiled with -ffp-contract=off (see lrm_point.h and lrm_footholds.h).
@@ -79,11 +84,15 @@ __device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b <
 #ifndef LRM_FOOTHOLDS_POSED_MIN_WAVES
 #define LRM_FOOTHOLDS_POSED_MIN_WAVES 8 // footholds_wave_kernel's setting
 #endif
-__global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void footholds_posed_kernel(
+// The traversal of both kernels.  kLists = false: footholds_posed_kernel (counts and choice).  kLists = true:
+// foothold_lists_posed_kernel -- no keys; every hit is stored at its rank in the (pose, leg) segment instead.
+template <bool kLists>
+__device__ __forceinline__ void footholds_posed_traverse(
     const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, size_t nt,
     const LrmPoseRecord* __restrict__ recs, const LrmPoseFootEntry* __restrict__ fh, uint32_t nposes, uint32_t nlegs,
     const float* __restrict__ boxes /* null = every tile near */, int32_t* __restrict__ count_out, int32_t* __restrict__ best_out,
-    float* __restrict__ best_d2_out, uint8_t* __restrict__ all_legs_out) {
+    float* __restrict__ best_d2_out, uint8_t* __restrict__ all_legs_out, const int64_t* __restrict__ offsets, int64_t capacity,
+    int32_t* __restrict__ idx_out, float* __restrict__ d2_out, int32_t* __restrict__ written_out) {
     __shared__ float s_qx[kWaves][kQueue], s_qy[kWaves][kQueue], s_qz[kWaves][kQueue];
     __shared__ uint32_t s_qi[kWaves][kQueue];
     __shared__ LrmCircle s_lists[kWaves][LRM_MAX_LEGS][4 * LRM_N_CIRCLES]; // the circle tables of the wave's pose
@@ -114,9 +123,25 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void foothol
 
         int count = 0;        // survivors waiting in this wave's queue
         uint32_t legs_n = 0;  // lane l: leg l's reachable targets
-        uint64_t key[LRM_MAX_LEGS]; // this lane's best candidate per leg (constant indices only: registers)
+        [[maybe_unused]] uint64_t key[LRM_MAX_LEGS]; // kLists = false: this lane's best candidate per leg (constant indices only: registers)
+        if constexpr (!kLists) {
 #pragma unroll
-        for (int k = 0; k < LRM_MAX_LEGS; k++) key[k] = kLrmFootholdNone;
+            for (int k = 0; k < LRM_MAX_LEGS; k++) key[k] = kLrmFootholdNone;
+        }
+        // kLists, lane l: leg l's segment [seg_base, seg_base + seg_room) of idx_out, clamped here, before any store:
+        // 0 <= seg_base and seg_base + seg_room <= capacity, or seg_room == 0
+        int64_t seg_base = 0;
+        uint32_t seg_room = 0u;
+        if constexpr (kLists) {
+            if ((uint32_t)lane < nlegs) {
+                const size_t o = (size_t)lane * nposes + p;
+                const int64_t b = offsets[o], e = offsets[o + 1] < capacity ? offsets[o + 1] : capacity; // e <= capacity
+                if (b >= 0 && e > b) { // both non-negative: e - b does not overflow
+                    seg_base = b;
+                    seg_room = e - b > (int64_t)INT32_MAX ? (uint32_t)INT32_MAX : (uint32_t)(e - b); // a list has at most nt <= INT32_MAX entries
+                }
+            }
+        }
 
         auto process = [&](int m) {
             LrmVec3 t{0.f, 0.f, 0.f};
@@ -138,11 +163,26 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void foothol
                 }
                 const unsigned long long hm = __ballot(hit);
                 if (hm == 0ull) continue; // wave-uniform
-                if ((uint32_t)lane == l) legs_n += (uint32_t)__builtin_popcountll(hm);
-                const uint64_t kk = hit ? lrm_foothold_key(lrm_foothold_d2(t, body, E.nominal_w), ti) : kLrmFootholdNone;
+                if constexpr (kLists) {
+                    // the queue is first-in first-out over ascending targets: a hit's rank in the list is the leg's
+                    // running count plus the hits in lower lanes; one ballot's stores are consecutive addresses
+                    const uint32_t rank = __builtin_amdgcn_readlane(legs_n, l) +
+                                          __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+                    const uint32_t room = __builtin_amdgcn_readlane(seg_room, l);
+                    const int64_t base = (int64_t)(((uint64_t)__builtin_amdgcn_readlane((uint32_t)((uint64_t)seg_base >> 32), l) << 32) |
+                                                   __builtin_amdgcn_readlane((uint32_t)seg_base, l));
+                    if (hit && rank < room) {
+                        idx_out[base + rank] = (int32_t)ti;
+                        if (d2_out) d2_out[base + rank] = lrm_foothold_d2(t, body, E.nominal_w);
+                    }
+                    if ((uint32_t)lane == l) legs_n += (uint32_t)__builtin_popcountll(hm);
+                } else {
+                    if ((uint32_t)lane == l) legs_n += (uint32_t)__builtin_popcountll(hm);
+                    const uint64_t kk = hit ? lrm_foothold_key(lrm_foothold_d2(t, body, E.nominal_w), ti) : kLrmFootholdNone;
 #pragma unroll
-                for (int k = 0; k < LRM_MAX_LEGS; k++)
-                    if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+                    for (int k = 0; k < LRM_MAX_LEGS; k++)
+                        if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+                }
             }
         };
 
@@ -229,30 +269,112 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void foothol
         }
         if (count > 0) process(count);
 
-        // per leg: the wave's smallest key; lane l keeps leg l's
-        uint64_t best = kLrmFootholdNone;
+        if constexpr (kLists) {
+            if (written_out && (uint32_t)lane < nlegs) written_out[(size_t)lane * nposes + p] = (int32_t)(legs_n < seg_room ? legs_n : seg_room);
+        } else {
+            // per leg: the wave's smallest key; lane l keeps leg l's
+            uint64_t best = kLrmFootholdNone;
 #pragma unroll
-        for (int k = 0; k < LRM_MAX_LEGS; k++) {
-            if ((uint32_t)k >= nlegs) break; // wave-uniform
-            uint64_t v = key[k];
+            for (int k = 0; k < LRM_MAX_LEGS; k++) {
+                if ((uint32_t)k >= nlegs) break; // wave-uniform
+                uint64_t v = key[k];
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
-                v = min_u64(v, ((uint64_t)hi << 32) | lo);
+                for (int off = 32; off > 0; off >>= 1) {
+                    const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
+                    v = min_u64(v, ((uint64_t)hi << 32) | lo);
+                }
+                if (lane == k) best = v;
             }
-            if (lane == k) best = v;
+            const bool mine = (uint32_t)lane < nlegs;
+            if (mine) {
+                const size_t o = (size_t)lane * nposes + p;
+                count_out[o] = (int32_t)legs_n;
+                best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
+                if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+            }
+            if (all_legs_out) { // wave-uniform
+                const unsigned long long have = __ballot(mine && legs_n != 0u);
+                if (lane == 0) all_legs_out[p] = have == ((1ull << nlegs) - 1ull);
+            }
         }
-        const bool mine = (uint32_t)lane < nlegs;
-        if (mine) {
-            const size_t o = (size_t)lane * nposes + p;
-            count_out[o] = (int32_t)legs_n;
-            best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
-            if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+    }
+}
+
+__global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void footholds_posed_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, size_t nt,
+    const LrmPoseRecord* __restrict__ recs, const LrmPoseFootEntry* __restrict__ fh, uint32_t nposes, uint32_t nlegs,
+    const float* __restrict__ boxes /* null = every tile near */, int32_t* __restrict__ count_out, int32_t* __restrict__ best_out,
+    float* __restrict__ best_d2_out, uint8_t* __restrict__ all_legs_out) {
+    footholds_posed_traverse<false>(tx, ty, tz, nt, recs, fh, nposes, nlegs, boxes, count_out, best_out, best_d2_out, all_legs_out,
+                                    nullptr, 0, nullptr, nullptr, nullptr);
+}
+
+// lrm_foothold_lists_posed_dev: the same traversal; the reachable targets of (pose p, leg l) in ascending index go to
+// idx_out[base + k] (their d2 to d2_out), base = offsets[l*nposes + p], as far as the segment has room (include/lrm.h).
+// The launch bound is footholds_posed_kernel's, carried over, not compared.
+__global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_POSED_MIN_WAVES) void foothold_lists_posed_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, size_t nt,
+    const LrmPoseRecord* __restrict__ recs, const LrmPoseFootEntry* __restrict__ fh, uint32_t nposes, uint32_t nlegs,
+    const float* __restrict__ boxes /* null = every tile near */, const int64_t* __restrict__ offsets, int64_t capacity,
+    int32_t* __restrict__ idx_out, float* __restrict__ d2_out /* may be null */, int32_t* __restrict__ written_out /* may be null */) {
+    footholds_posed_traverse<true>(tx, ty, tz, nt, recs, fh, nposes, nlegs, boxes, nullptr, nullptr, nullptr, nullptr, offsets,
+                                   capacity, idx_out, d2_out, written_out);
+}
+
+// lrm_foothold_offsets_dev: out[0] = 0, out[k + 1] = out[k] + max(count[k], 0).  ONE workgroup strides over n in slices
+// of kScanSlice with a running carry: no second workgroup to wait for, no scratch.  A thread sums kScanItems
+// consecutive counts, the waves scan those sums (__shfl_up, then the 16 wave totals through LDS), and the next slice's
+// counts are loaded before the current slice is scanned.
+constexpr int kScanBlock = 1024;
+constexpr int kScanItems = 8;
+constexpr int kScanSlice = kScanBlock * kScanItems;
+
+__global__ __launch_bounds__(kScanBlock) void foothold_offsets_kernel(const int32_t* __restrict__ count, size_t n, int64_t* __restrict__ out) {
+    __shared__ int64_t s_wave[kScanBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) out[0] = 0;
+    int64_t carry = 0; // the same in every thread
+    int32_t c[kScanItems], nx[kScanItems];
+    auto load = [&](size_t s0, int32_t* v) {
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) {
+            const size_t i = s0 + (size_t)tid * kScanItems + k;
+            const int32_t x = i < n ? count[i] : 0;
+            v[k] = x > 0 ? x : 0;
         }
-        if (all_legs_out) { // wave-uniform
-            const unsigned long long have = __ballot(mine && legs_n != 0u);
-            if (lane == 0) all_legs_out[p] = have == ((1ull << nlegs) - 1ull);
+    };
+    load(0, nx);
+    for (size_t s0 = 0; s0 < n; s0 += kScanSlice) {
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) c[k] = nx[k];
+        if (s0 + kScanSlice < n) load(s0 + kScanSlice, nx);
+        int64_t mine = 0;
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) mine += c[k];
+        int64_t incl = mine; // inclusive scan over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int64_t up = __shfl_up(incl, off);
+            if (lane >= off) incl += up;
         }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int64_t before = carry, total = 0;
+#pragma unroll
+        for (int w = 0; w < kScanBlock / 64; w++) {
+            const int64_t v = s_wave[w];
+            if (w < wave) before += v;
+            total += v;
+        }
+        __syncthreads(); // s_wave is rewritten in the next slice
+        int64_t run = before + incl - mine;
+#pragma unroll
+        for (int k = 0; k < kScanItems; k++) {
+            const size_t i = s0 + (size_t)tid * kScanItems + k;
+            run += c[k];
+            if (i < n) out[i + 1] = run;
+        }
+        carry += total;
     }
 }
 
@@ -282,5 +404,28 @@ hipError_t lrm_launch_footholds_posed(const float* tx, const float* ty, const fl
     hipLaunchKernelGGL(footholds_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
                        (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, count_out, best_out, best_d2_out,
                        all_legs_out);
+    return hipGetLastError();
+}
+
+hipError_t lrm_launch_foothold_lists_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                           const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
+                                           const int64_t* offsets, size_t capacity, int32_t* idx_out, float* d2_out,
+                                           int32_t* written_out, hipStream_t st) {
+    if (tile_boxes && nt) {
+        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
+        if (e != hipSuccess) return e;
+    }
+    size_t g = (nposes + kWaves - 1) / kWaves;
+    if (g > kMaxGrid) g = kMaxGrid;
+    const float* boxes = nt ? tile_boxes : nullptr;
+    const int64_t cap = capacity > (size_t)INT64_MAX ? INT64_MAX : (int64_t)capacity;
+    hipLaunchKernelGGL(foothold_lists_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, offsets, cap, idx_out, d2_out,
+                       written_out);
+    return hipGetLastError();
+}
+
+hipError_t lrm_launch_foothold_offsets(const int32_t* count, size_t n, int64_t* offsets_out, hipStream_t st) {
+    hipLaunchKernelGGL(foothold_offsets_kernel, dim3(1), dim3(kScanBlock), 0, st, count, n, offsets_out);
     return hipGetLastError();
 }

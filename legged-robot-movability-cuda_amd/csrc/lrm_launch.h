@@ -79,6 +79,14 @@ hipError_t lrm_launch_pose_footholds_compile(const float* quats, size_t nposes, 
 hipError_t lrm_launch_footholds_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
                                       const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, int32_t* count_out,
                                       int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st);
+// lrm_foothold_lists_posed_dev / lrm_foothold_offsets_dev (lrm_footholds_posed.hip): the same tables and tile_boxes;
+// offsets: device, nlegs * nposes + 1; d2_out and written_out may be null.  The kernel clamps every segment to
+// [0, capacity) before it stores.
+hipError_t lrm_launch_foothold_lists_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                           const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
+                                           const int64_t* offsets, size_t capacity, int32_t* idx_out, float* d2_out,
+                                           int32_t* written_out, hipStream_t st);
+hipError_t lrm_launch_foothold_offsets(const int32_t* count, size_t n, int64_t* offsets_out, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

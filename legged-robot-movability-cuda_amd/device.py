@@ -209,6 +209,22 @@ def footholds(bx, by, bz, tx, ty, tz, legs, quat=None, nominal=None, count=None,
     return count, best, best_d2
 
 
+def foothold_offsets(count, out=None):
+    """lrm_foothold_offsets_dev: the exclusive scan that turns the counts of footholds() into CSR offsets --
+    out[0] = 0, out[k + 1] = out[k] + max(count.view(-1)[k], 0) -> int64 [count.numel() + 1].  One launch, no
+    allocation inside, no host synchronisation."""
+    torch = _torch()
+    n = count.numel()
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
+        raise ValueError("count: expected a contiguous int32 CUDA tensor")
+    if out is None:
+        out = torch.empty(n + 1, dtype=torch.int64, device=count.device)
+    _check_out(out, count, torch.int64, n + 1, "offsets")
+    with torch.cuda.device(count.device):
+        _capi.check(_capi.load().lrm_foothold_offsets_dev(_dp(count) if n else None, n, _dp(out), _stream(count)))
+    return out
+
+
 def footholds_layout(nb, nlegs, device):
     """(pose_idx int32, leg_idx uint8) of the [l*nb + b] order of both foothold calls with one pose per body: entry
     l*nb + b is (b, l), so that ps.ik(tx, ty, tz, *footholds_layout(nb, nlegs, dev), target_idx=best.view(-1)) solves
@@ -392,6 +408,54 @@ class PoseSet:
                                                              self.nposes, self.nlegs, _dp(count), _dp(best), _dp(best_d2),
                                                              _dp(all_legs), _stream(self.workspace)))
         return count, best, best_d2, all_legs
+
+    def foothold_lists(self, tx, ty, tz, count=None, offsets=None, capacity=None, idx=None, d2=None, written=None, want_d2=True):
+        """lrm_foothold_lists_posed_dev: the reachable targets of every (pose, leg) in CSR form.  Segment o = l*nposes + p
+        of idx holds the targets leg l reaches under pose p in ascending index, from offsets[o] on, as far as
+        min(offsets[o + 1], capacity) leaves room; d2 holds, at the same positions, the squared distance to the leg's
+        nominal point that footholds() minimises; written[l, p] = the entries stored.  Nothing else in idx / d2 is
+        touched, whatever offsets holds (include/lrm.h).  -> (offsets int64[nlegs*nposes + 1], idx int32[capacity],
+        d2 float32[capacity] or None with want_d2=False, written int32[nlegs, nposes]).
+          * count=None and offsets=None: footholds() runs first; offsets=None: foothold_offsets(count).
+          * capacity=None and idx=None: offsets[-1] is read back to allocate exactly that -- ONE host synchronisation.
+            With capacity or a preallocated idx (capacity = its length) the call only launches, so update -> footholds
+            -> foothold_offsets -> foothold_lists can be captured in a graph after one warm call on the largest cloud;
+            a list that does not fit is cut short and written says so."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        if self.fh_workspace is None:
+            raise ValueError("PoseSet: built without footholds=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        n = self.nlegs * self.nposes
+        if offsets is None:
+            if count is None:
+                count = self.footholds(tx, ty, tz)[0]
+            _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
+            offsets = foothold_offsets(count.view(-1)[:n])
+        _check_out(offsets, self.workspace, torch.int64, n + 1, "offsets")
+        if capacity is None:
+            capacity = idx.numel() if idx is not None else max(int(offsets[n].item()), 0)  # the one synchronisation
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity >= 0")
+        if idx is None:
+            idx = torch.empty(capacity, dtype=torch.int32, device=self.device)
+        if d2 is None and want_d2:
+            d2 = torch.empty(capacity, dtype=torch.float32, device=self.device)
+        if written is None:
+            written = torch.empty((self.nlegs, self.nposes), dtype=torch.int32, device=self.device)
+        _check_out(idx, self.workspace, torch.int32, capacity, "list indices")
+        _check_out(d2, self.workspace, torch.float32, capacity, "list squared distances")
+        _check_out(written, self.workspace, torch.int32, n, "per-leg written counts")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_foothold_lists_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
+                                                                  _dp(self.fh_workspace), self.nposes, self.nlegs, _dp(offsets),
+                                                                  capacity, _dp(idx), _dp(d2) if want_d2 else None, _dp(written),
+                                                                  _stream(self.workspace)))
+        return offsets, idx, d2 if want_d2 else None, written
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
