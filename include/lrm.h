@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -462,6 +462,45 @@ int lrm_foothold_lists_posed_cpu(const float* targets_aos, size_t nt, const floa
                                  const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
                                  const int64_t* offsets /* host */, size_t capacity, int32_t* idx_out, float* d2_out,
                                  int32_t* written_out, double* ms);
+/* COMMON-foothold counts and choice per pose TRANSITION.  While the body moves from pose a to pose b a stance foot stays
+ * planted: its foothold must be reachable from both.  Pose table, leg table, `workspace` and `fh_workspace` are those of
+ * lrm_footholds_posed_dev (no new table, no new compile step).  With e an edge, a = edge_a[e], b = edge_b[e] (int32 pose
+ * indices, on the device for _dev and on the host for _cpu), triple (e, l, t) is common iff
+ *   reachability_global(t - body[a], legs[l], quats[a]) AND reachability_global(t - body[b], legs[l], quats[b]):
+ * the strict test on the two pose records, whatever lrm_set_mode says, without a gravity gate -- exactly
+ * lrm_footholds_posed_dev's rule, twice.  Every output has nlegs * nedges entries at [l*nedges + e], all written:
+ *   count_out     the number of common targets;
+ *   best_out      the common target with the smallest d2 (ties: the smaller index), -1 when count is 0;
+ *   best_d2_out   (may be NULL) that d2, +inf when count is 0;
+ *                 d2 = d2_a + d2_b, ONE float32 add (no contraction) of the two d2 of lrm_footholds_posed_dev, i.e. of
+ *                 (t - (body[a] + nominal_w[a,l]))^2 and (t - (body[b] + nominal_w[b,l]))^2: its minimum is the common
+ *                 target nearest the midpoint of the leg's two nominal foot positions;
+ *   all_legs_out  (may be NULL, nedges) 1 iff every leg has count > 0: the move is feasible with all feet planted.
+ * Consequences: for a == b count and best are lrm_footholds_posed_dev's of that pose and best_d2 is exactly twice its
+ * value (x + x is exact); swapping edge_a and edge_b changes no output bit; best_out is a valid target_idx of
+ * lrm_ik_posed_dev with pose_idx = either end of the edge.
+ * An edge with a or b outside [0, nposes) gives count 0, best -1, d2 +inf, all_legs 0: the kernel checks the indices
+ * before it loads any record and never reads outside the tables, so ANY edge_a / edge_b contents are memory-safe.
+ * Checked first: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX or more than 2^32 - 1 records, and
+ * nedges * nlegs > 2^32 - 1 give LRM_EINVAL; then nedges == 0 is a no-op; NULL edge_a / edge_b / count_out / best_out
+ * give LRM_EINVAL; nt == 0 gives count 0, best -1, d2 +inf everywhere.
+ * Threading and streams: lrm_foothold_edges_posed_dev is one of the pair kernels, with lrm_footholds_posed_dev's rules:
+ * the per-device tile-box buffer from 4096 targets on, one host thread at a time, no two pair launches on different
+ * clouds concurrently on one device; the first call for a larger cloud than the buffer holds allocates, every later call
+ * (and every call below 4096 targets) only launches, so compile -> footholds -> edges can be captured in a graph after
+ * one call on a cloud of the largest size.
+ * lrm_foothold_edges_posed_cpu: AoS float3 targets, host tables and host edges, a serial loop over every (edge, leg,
+ * target) with both strict tests and no culling: the reference the GPU tests compare with bit for bit; *ms = the loop's
+ * time. */
+int lrm_foothold_edges_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                                 const void* workspace, const void* fh_workspace, size_t nposes, size_t nlegs,
+                                 const int32_t* edge_a, const int32_t* edge_b /* device, nedges */, size_t nedges,
+                                 int32_t* count_out, int32_t* best_out, float* best_d2_out /* may be NULL */,
+                                 uint8_t* all_legs_out /* may be NULL, nedges */, void* stream);
+int lrm_foothold_edges_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                                 const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
+                                 const int32_t* edge_a, const int32_t* edge_b /* host */, size_t nedges,
+                                 int32_t* count_out, int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

@@ -126,6 +126,8 @@ def load():
         "lrm_foothold_offsets_dev": [vp, sz, vp, vp],
         "lrm_foothold_lists_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp],
         "lrm_foothold_lists_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp],
+        "lrm_foothold_edges_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp],
+        "lrm_foothold_edges_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -505,6 +507,31 @@ def foothold_lists_posed_cpu(targets, quats, body, legs, offsets, capacity=None,
                                               _ptr(d2) if want_d2 else None, _ptr(written) if want_written else None,
                                               C.addressof(ms)))
     return idx, d2 if want_d2 else None, written if want_written else None, ms.value
+
+
+def foothold_edges_posed_cpu(targets, quats, body, legs, edge_a, edge_b, nominal=None, want_d2=True, want_all_legs=True):
+    """lrm_foothold_edges_posed_cpu: per (leg, edge) the number of targets leg reaches under pose edge_a[e] AND under pose
+    edge_b[e], the common target with the smallest d2_a + d2_b (one float32 add of footholds_posed_cpu's two d2; -1 if
+    none), that sum (+inf if none), and per edge whether every leg has one.  An edge with an index outside
+    [0, nposes) gives 0, -1, +inf, 0.  Serial host loop, no culling; want_d2 / want_all_legs False pass NULL.
+    -> (count int32[nlegs, nedges], best int32[nlegs, nedges], best_d2 float32[nlegs, nedges] or None,
+    all_legs uint8[nedges] or None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    if len(edge_a) != len(edge_b):
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    shape = (len(legs), len(edge_a))
+    count, best = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    best_d2 = np.zeros(shape, np.float32) if want_d2 else None
+    all_legs = np.zeros(len(edge_a), np.uint8) if want_all_legs else None
+    ms = C.c_double(0)
+    check(load().lrm_foothold_edges_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs),
+                                              _ptr(nom), _ptr(edge_a), _ptr(edge_b), len(edge_a), _ptr(count), _ptr(best),
+                                              _ptr(best_d2), _ptr(all_legs), C.addressof(ms)))
+    return count, best, best_d2, all_legs, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

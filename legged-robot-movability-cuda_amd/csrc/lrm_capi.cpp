@@ -1560,6 +1560,97 @@ int lrm_foothold_lists_posed_cpu(const float* targets, size_t nt, const float* q
     return LRM_OK;
 }
 
+// ---- common-foothold counts and choice per pose transition (lrm_footholds_posed.hip) -----------
+namespace {
+// the range checks of both forms, before any early return
+int foothold_edges_args(size_t nt, size_t nposes, size_t nlegs, size_t nedges) {
+    const int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (nedges > (size_t)UINT32_MAX / nlegs) return fail(LRM_EINVAL, "foothold edges: more than 2^32 - 1 (edge, leg) outputs");
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_foothold_edges_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                                 const void* fh_workspace, size_t nposes, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b,
+                                 size_t nedges, int32_t* count_out, int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out,
+                                 void* stream) {
+    int rc = foothold_edges_args(nt, nposes, nlegs, nedges);
+    if (rc != LRM_OK) return rc;
+    if (nedges == 0) return LRM_OK;
+    if (!edge_a || !edge_b || !count_out || !best_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
+    if (nposes && (!workspace || !fh_workspace)) return fail(LRM_EINVAL, "null argument"); // without poses no record is ever read
+    if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
+        return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_foothold_edges_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, edge_a, edge_b, nedges,
+                                            count_out, best_out, best_d2_out, all_legs_out, (hipStream_t)stream),
+            "posed foothold edges launch");
+    return LRM_OK;
+}
+
+int lrm_foothold_edges_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                 const LrmLegDimensions* legs, size_t nlegs, const float* nominal, const int32_t* edge_a,
+                                 const int32_t* edge_b, size_t nedges, int32_t* count_out, int32_t* best_out, float* best_d2_out,
+                                 uint8_t* all_legs_out, double* ms) {
+    int rc = foothold_edges_args(nt, nposes, nlegs, nedges);
+    if (rc != LRM_OK) return rc;
+    if (!legs) return fail(LRM_EINVAL, "null argument");
+    if (nedges == 0) return LRM_OK;
+    if (!edge_a || !edge_b || !count_out || !best_out || (nposes && !quats) || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
+    if (nposes) {
+        host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+        host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
+    }
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t e = 0; e < nedges; e++) {
+        const int64_t a = edge_a[e], b = edge_b[e];
+        const bool valid = a >= 0 && b >= 0 && (uint64_t)a < nposes && (uint64_t)b < nposes;
+        bool all = valid;
+        for (size_t l = 0; l < nlegs; l++) {
+            int32_t count = 0;
+            uint64_t best = kLrmFootholdNone;
+            if (valid) {
+                const LrmPoseRecord& RA = recs[(size_t)a * nlegs + l];
+                const LrmPoseRecord& RB = recs[(size_t)b * nlegs + l];
+                const LrmCompiledLeg& LA = reinterpret_cast<const LrmCompiledLeg&>(RA.head); // lrm_point.h reads the head only
+                const LrmCompiledLeg& LB = reinterpret_cast<const LrmCompiledLeg&>(RB.head);
+                const LrmVec3 ba{RA.body_pos[0], RA.body_pos[1], RA.body_pos[2]}, bb{RB.body_pos[0], RB.body_pos[1], RB.body_pos[2]};
+                for (size_t t = 0; t < nt; t++) { // every target: no sphere is consulted
+                    const LrmVec3 tg{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
+                    const LrmVec3 rel_a{tg.x - ba.x, tg.y - ba.y, tg.z - ba.z}, rel_b{tg.x - bb.x, tg.y - bb.y, tg.z - bb.z};
+                    if (!lrm_reach_global(LA, &RA.head.lists[0][0], rel_a) || !lrm_reach_global(LB, &RB.head.lists[0][0], rel_b)) continue;
+                    count++;
+                    const float d2 = lrm_foothold_d2(tg, ba, ent[(size_t)a * nlegs + l].nominal_w) +
+                                     lrm_foothold_d2(tg, bb, ent[(size_t)b * nlegs + l].nominal_w); // one f32 add, no contraction
+                    const uint64_t key = lrm_foothold_key(d2, (uint32_t)t);
+                    if (key < best) best = key;
+                }
+            }
+            const size_t o = l * nedges + e;
+            count_out[o] = count;
+            best_out[o] = count ? (int32_t)(uint32_t)best : -1;
+            if (best_d2_out) {
+                const uint32_t hi = (uint32_t)(best >> 32);
+                float d2;
+                std::memcpy(&d2, &hi, sizeof d2);
+                best_d2_out[o] = count ? d2 : INFINITY;
+            }
+            all = all && count > 0;
+        }
+        if (all_legs_out) all_legs_out[e] = all;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
 namespace {
 int any_in_shape_impl(int shape, const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,
                       const float* ty, const float* tz, size_t nt, float radius, float plus_z, float minus_z,

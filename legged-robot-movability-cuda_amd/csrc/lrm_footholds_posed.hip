@@ -28,6 +28,8 @@
 //    without the keys: survivors reach process() in ascending target index, so a hit's rank in the list of (pose, leg)
 //    is the leg's running count plus the hits in lower lanes, and it is stored at that rank in the caller's segment.
 //  * foothold_offsets_kernel (lrm_foothold_offsets_dev): the exclusive scan between the two, one workgroup with a carry.
+//  * foothold_edges_posed_kernel (lrm_foothold_edges_posed_dev): a wave per pose TRANSITION (a, b); counts and chooses
+//    among the targets a leg reaches under both poses, with every cull the intersection of the two poses' (see there).
 //
 // boxes == null (clouds below the 4096-target threshold of the C ABI): every tile and every chunk counts as near.
 //
@@ -378,6 +380,236 @@ __global__ __launch_bounds__(kScanBlock) void foothold_offsets_kernel(const int3
     }
 }
 
+// lrm_foothold_edges_posed_dev: per (edge e = (pose a, pose b), leg l) the targets leg l reaches under BOTH poses -- the
+// footholds a stance foot can keep while the body moves from a to b -- counted, and the one with the smallest
+// d2(a) + d2(b) chosen.  A sibling of footholds_posed_traverse (that template is left alone: its two kernels keep their
+// code): a wave per edge, the same walk over tile boxes and chunk boxes, the same pipelined loads, LDS queue, ballots and
+// key minima.  Every cull is the intersection of the two poses':
+//   - a tile is near when its box is within r2max of both bodies;
+//   - a chunk is read when, for some leg, its box touches that leg's sphere under a AND under b;
+//   - a target is queued when it is within r2max of both bodies;
+//   - process() tests a target against leg l when it lies in both of l's spheres, runs the strict test of pose b only in
+//     the lanes where pose a's hit, and skips b for the wave when none did.
+// A +inf sphere or r2max excludes nothing on its side only.  Each wave stages the circle tables and spheres of both poses
+// (2 x 8 x 256 B + 2 x 128 B): 25 600 B of LDS per workgroup, which admits 6 workgroups on a CU's 160 KiB, i.e. 6 waves
+// per SIMD -- so the launch bound asks for 6, not 8, and the compiler gets 80 VGPRs instead of 64.
+// edge_a / edge_b are checked against nposes before any record is touched; a bad edge gets count 0, best -1, d2 +inf.
+#ifndef LRM_FOOTHOLD_EDGES_MIN_WAVES
+#define LRM_FOOTHOLD_EDGES_MIN_WAVES 6
+#endif
+__global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold_edges_posed_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, size_t nt,
+    const LrmPoseRecord* __restrict__ recs, const LrmPoseFootEntry* __restrict__ fh, uint32_t nposes, uint32_t nlegs,
+    const float* __restrict__ boxes /* null = every tile near */, const int32_t* __restrict__ edge_a,
+    const int32_t* __restrict__ edge_b, uint32_t nedges, int32_t* __restrict__ count_out, int32_t* __restrict__ best_out,
+    float* __restrict__ best_d2_out, uint8_t* __restrict__ all_legs_out) {
+    __shared__ float s_qx[kWaves][kQueue], s_qy[kWaves][kQueue], s_qz[kWaves][kQueue];
+    __shared__ uint32_t s_qi[kWaves][kQueue];
+    __shared__ LrmCircle s_lists[kWaves][2][LRM_MAX_LEGS][4 * LRM_N_CIRCLES]; // [0]: pose a's circle tables, [1]: pose b's
+    __shared__ float s_sphere[kWaves][2][LRM_MAX_LEGS][4];                    // the legs' spheres: centre (relative to the body), r^2
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    float* qx = s_qx[wave];
+    float* qy = s_qy[wave];
+    float* qz = s_qz[wave];
+    uint32_t* qi = s_qi[wave];
+    LrmCircle(*lists_a)[4 * LRM_N_CIRCLES] = s_lists[wave][0];
+    LrmCircle(*lists_b)[4 * LRM_N_CIRCLES] = s_lists[wave][1];
+    float(*sph_a)[4] = s_sphere[wave][0];
+    float(*sph_b)[4] = s_sphere[wave][1];
+    const size_t ntiles = (nt + kTargetTile - 1) / kTargetTile;
+    const bool mine = (uint32_t)lane < nlegs;
+
+    for (uint64_t e = blockIdx.x * kWaves + wave; e < nedges; e += (uint64_t)gridDim.x * kWaves) { // wave-uniform
+        const uint32_t pa = (uint32_t)__builtin_amdgcn_readfirstlane(edge_a[e]);
+        const uint32_t pb = (uint32_t)__builtin_amdgcn_readfirstlane(edge_b[e]);
+        if (pa >= nposes || pb >= nposes) { // negative indices included; before any record is read
+            if (mine) {
+                const size_t o = (size_t)lane * nedges + e;
+                count_out[o] = 0;
+                best_out[o] = -1;
+                if (best_d2_out) best_d2_out[o] = __builtin_inff();
+            }
+            if (all_legs_out && lane == 0) all_legs_out[e] = 0;
+            continue;
+        }
+        const uint32_t ra0 = pa * nlegs, rb0 = pb * nlegs; // nposes * nlegs < 2^32 (checked by the C ABI)
+        // stage both poses' tables: every lane is done with the previous edge's
+        wave_lds_fence();
+        for (uint32_t l = 0; l < nlegs; l++) {
+            reinterpret_cast<float*>(lists_a[l])[lane] = reinterpret_cast<const float*>(&recs[ra0 + l].head.lists[0][0])[lane];
+            reinterpret_cast<float*>(lists_b[l])[lane] = reinterpret_cast<const float*>(&recs[rb0 + l].head.lists[0][0])[lane];
+        }
+        { // lanes 0-31: pose a's spheres, lanes 32-63: pose b's
+            const uint32_t k = (uint32_t)lane & 31u;
+            if (k < nlegs * 4) s_sphere[wave][lane >> 5][k >> 2][k & 3] = reinterpret_cast<const float*>(&fh[(lane < 32 ? ra0 : rb0) + (k >> 2)])[k & 3];
+        }
+        wave_lds_fence();
+        const LrmPoseRecord& RA = lrm_fresh(recs[ra0]);
+        const LrmPoseRecord& RB = lrm_fresh(recs[rb0]);
+        const LrmVec3 body_a{RA.body_pos[0], RA.body_pos[1], RA.body_pos[2]}; // the same in every record of the pose
+        const LrmVec3 body_b{RB.body_pos[0], RB.body_pos[1], RB.body_pos[2]};
+        float r2a = 0.f, r2b = 0.f;
+        for (uint32_t l = 0; l < nlegs; l++) {
+            r2a = fmaxf(r2a, lrm_fresh(fh[ra0 + l]).cull_r2 < __builtin_inff() ? lrm_fresh(recs[ra0 + l]).head.reach_r2_max : __builtin_inff());
+            r2b = fmaxf(r2b, lrm_fresh(fh[rb0 + l]).cull_r2 < __builtin_inff() ? lrm_fresh(recs[rb0 + l]).head.reach_r2_max : __builtin_inff());
+        }
+
+        int count = 0;        // survivors waiting in this wave's queue
+        uint32_t legs_n = 0;  // lane l: leg l's common targets
+        uint64_t key[LRM_MAX_LEGS]; // this lane's best candidate per leg (constant indices only: registers)
+#pragma unroll
+        for (int k = 0; k < LRM_MAX_LEGS; k++) key[k] = kLrmFootholdNone;
+
+        auto process = [&](int m) {
+            LrmVec3 t{0.f, 0.f, 0.f};
+            uint32_t ti = 0u;
+            if (lane < m) {
+                t = LrmVec3{qx[lane], qy[lane], qz[lane]};
+                ti = qi[lane];
+            }
+            const LrmVec3 rel_a{t.x - body_a.x, t.y - body_a.y, t.z - body_a.z};
+            const LrmVec3 rel_b{t.x - body_b.x, t.y - body_b.y, t.z - body_b.z};
+            for (uint32_t l = 0; l < nlegs; l++) {
+                const LrmPoseFootEntry& EA = lrm_fresh(fh[ra0 + l]);
+                const LrmPoseFootEntry& EB = lrm_fresh(fh[rb0 + l]);
+                const float ax = rel_a.x - EA.cull_center[0], ay = rel_a.y - EA.cull_center[1], az = rel_a.z - EA.cull_center[2];
+                const float bx = rel_b.x - EB.cull_center[0], by = rel_b.y - EB.cull_center[1], bz = rel_b.z - EB.cull_center[2];
+                const bool inside = (lane < m) && __builtin_fmaf(az, az, __builtin_fmaf(ay, ay, ax * ax)) <= EA.cull_r2 &&
+                                    __builtin_fmaf(bz, bz, __builtin_fmaf(by, by, bx * bx)) <= EB.cull_r2;
+                if (__ballot(inside) == 0ull) continue;
+                bool hit = false;
+                if (inside) {
+                    const LrmPoseRecord& R = lrm_fresh(recs[ra0 + l]);
+                    hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), lists_a[l], rel_a);
+                }
+                if (__ballot(hit) == 0ull) continue; // nobody reaches it under a: b is not asked
+                if (hit) {
+                    const LrmPoseRecord& R = lrm_fresh(recs[rb0 + l]);
+                    hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), lists_b[l], rel_b);
+                }
+                const unsigned long long hm = __ballot(hit);
+                if (hm == 0ull) continue; // wave-uniform
+                if ((uint32_t)lane == l) legs_n += (uint32_t)__builtin_popcountll(hm);
+                // one f32 add of the two poses' d2 (no contraction: -ffp-contract=off); it commutes
+                const uint64_t kk = hit ? lrm_foothold_key(lrm_foothold_d2(t, body_a, EA.nominal_w) + lrm_foothold_d2(t, body_b, EB.nominal_w), ti)
+                                        : kLrmFootholdNone;
+#pragma unroll
+                for (int k = 0; k < LRM_MAX_LEGS; k++)
+                    if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+            }
+        };
+
+        for (size_t tg0 = 0; tg0 < ntiles; tg0 += 64) {
+            // lane = tile: near only when the box is within reach of BOTH bodies (0.999: the rounding of the bound itself)
+            const size_t tl = tg0 + lane;
+            unsigned long long near = __ballot(tl < ntiles && (!boxes || (box_dist2(boxes + tl * 6, body_a.x, body_a.y, body_a.z) * 0.999f <= r2a &&
+                                                                          box_dist2(boxes + tl * 6, body_b.x, body_b.y, body_b.z) * 0.999f <= r2b)));
+            while (near != 0ull) {
+                const int tb = __builtin_ctzll(near);
+                near &= near - 1ull;
+                const size_t tile = tg0 + tb;
+                const size_t t0 = tile * kTargetTile;
+                // lane = (chunk of this tile, one of four legs): a chunk is read when, for some leg, its box touches
+                // that leg's sphere under a and under b (empty chunks carry an inverted box)
+                uint32_t cnear = 0u;
+                if (boxes) {
+                    const float* cb = boxes + (ntiles + tile * 16 + (lane & 15)) * 6;
+                    for (uint32_t l0 = 0; l0 < nlegs; l0 += 4) { // wave-uniform
+                        const uint32_t l = l0 + (lane >> 4);
+                        bool touch = false;
+                        if (l < nlegs)
+                            touch = box_dist2(cb, body_a.x + sph_a[l][0], body_a.y + sph_a[l][1], body_a.z + sph_a[l][2]) * 0.999f <= sph_a[l][3] &&
+                                    box_dist2(cb, body_b.x + sph_b[l][0], body_b.y + sph_b[l][1], body_b.z + sph_b[l][2]) * 0.999f <= sph_b[l][3];
+                        const unsigned long long mm = __ballot(touch);
+                        cnear |= (uint32_t)((mm | (mm >> 16) | (mm >> 32) | (mm >> 48)) & 0xffffull);
+                    }
+                } else {
+                    const size_t left = nt - t0; // > 0: tile < ntiles
+                    const int chunks = left >= (size_t)kTargetTile ? 16 : (int)((left + 63) / 64);
+                    cnear = chunks == 16 ? 0xffffu : (1u << chunks) - 1u;
+                }
+                // software pipeline: the next near chunk's loads are issued before this one is tested
+                LrmVec3 nxt{0.f, 0.f, 0.f};
+                uint32_t nxt_i = 0u;
+                bool nxt_ok = false;
+                auto fetch = [&](int chunk) {
+                    const size_t i = t0 + (size_t)chunk * 64 + lane;
+                    nxt_ok = i < nt;
+                    nxt_i = (uint32_t)i; // nt <= INT32_MAX (checked by the C ABI)
+                    if (nxt_ok) nxt = LrmVec3{tx[i], ty[i], tz[i]};
+                };
+                if (cnear) {
+                    fetch(__builtin_ctz(cnear));
+                    cnear &= cnear - 1u;
+                }
+                bool more = true;
+                while (more) {
+                    const LrmVec3 t = nxt;
+                    const uint32_t ti = nxt_i;
+                    const bool ok = nxt_ok;
+                    more = cnear != 0u;
+                    if (more) {
+                        fetch(__builtin_ctz(cnear));
+                        cnear &= cnear - 1u;
+                    }
+                    const float ax = t.x - body_a.x, ay = t.y - body_a.y, az = t.z - body_a.z;
+                    const float bx = t.x - body_b.x, by = t.y - body_b.y, bz = t.z - body_b.z;
+                    const bool keep = ok && __builtin_fmaf(az, az, __builtin_fmaf(ay, ay, ax * ax)) <= r2a &&
+                                      __builtin_fmaf(bz, bz, __builtin_fmaf(by, by, bx * bx)) <= r2b;
+                    const unsigned long long m = __ballot(keep);
+                    if (m == 0ull) continue;
+                    if (keep) {
+                        const int pos = count + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                        qx[pos] = t.x;
+                        qy[pos] = t.y;
+                        qz[pos] = t.z;
+                        qi[pos] = ti;
+                    }
+                    count += __builtin_popcountll(m);
+                    wave_lds_fence();
+                    if (count >= 64) {
+                        process(64);
+                        count -= 64;
+                        // the (< 64) entries behind the processed batch move to the front
+                        float mx = 0.f, my = 0.f, mz = 0.f;
+                        uint32_t mi = 0u;
+                        if (lane < count) { mx = qx[64 + lane]; my = qy[64 + lane]; mz = qz[64 + lane]; mi = qi[64 + lane]; }
+                        wave_lds_fence();
+                        if (lane < count) { qx[lane] = mx; qy[lane] = my; qz[lane] = mz; qi[lane] = mi; }
+                        wave_lds_fence();
+                    }
+                }
+            }
+        }
+        if (count > 0) process(count);
+
+        // per leg: the wave's smallest key; lane l keeps leg l's
+        uint64_t best = kLrmFootholdNone;
+#pragma unroll
+        for (int k = 0; k < LRM_MAX_LEGS; k++) {
+            if ((uint32_t)k >= nlegs) break; // wave-uniform
+            uint64_t v = key[k];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
+                v = min_u64(v, ((uint64_t)hi << 32) | lo);
+            }
+            if (lane == k) best = v;
+        }
+        if (mine) {
+            const size_t o = (size_t)lane * nedges + e;
+            count_out[o] = (int32_t)legs_n;
+            best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
+            if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+        }
+        if (all_legs_out) { // wave-uniform
+            const unsigned long long have = __ballot(mine && legs_n != 0u);
+            if (lane == 0) all_legs_out[e] = have == ((1ull << nlegs) - 1ull);
+        }
+    }
+}
+
 } // namespace
 
 hipError_t lrm_launch_pose_footholds_compile(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
@@ -422,6 +654,23 @@ hipError_t lrm_launch_foothold_lists_posed(const float* tx, const float* ty, con
     hipLaunchKernelGGL(foothold_lists_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
                        (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, offsets, cap, idx_out, d2_out,
                        written_out);
+    return hipGetLastError();
+}
+
+hipError_t lrm_launch_foothold_edges_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                           const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
+                                           const int32_t* edge_a, const int32_t* edge_b, size_t nedges, int32_t* count_out,
+                                           int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st) {
+    if (tile_boxes && nt) {
+        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
+        if (e != hipSuccess) return e;
+    }
+    size_t g = (nedges + kWaves - 1) / kWaves;
+    if (g > kMaxGrid) g = kMaxGrid;
+    const float* boxes = nt ? tile_boxes : nullptr;
+    hipLaunchKernelGGL(foothold_edges_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, edge_a, edge_b, (uint32_t)nedges,
+                       count_out, best_out, best_d2_out, all_legs_out);
     return hipGetLastError();
 }
 

@@ -87,6 +87,13 @@ hipError_t lrm_launch_foothold_lists_posed(const float* tx, const float* ty, con
                                            const int64_t* offsets, size_t capacity, int32_t* idx_out, float* d2_out,
                                            int32_t* written_out, hipStream_t st);
 hipError_t lrm_launch_foothold_offsets(const int32_t* count, size_t n, int64_t* offsets_out, hipStream_t st);
+// lrm_foothold_edges_posed_dev (lrm_footholds_posed.hip): the same tables and tile_boxes; edge_a / edge_b: device, nedges
+// pose indices of any value (the kernel checks them); outputs [nlegs * nedges] at l * nedges + e and all_legs_out[nedges];
+// best_d2_out and all_legs_out may be null.  nedges * nlegs < 2^32 (checked by the C ABI).
+hipError_t lrm_launch_foothold_edges_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                           const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
+                                           const int32_t* edge_a, const int32_t* edge_b, size_t nedges, int32_t* count_out,
+                                           int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

@@ -240,6 +240,23 @@ def footholds_layout(nb, nlegs, device):
     return pose, leg
 
 
+def foothold_edges_layout(nedges, nlegs, device, edge_a, edge_b, which="a"):
+    """(pose_idx int32, leg_idx uint8) of the [l*nedges + e] order of PoseSet.foothold_edges for ONE end of every edge:
+    entry l*nedges + e is (edge_a[e] or edge_b[e], l), so that
+    ps.ik(tx, ty, tz, *foothold_edges_layout(ne, nlegs, dev, ea, eb, "b"), target_idx=best.view(-1)) solves every chosen
+    common foothold under the pose the body moves to ("a": the pose it leaves).  edge_a / edge_b: the int32 device tensors
+    of the query; an edge whose best is -1 gets ik()'s status 0 (give ik() check=False if the edges hold bad indices)."""
+    torch = _torch()
+    if which not in ("a", "b"):
+        raise ValueError('which: "a" or "b"')
+    edge = edge_a if which == "a" else edge_b
+    if not (edge.dtype == torch.int32 and edge.numel() == nedges):
+        raise ValueError("edge_a / edge_b: int32 tensors of nedges pose indices")
+    pose = edge.reshape(-1).to(device).repeat(nlegs)
+    leg = torch.arange(nlegs, dtype=torch.uint8, device=device).repeat_interleave(nedges)
+    return pose, leg
+
+
 def positionability(bx, by, bz, tx, ty, tz, legs, quats, reference_culls=0, active=None, out=None):
     """lrm_positionability_dev: the orientation sweep of robot_full_struct on device-resident clouds and masks.
     reference_culls: 0 none, 2 the per-orientation cylinder culls.  -> (accepted uint8[nb] on the device, kernel ms)"""
@@ -320,7 +337,7 @@ class PoseSet:
     compiles it too on the same stream, and ik() / fk() answer joint-angle queries.  footholds=True: the set owns the
     foothold table as well (32 bytes per (pose, leg): bounding sphere and nominal point, nominal (nlegs, 3) on the host
     in the BODY frame or None = zero), update() compiles it on the same stream, and footholds() counts and chooses the
-    reachable targets per (pose, leg)."""
+    reachable targets per (pose, leg); foothold_edges() does the same for the targets two poses have in common."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -456,6 +473,53 @@ class PoseSet:
                                                                   capacity, _dp(idx), _dp(d2) if want_d2 else None, _dp(written),
                                                                   _stream(self.workspace)))
         return offsets, idx, d2 if want_d2 else None, written
+
+    def foothold_edges(self, tx, ty, tz, edge_a, edge_b, count=None, best=None, best_d2=None, all_legs=None, check=True):
+        """lrm_foothold_edges_posed_dev: per pose transition e = (edge_a[e], edge_b[e]) (int32 device tensors of pose
+        indices) and leg l, the targets leg l reaches under BOTH poses, i.e. the footholds a stance foot can keep during
+        the move.  count[l, e] = how many, best[l, e] = the common target with the smallest sum of footholds()'s two d2
+        (-1 if none), best_d2[l, e] = that sum (+inf if none), all_legs[e] = 1 iff every leg has one.
+        -> (count int32, best int32, best_d2 float32, each [nlegs, nedges]; all_legs uint8[nedges]).  check=True
+        validates the indices on the host (one synchronisation); check=False leaves an index outside [0, nposes) to the
+        kernel (count 0, best -1, +inf, all_legs 0): the form for graph capture.  One launch behind the cloud's bounding
+        boxes; best.view(-1) is ik()'s target_idx with foothold_edges_layout() for either end of the edges."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        if self.fh_workspace is None:
+            raise ValueError("PoseSet: built without footholds=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        ne = edge_a.numel()
+        _check_out(edge_a, self.workspace, torch.int32, ne, "edge_a")
+        _check_out(edge_b, self.workspace, torch.int32, ne, "edge_b")
+        if edge_b.numel() != ne:
+            raise ValueError("edge_a / edge_b: one pose index each per edge")
+        if check and ne:
+            lo = min(int(edge_a.min()), int(edge_b.min()))
+            hi = max(int(edge_a.max()), int(edge_b.max()))
+            if lo < 0 or hi >= self.nposes:
+                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
+        shape, n = (self.nlegs, ne), self.nlegs * ne
+        if count is None:
+            count = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if best is None:
+            best = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if best_d2 is None:
+            best_d2 = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if all_legs is None:
+            all_legs = torch.empty(ne, dtype=torch.uint8, device=self.device)
+        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
+        _check_out(best, self.workspace, torch.int32, n, "per-leg choices")
+        _check_out(best_d2, self.workspace, torch.float32, n, "per-leg squared distances")
+        _check_out(all_legs, self.workspace, torch.uint8, ne, "per-edge bytes")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_foothold_edges_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
+                                                                  _dp(self.fh_workspace), self.nposes, self.nlegs, _dp(edge_a),
+                                                                  _dp(edge_b), ne, _dp(count), _dp(best), _dp(best_d2), _dp(all_legs),
+                                                                  _stream(self.workspace)))
+        return count, best, best_d2, all_legs
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
