@@ -1,7 +1,8 @@
 """Batched multi-pose queries on the MI355X (run with -m gpu): the device pose compiler against the host's, the posed kernel
 against the oracle per (pose, leg) in every index order, against the reference fixtures and against the single-pose strict
-call, at scale, and captured in a graph.  Every output bit must be equal.  No test here feeds an out-of-range index to the
-kernel (tests/test_posed_cpu.py covers that rule on the host)."""
+call, at scale, and captured in a graph.  Every output bit must be equal.  Out-of-range indices reach the kernel in
+tests/test_gpu_query_shapes.py, next to its wave, block and pass boundaries (tests/test_posed_cpu.py covers that rule on the
+host)."""
 import numpy as np
 import pytest
 
