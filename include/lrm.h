@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_foothold_misses_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -501,6 +501,56 @@ int lrm_foothold_edges_posed_cpu(const float* targets_aos, size_t nt, const floa
                                  const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
                                  const int32_t* edge_a, const int32_t* edge_b /* host */, size_t nedges,
                                  int32_t* count_out, int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, double* ms);
+/* NEAREST-MISS footholds per (pose, leg): for a leg that reaches nothing, the target that is closest to being reachable
+ * and the body translation that would make it so.  Pose table, leg table, `workspace` and `fh_workspace` are those of
+ * lrm_footholds_posed_dev (no new table, no new compile step).  One extra scalar, `margin` (mm, float32): margin >= 0 or
+ * +inf is accepted, negative or nan gives LRM_EINVAL.  One optional input, count_in (int32, nlegs*nposes, device for _dev
+ * and host for _cpu, may be NULL): wherever count_in[o] > 0 that (pose, leg) is skipped and gets the empty answer
+ * (entries <= 0, negative ones included, are not skipped).  Pass count_out of lrm_footholds_posed_dev so that only
+ * footless legs cost anything.
+ * With o = l*nposes + p, E the foothold entry of (p, l) and q = t - body[p] (one float32 subtraction per component, as
+ * everywhere in the posed calls), all float32 without contraction, device and host identical:
+ *   candidate  target t is a candidate iff e2 <= rm2, with e = q - E.cull_center (one subtraction per component),
+ *              e2 = (ex*ex + ey*ey) + ez*ez, rm = sqrtf(E.cull_r2) + margin (correctly rounded), rm2 = rm*rm.
+ *              cull_r2 = +inf (non-unit quaternion) or margin = +inf makes every target with a non-nan e2 a candidate.
+ *   miss       a candidate with reachability_global(q, legs[l], quats[p]) == 0; its vector is
+ *              d = distance_global(q, legs[l], quats[p]): the strict evaluation whatever lrm_set_mode says, the bytes
+ *              lrm_reach_dist_posed_cpu returns.  m2 = (dx*dx + dy*dy) + dz*dz.  A miss is eligible iff m2 < +inf
+ *              (false for nan).
+ * Every output has nlegs * nposes entries at [o], all written:
+ *   miss_out     the eligible miss with the smallest (m2, index) -- the m2 bits order like its value, ties go to the
+ *                smaller index; -1 when there is none;
+ *   miss_m2_out  (may be NULL) that m2, +inf when there is none;
+ *   shift_x / shift_y / shift_z  (all three or none; else LRM_EINVAL) that d, nan (the one bit pattern 0x7fc00000) when
+ *                there is none.  Translating the body by d at fixed orientation puts the target on the workspace
+ *                boundary: t - (body + d) = q - d, the reference's nearest point;
+ *   near_out     (may be NULL) the number of misses, eligible or not: the number of distance evaluations the entry cost.
+ *                A skipped entry gets 0.
+ * Consequences: lrm_reach_dist_posed_* on (miss_out[o], p, l) returns mask 0 and exactly the shift bits; with
+ * margin = +inf the answer is the minimum over ALL unreachable targets; a larger margin never gives a larger m2.
+ * Checked first, in lrm_footholds_posed_dev's order: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX or
+ * more than 2^32 - 1 records, then a bad margin give LRM_EINVAL; then nposes == 0 is a no-op; NULL miss_out gives
+ * LRM_EINVAL; nt == 0 gives the empty answer (-1, +inf, nan, 0) everywhere.
+ * Threading and streams: lrm_foothold_misses_posed_dev is one of the pair kernels, with lrm_footholds_posed_dev's rules:
+ * the per-device tile-box buffer from 4096 targets on, one host thread at a time, no two pair launches on different
+ * clouds concurrently on one device; the first call for a larger cloud than the buffer holds allocates, every later call
+ * (and every call below 4096 targets) only launches, so compile -> footholds -> foothold_misses(count_in = count_out)
+ * can be captured in a graph after one call on a cloud of the largest size.  The box culls keep every candidate: their
+ * radius carries an absolute slack of 2^-21 (max|body| + max|centre| + rm) for the different roundings of
+ * (t - body) - centre and of body + centre (csrc/lrm_foothold_misses.hip).
+ * lrm_foothold_misses_posed_cpu: AoS float3 targets, host tables and a host count_in, a serial loop over every (pose,
+ * leg, target) with the same candidate function and the strict code and no box culling: the reference the GPU tests
+ * compare with bit for bit; *ms = the loop's time. */
+int lrm_foothold_misses_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                                  const void* workspace, const void* fh_workspace, size_t nposes, size_t nlegs,
+                                  float margin, const int32_t* count_in /* device, nlegs*nposes, may be NULL */,
+                                  int32_t* miss_out, float* miss_m2_out /* may be NULL */,
+                                  float* shift_x, float* shift_y, float* shift_z /* all three or none */,
+                                  int32_t* near_out /* may be NULL */, void* stream);
+int lrm_foothold_misses_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                                  const LrmLegDimensions* legs, size_t nlegs, float margin,
+                                  const int32_t* count_in /* host, may be NULL */, int32_t* miss_out, float* miss_m2_out,
+                                  float* shift_x, float* shift_y, float* shift_z, int32_t* near_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

@@ -13,6 +13,7 @@ from ._capi import (  # noqa: F401
     apply_ik_posed_cpu, apply_fk_posed_cpu, dbg_pose_ik_compile_host, POSE_IK_RECORD_BYTES,
     footholds_posed_cpu, dbg_pose_footholds_compile_host, POSE_FOOTHOLD_BYTES, foothold_lists_posed_cpu,
     foothold_edges_posed_cpu,
+    foothold_misses_posed_cpu,
 )
 from . import device  # noqa: F401
 from .device import PoseSet, ik, fk, foothold_offsets, foothold_edges_layout  # noqa: F401

@@ -128,6 +128,8 @@ def load():
         "lrm_foothold_lists_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp],
         "lrm_foothold_edges_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp],
         "lrm_foothold_edges_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp],
+        "lrm_foothold_misses_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, fp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_foothold_misses_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, fp, vp, vp, vp, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -532,6 +534,33 @@ def foothold_edges_posed_cpu(targets, quats, body, legs, edge_a, edge_b, nominal
                                               _ptr(nom), _ptr(edge_a), _ptr(edge_b), len(edge_a), _ptr(count), _ptr(best),
                                               _ptr(best_d2), _ptr(all_legs), C.addressof(ms)))
     return count, best, best_d2, all_legs, ms.value
+
+
+def foothold_misses_posed_cpu(targets, quats, body, legs, margin, count_in=None, want_m2=True, want_shift=True, want_near=True):
+    """lrm_foothold_misses_posed_cpu: per (leg, pose) not skipped by count_in (int32[nlegs, nposes] or None; > 0 skips) the
+    unreachable target inside the entry's sphere widened by margin (mm, >= 0 or +inf) whose distance_global vector is the
+    shortest (-1 if none), that squared length m2 (+inf if none), the vector itself -- the body translation that puts the
+    target on the workspace boundary (nan if none) -- and the number of unreachable candidates.  Serial host loop, no box
+    culling; want_* False pass NULL.
+    -> (miss int32[nlegs, nposes], m2 float32[nlegs, nposes] or None, shift float32[3, nlegs, nposes] or None,
+    near int32[nlegs, nposes] or None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    shape = (len(legs), len(quats))
+    if count_in is not None:
+        count_in = np.ascontiguousarray(count_in, np.int32)
+        if count_in.size != shape[0] * shape[1]:
+            raise ValueError("count_in: nlegs * nposes entries")
+    miss = np.zeros(shape, np.int32)
+    m2 = np.zeros(shape, np.float32) if want_m2 else None
+    shift = np.zeros((3,) + shape, np.float32) if want_shift else None
+    near = np.zeros(shape, np.int32) if want_near else None
+    ms = C.c_double(0)
+    check(load().lrm_foothold_misses_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs),
+                                               float(margin), _ptr(count_in), _ptr(miss), _ptr(m2),
+                                               _ptr(shift[0]) if want_shift else None, _ptr(shift[1]) if want_shift else None,
+                                               _ptr(shift[2]) if want_shift else None, _ptr(near), C.addressof(ms)))
+    return miss, m2, shift, near, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

@@ -1651,6 +1651,103 @@ int lrm_foothold_edges_posed_cpu(const float* targets, size_t nt, const float* q
     return LRM_OK;
 }
 
+// ---- nearest-miss footholds per (pose, leg): target and body shift (lrm_foothold_misses.hip) -----------
+namespace {
+// lrm_footholds_posed_dev's range checks, then the margin's, before any early return
+int foothold_misses_args(size_t nt, size_t nposes, size_t nlegs, float margin) {
+    const int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (!(margin >= 0.f)) return fail(LRM_EINVAL, "foothold misses: margin must be >= 0 or +inf"); // negative and nan
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_foothold_misses_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                                  const void* fh_workspace, size_t nposes, size_t nlegs, float margin, const int32_t* count_in,
+                                  int32_t* miss_out, float* miss_m2_out, float* shift_x, float* shift_y, float* shift_z,
+                                  int32_t* near_out, void* stream) {
+    int rc = foothold_misses_args(nt, nposes, nlegs, margin);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!workspace || !fh_workspace || !miss_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
+    if (!shift_x != !shift_y || !shift_x != !shift_z) return fail(LRM_EINVAL, "foothold misses: give all three shift components or none");
+    if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
+        return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_foothold_misses_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, margin, count_in, miss_out,
+                                             miss_m2_out, shift_x, shift_y, shift_z, near_out, (hipStream_t)stream),
+            "posed foothold misses launch");
+    return LRM_OK;
+}
+
+int lrm_foothold_misses_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                  const LrmLegDimensions* legs, size_t nlegs, float margin, const int32_t* count_in,
+                                  int32_t* miss_out, float* miss_m2_out, float* shift_x, float* shift_y, float* shift_z,
+                                  int32_t* near_out, double* ms) {
+    int rc = foothold_misses_args(nt, nposes, nlegs, margin);
+    if (rc != LRM_OK) return rc;
+    if (!legs) return fail(LRM_EINVAL, "null argument");
+    if (nposes == 0) return LRM_OK;
+    if (!quats || !miss_out || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    if (!shift_x != !shift_y || !shift_x != !shift_z) return fail(LRM_EINVAL, "foothold misses: give all three shift components or none");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
+    host_pose_foothold_entries(quats, nposes, legs, nlegs, nullptr, ent.data()); // the sphere does not depend on the nominal point
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t p = 0; p < nposes; p++) {
+        for (size_t l = 0; l < nlegs; l++) {
+            const size_t o = l * nposes + p;
+            const LrmPoseRecord& R = recs[p * nlegs + l];
+            const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+            const LrmPoseFootEntry& E = ent[p * nlegs + l];
+            const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
+            int32_t near = 0;
+            uint64_t best = kLrmFootholdNone;
+            LrmVec3 best_d{std::nanf(""), std::nanf(""), std::nanf("")};
+            if (!(count_in && count_in[o] > 0)) { // a skipped entry keeps the empty answer
+                const float rm2 = lrm_foothold_miss_rm2(E.cull_r2, margin);
+                for (size_t t = 0; t < nt; t++) { // every target: no box is consulted
+                    const LrmVec3 q{targets[3 * t] - b.x, targets[3 * t + 1] - b.y, targets[3 * t + 2] - b.z};
+                    if (!lrm_foothold_miss_candidate(q, E.cull_center, rm2)) continue;
+                    if (lrm_reach_global(L, &R.head.lists[0][0], q)) continue;
+                    near++;
+                    LrmVec3 d = q;
+                    lrm_dist_global(L, &R.head.lists[0][0], d);
+                    const float m2 = lrm_foothold_miss_m2(d);
+                    if (!(m2 < INFINITY)) continue;
+                    const uint64_t key = lrm_foothold_key(m2, (uint32_t)t);
+                    if (key < best) {
+                        best = key;
+                        best_d = d;
+                    }
+                }
+            }
+            const bool have = best != kLrmFootholdNone;
+            miss_out[o] = have ? (int32_t)(uint32_t)best : -1;
+            if (miss_m2_out) {
+                const uint32_t hi = (uint32_t)(best >> 32);
+                float m2;
+                std::memcpy(&m2, &hi, sizeof m2);
+                miss_m2_out[o] = have ? m2 : INFINITY;
+            }
+            if (shift_x) {
+                shift_x[o] = best_d.x;
+                shift_y[o] = best_d.y;
+                shift_z[o] = best_d.z;
+            }
+            if (near_out) near_out[o] = near;
+        }
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
 namespace {
 int any_in_shape_impl(int shape, const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,
                       const float* ty, const float* tz, size_t nt, float radius, float plus_z, float minus_z,

@@ -86,3 +86,23 @@ LRM_HD void lrm_pose_foothold_entry(const LrmLegDimensions& leg, const float qua
     E->cull_center[2] = w.z;
     E->cull_r2 = out_r2;
 }
+
+// ---- nearest-miss footholds (lrm_foothold_misses_posed_dev / _cpu, lrm_foothold_misses.hip) ----------------------
+// One arithmetic for the kernel and the host loop, float32 without contraction: these three functions decide outputs
+// (which targets are candidates, and the order of the misses), so the conservative fmaf sphere tests of the other pair
+// kernels are NOT a substitute for them.
+//
+// rm2 of an entry: the square of the entry's radius widened by `margin` (mm).  cull_r2 = +inf or margin = +inf give +inf.
+LRM_HD float lrm_foothold_miss_rm2(float cull_r2, float margin) {
+    const float rm = lrm_sqrtf(cull_r2) + margin;
+    return rm * rm;
+}
+// Target q = t - body[p] (already subtracted, one f32 subtraction per component) is a candidate of the entry with centre
+// `center` iff e2 <= rm2, e = q - center.  A nan e2 is no candidate; rm2 = +inf takes every other target.
+LRM_HD bool lrm_foothold_miss_candidate(LrmVec3 q, const float center[3], float rm2) {
+    const float ex = q.x - center[0], ey = q.y - center[1], ez = q.z - center[2];
+    const float e2 = (ex * ex + ey * ey) + ez * ez;
+    return e2 <= rm2;
+}
+// m2 of a miss: the squared length of its distance_global vector; the miss is eligible iff m2 < +inf (false for nan)
+LRM_HD float lrm_foothold_miss_m2(LrmVec3 d) { return (d.x * d.x + d.y * d.y) + d.z * d.z; }

@@ -94,6 +94,13 @@ hipError_t lrm_launch_foothold_edges_posed(const float* tx, const float* ty, con
                                            const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
                                            const int32_t* edge_a, const int32_t* edge_b, size_t nedges, int32_t* count_out,
                                            int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st);
+// lrm_foothold_misses_posed_dev (lrm_foothold_misses.hip): the same tables and tile_boxes; margin >= 0 or +inf (checked by
+// the C ABI); count_in: device, nlegs * nposes, or null; outputs [nlegs * nposes] at l * nposes + p; miss_m2_out, the three
+// shift arrays (all or none) and near_out may be null.
+hipError_t lrm_launch_foothold_misses_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                            const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, float margin,
+                                            const int32_t* count_in, int32_t* miss_out, float* miss_m2_out, float* shift_x,
+                                            float* shift_y, float* shift_z, int32_t* near_out, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

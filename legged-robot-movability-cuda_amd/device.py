@@ -337,7 +337,8 @@ class PoseSet:
     compiles it too on the same stream, and ik() / fk() answer joint-angle queries.  footholds=True: the set owns the
     foothold table as well (32 bytes per (pose, leg): bounding sphere and nominal point, nominal (nlegs, 3) on the host
     in the BODY frame or None = zero), update() compiles it on the same stream, and footholds() counts and chooses the
-    reachable targets per (pose, leg); foothold_edges() does the same for the targets two poses have in common."""
+    reachable targets per (pose, leg); foothold_edges() does the same for the targets two poses have in common, and
+    foothold_misses() finds, for a leg that reaches nothing, the nearest miss and the body shift that would reach it."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -520,6 +521,54 @@ class PoseSet:
                                                                   _dp(edge_b), ne, _dp(count), _dp(best), _dp(best_d2), _dp(all_legs),
                                                                   _stream(self.workspace)))
         return count, best, best_d2, all_legs
+
+    def foothold_misses(self, tx, ty, tz, margin, count=None, miss=None, m2=None, shift=None, near=None, want_shift=True):
+        """lrm_foothold_misses_posed_dev: for every (pose, leg) that count does not skip, the target closest to being
+        reachable.  Candidates are the targets inside the leg's bounding sphere widened by margin (mm, >= 0 or +inf);
+        among the unreachable ones, miss[l, p] = the target whose distance_global vector is the shortest (-1 if none),
+        m2[l, p] = its squared length (+inf if none), shift[:, l, p] = the vector -- translating the body by it at fixed
+        orientation puts the target on the workspace boundary (nan if none) -- and near[l, p] = the number of unreachable
+        candidates.  count: int32 [nlegs, nposes] or None; wherever count > 0 the entry is skipped and gets the empty
+        answer: pass footholds()'s count so that only footless legs cost anything.
+        -> (miss int32, m2 float32, each [nlegs, nposes]; shift float32 [3, nlegs, nposes] or None with
+        want_shift=False; near int32 [nlegs, nposes]).  One launch behind the cloud's bounding boxes; it only launches,
+        so update -> footholds -> foothold_misses can be captured in a graph after one warm call on the largest cloud.
+        reach_dist on (miss, p, l) returns mask 0 and exactly the shift bits."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        if self.fh_workspace is None:
+            raise ValueError("PoseSet: built without footholds=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        margin = float(margin)
+        if not margin >= 0.0:
+            raise ValueError("margin: >= 0 or +inf")
+        shape, n = (self.nlegs, self.nposes), self.nlegs * self.nposes
+        if miss is None:
+            miss = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if m2 is None:
+            m2 = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if shift is None and want_shift:
+            shift = torch.empty((3,) + shape, dtype=torch.float32, device=self.device)
+        if near is None:
+            near = torch.empty(shape, dtype=torch.int32, device=self.device)
+        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
+        _check_out(miss, self.workspace, torch.int32, n, "per-leg misses")
+        _check_out(m2, self.workspace, torch.float32, n, "per-leg squared distances")
+        _check_out(near, self.workspace, torch.int32, n, "per-leg miss counts")
+        sx = sy = sz = None
+        if want_shift:
+            _check_out(shift, self.workspace, torch.float32, 3 * n, "per-leg shift vectors")
+            sv = shift.view(-1)
+            sx, sy, sz = sv[:n], sv[n:2 * n], sv[2 * n:3 * n]
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_foothold_misses_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
+                                                                   _dp(self.fh_workspace), self.nposes, self.nlegs, margin,
+                                                                   _dp(count), _dp(miss), _dp(m2), _dp(sx), _dp(sy), _dp(sz),
+                                                                   _dp(near), _stream(self.workspace)))
+        return miss, m2, shift if want_shift else None, near
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
