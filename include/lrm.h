@@ -551,6 +551,58 @@ int lrm_foothold_misses_posed_cpu(const float* targets_aos, size_t nt, const flo
                                   const LrmLegDimensions* legs, size_t nlegs, float margin,
                                   const int32_t* count_in /* host, may be NULL */, int32_t* miss_out, float* miss_m2_out,
                                   float* shift_x, float* shift_y, float* shift_z, int32_t* near_out, double* ms);
+/* Per-TARGET foothold SUPPORT: for every terrain point and leg, how many of the candidate body poses can put that foot
+ * there, and which pose does it best -- the foothold queries above with the roles swapped (a contact-first planner, a
+ * terrain-usability map).  Pose table, leg table, `workspace` and `fh_workspace` are those of lrm_footholds_posed_dev
+ * (no new table, no new compile step).  One optional input, pose_live (uint8, nposes, device for _dev and host for _cpu,
+ * may be NULL): pose p is live when pose_live is NULL or pose_live[p] != 0; a dead pose contributes nothing.
+ * Triple (t, p, l) is REACHING iff pose p is live and reachability_global(t - body[p], legs[l], quats[p]): the strict
+ * test on the pose record, whatever lrm_set_mode says, without a gravity gate -- exactly lrm_footholds_posed_dev's rule.
+ * Every float is float32 without contraction, device and host identical.  Outputs with nlegs * nt entries at
+ * [l*nt + t], all written:
+ *   count_out      the number of reaching poses;
+ *   best_pose_out  the reaching pose with the smallest lrm_footholds_posed_dev d2 of that triple,
+ *                  d2 = (t - (body[p] + nominal_w[p,l]))^2 -- the same bits -- ties to the smaller pose index; -1 when
+ *                  count is 0;
+ *   best_d2_out    (may be NULL) that d2, +inf when count is 0;
+ * and legs_mask_out[t] (may be NULL, nt bytes): bit l set iff count_out[l*nt + t] > 0 (LRM_MAX_LEGS is 8).
+ * Consequences: with pose_live NULL the sum over t of count_out[l, t] equals the sum over p of
+ * lrm_footholds_posed_dev's count[l, p]; count_out[l, t] > 0 iff t occurs in some list of leg l of
+ * lrm_foothold_lists_posed_dev; for p* = best_pose_out[l, t] the list of (p*, l) contains t with exactly best_d2_out's
+ * bits; lrm_ik_posed_dev on (t, p*, l) reports a mask-1 status: LRM_IK_REACHED, or LRM_IK_MODEL_GAP at the few boundary
+ * points where the joint model does not follow the circle model (see the IK section), never LRM_IK_NONE / NEAREST /
+ * FAR_GAP; with pose_live = all_legs_out of lrm_footholds_posed_dev only positionable bodies count.
+ * A nan or infinite target reaches nothing.  A pose with a nan body or a non-unit quaternion is handled as in
+ * lrm_footholds_posed_dev: its sphere excludes nothing and it is tested against every target.
+ * Checked first, in lrm_footholds_posed_dev's order: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX or
+ * more than 2^32 - 1 records give LRM_EINVAL; then nt == 0 is a no-op; NULL count_out, best_pose_out or
+ * support_workspace give LRM_EINVAL; nposes == 0 writes 0 / -1 / +inf / 0 everywhere (no table is read).
+ * support_workspace: lrm_foothold_support_workspace_bytes(nposes, nlegs, nt) bytes of device memory, 16-byte aligned,
+ * owned by the caller for the duration of the call; every call rewrites it, no initialisation is needed, and a
+ * workspace sized for larger nposes / nt serves smaller ones.  It holds the per-(target, leg) accumulators, one cull
+ * sphere per (pose, leg) and one bounding box per 64 poses.
+ * Threading and streams: UNLIKE the pair kernels above, lrm_foothold_support_posed_dev does not use the per-device
+ * tile-box buffer -- every wave boxes its own 64 targets -- so it does not inherit their rules about one host thread
+ * and one cloud at a time: calls with different support workspaces may run concurrently from several threads and
+ * streams.  The call allocates nothing and never synchronises with the host; it is three launches on `stream` and can be
+ * captured in a graph from its first call.  The pose range is cut into S slices whose partial answers meet through
+ * integer atomic add and 64-bit atomic min, both order-independent: the outputs are bit-deterministic.  The box culls
+ * keep every reaching triple: they carry an absolute slack of 2^-21 (max|body| + max|centre| + r) for the different
+ * roundings of (t - body) - centre and of body + centre (csrc/lrm_foothold_support.hip).
+ * lrm_foothold_support_posed_cpu: AoS float3 targets, host tables and a host pose_live, a serial loop over every
+ * (target, leg, pose) with the strict test and no culling: the reference the GPU tests compare with bit for bit;
+ * *ms = the loop's time. */
+size_t lrm_foothold_support_workspace_bytes(size_t nposes, size_t nlegs, size_t nt);
+int lrm_foothold_support_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                                   const void* workspace, const void* fh_workspace, size_t nposes, size_t nlegs,
+                                   const uint8_t* pose_live /* device, nposes, may be NULL */,
+                                   void* support_workspace /* device, caller-owned, 16-byte aligned */,
+                                   int32_t* count_out, int32_t* best_pose_out, float* best_d2_out /* may be NULL */,
+                                   uint8_t* legs_mask_out /* may be NULL, nt */, void* stream);
+int lrm_foothold_support_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                                   const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
+                                   const uint8_t* pose_live /* host, may be NULL */, int32_t* count_out,
+                                   int32_t* best_pose_out, float* best_d2_out, uint8_t* legs_mask_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a
@@ -749,6 +801,12 @@ int lrm_dbg_tol_queue_counts(uint64_t* n_points, uint64_t* n_queued, uint64_t* n
  * (before its allocation slack).  A workgroup has 256 threads; a grid of b workgroups strides by 256 b points per round.
  * tests/test_grid_cpu.py checks lrm_tol_prepare's invariant with it, tests/test_gpu_shapes.py aims at the grids' transitions. */
 int lrm_dbg_tol_grid(size_t n, uint64_t out[6]);
+/* The launch shape of lrm_foothold_support_posed_dev for nt targets and nposes poses, from the function the launch itself
+ * calls (host only, no device needed; a function of nt and nposes alone): out[0] poses per pose chunk (one bounding box
+ * each), out[1] the slices S the pose range is cut into per 64-target chunk, out[2] the most poses one slice walks (slice s
+ * takes the pose chunks c with c % S == s), out[3] workgroups of the traversal (4 waves each, one (target chunk, slice)
+ * per wave).  tests/test_gpu_foothold_support.py takes its boundaries from it. */
+int lrm_dbg_foothold_support_grid(size_t nt, size_t nposes, uint64_t out[4]);
 /* 1 if (leg, quat) is eligible for LRM_MODE_TOL, else 0 */
 int lrm_dbg_tol_ok(const LrmLegDimensions* leg, const float* quat);
 /* The per-leg bounding sphere the pair kernels use to skip batches of footholds:

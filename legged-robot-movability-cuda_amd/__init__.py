@@ -14,7 +14,8 @@ from ._capi import (  # noqa: F401
     footholds_posed_cpu, dbg_pose_footholds_compile_host, POSE_FOOTHOLD_BYTES, foothold_lists_posed_cpu,
     foothold_edges_posed_cpu,
     foothold_misses_posed_cpu,
+    foothold_support_posed_cpu, dbg_foothold_support_grid,
 )
 from . import device  # noqa: F401
-from .device import PoseSet, ik, fk, foothold_offsets, foothold_edges_layout  # noqa: F401
+from .device import PoseSet, ik, fk, foothold_offsets, foothold_edges_layout, foothold_support_layout  # noqa: F401
 from . import shard  # noqa: F401

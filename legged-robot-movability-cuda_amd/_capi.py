@@ -130,6 +130,9 @@ def load():
         "lrm_foothold_edges_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp],
         "lrm_foothold_misses_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, fp, vp, vp, vp, vp, vp, vp, vp, vp],
         "lrm_foothold_misses_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, fp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_foothold_support_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_foothold_support_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_dbg_foothold_support_grid": [sz, sz, vp],
     }
     for name, argtypes in sig.items():
         try:
@@ -170,6 +173,9 @@ def load():
     L.lrm_posed_ik_workspace_bytes.restype = sz
     L.lrm_posed_footholds_workspace_bytes.argtypes = [sz, sz]
     L.lrm_posed_footholds_workspace_bytes.restype = sz
+    if hasattr(L, "lrm_foothold_support_workspace_bytes"):  # missing in an older library variant of an A/B run
+        L.lrm_foothold_support_workspace_bytes.argtypes = [sz, sz, sz]
+        L.lrm_foothold_support_workspace_bytes.restype = sz
     _lib = L
     return L
 
@@ -561,6 +567,40 @@ def foothold_misses_posed_cpu(targets, quats, body, legs, margin, count_in=None,
                                                _ptr(shift[0]) if want_shift else None, _ptr(shift[1]) if want_shift else None,
                                                _ptr(shift[2]) if want_shift else None, _ptr(near), C.addressof(ms)))
     return miss, m2, shift, near, ms.value
+
+
+def foothold_support_posed_cpu(targets, quats, body, legs, nominal=None, pose_live=None, want_d2=True, want_mask=True):
+    """lrm_foothold_support_posed_cpu: per (leg, target) the number of live poses p (pose_live uint8[nposes] or None = all)
+    with reachability_global(t - body[p], legs[leg], quats[p]), the reaching pose with the smallest footholds_posed_cpu d2
+    of that triple (ties: the smaller pose; -1 if none), that d2 (+inf if none), and per target the bit mask of the legs
+    with a reaching pose.  Serial host loop over every (target, leg, pose), no culling; want_* False pass NULL.
+    -> (count int32[nlegs, nt], best_pose int32[nlegs, nt], best_d2 float32[nlegs, nt] or None, legs_mask uint8[nt] or
+    None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    if pose_live is not None:
+        pose_live = np.ascontiguousarray(pose_live, np.uint8).reshape(-1)
+        if len(pose_live) != len(quats):
+            raise ValueError("pose_live: one byte per pose")
+    shape = (len(legs), len(targets))
+    count, best = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    best_d2 = np.zeros(shape, np.float32) if want_d2 else None
+    mask = np.zeros(len(targets), np.uint8) if want_mask else None
+    ms = C.c_double(0)
+    check(load().lrm_foothold_support_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), len(legs),
+                                                _ptr(nom), _ptr(pose_live), _ptr(count), _ptr(best), _ptr(best_d2), _ptr(mask),
+                                                C.addressof(ms)))
+    return count, best, best_d2, mask, ms.value
+
+
+def dbg_foothold_support_grid(nt, nposes):
+    """lrm_dbg_foothold_support_grid: the launch shape of the per-target support call for nt targets and nposes poses --
+    dict with the poses per pose chunk, the slices of the pose range per 64-target chunk, the most poses one slice walks
+    (slice s takes the pose chunks c with c % slices == s) and the workgroups of the traversal.  Host only."""
+    out = np.zeros(4, np.uint64)
+    check(load().lrm_dbg_foothold_support_grid(int(nt), int(nposes), _ptr(out)))
+    return {"pose_chunk": int(out[0]), "slices": int(out[1]), "poses_per_slice": int(out[2]), "blocks": int(out[3])}
 
 
 def apply_rbdl_equiv(xyz, leg):

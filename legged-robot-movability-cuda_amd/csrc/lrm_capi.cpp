@@ -1748,6 +1748,82 @@ int lrm_foothold_misses_posed_cpu(const float* targets, size_t nt, const float* 
     return LRM_OK;
 }
 
+// ---- per-target foothold support: which poses reach each target, per leg (lrm_foothold_support.hip) -----------
+size_t lrm_foothold_support_workspace_bytes(size_t nposes, size_t nlegs, size_t nt) { return lrm_foothold_support_bytes(nposes, nlegs, nt); }
+
+int lrm_dbg_foothold_support_grid(size_t nt, size_t nposes, uint64_t out[4]) {
+    if (!out) return fail(LRM_EINVAL, "null argument");
+    lrm_foothold_support_grid(nt, nposes, out);
+    return LRM_OK;
+}
+
+int lrm_foothold_support_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                                   const void* fh_workspace, size_t nposes, size_t nlegs, const uint8_t* pose_live,
+                                   void* support_workspace, int32_t* count_out, int32_t* best_pose_out, float* best_d2_out,
+                                   uint8_t* legs_mask_out, void* stream) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (nt == 0) return LRM_OK;
+    if (!count_out || !best_pose_out || !support_workspace || !tx || !ty || !tz) return fail(LRM_EINVAL, "null argument");
+    if (nposes && (!workspace || !fh_workspace)) return fail(LRM_EINVAL, "null argument"); // without poses no record is ever read
+    if (((uintptr_t)workspace | (uintptr_t)fh_workspace | (uintptr_t)support_workspace) & 15)
+        return fail(LRM_EINVAL, "foothold support: the workspaces must be 16-byte aligned");
+    HIP_TRY(lrm_launch_foothold_support(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, pose_live, support_workspace, count_out,
+                                        best_pose_out, best_d2_out, legs_mask_out, (hipStream_t)stream),
+            "foothold support launch");
+    return LRM_OK;
+}
+
+int lrm_foothold_support_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                   const LrmLegDimensions* legs, size_t nlegs, const float* nominal, const uint8_t* pose_live,
+                                   int32_t* count_out, int32_t* best_pose_out, float* best_d2_out, uint8_t* legs_mask_out, double* ms) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (!legs) return fail(LRM_EINVAL, "null argument");
+    if (nt == 0) return LRM_OK;
+    if (!count_out || !best_pose_out || !targets || (nposes && !quats)) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
+    if (nposes) {
+        host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+        host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
+    }
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t t = 0; t < nt; t++) {
+        const LrmVec3 tg{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
+        uint8_t mask = 0;
+        for (size_t l = 0; l < nlegs; l++) {
+            int32_t count = 0;
+            uint64_t best = kLrmFootholdNone;
+            for (size_t p = 0; p < nposes; p++) { // every pose: no sphere and no box is consulted
+                if (pose_live && !pose_live[p]) continue;
+                const LrmPoseRecord& R = recs[p * nlegs + l];
+                const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+                const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
+                const LrmVec3 rel{tg.x - b.x, tg.y - b.y, tg.z - b.z};
+                if (!lrm_reach_global(L, &R.head.lists[0][0], rel)) continue;
+                count++;
+                const uint64_t key = lrm_foothold_key(lrm_foothold_d2(tg, b, ent[p * nlegs + l].nominal_w), (uint32_t)p);
+                if (key < best) best = key;
+            }
+            const size_t o = l * nt + t;
+            count_out[o] = count;
+            best_pose_out[o] = count ? (int32_t)(uint32_t)best : -1;
+            if (best_d2_out) {
+                const uint32_t hi = (uint32_t)(best >> 32);
+                float d2;
+                std::memcpy(&d2, &hi, sizeof d2);
+                best_d2_out[o] = count ? d2 : INFINITY;
+            }
+            if (count) mask |= (uint8_t)(1u << l);
+        }
+        if (legs_mask_out) legs_mask_out[t] = mask;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
 namespace {
 int any_in_shape_impl(int shape, const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,
                       const float* ty, const float* tz, size_t nt, float radius, float plus_z, float minus_z,

@@ -101,6 +101,18 @@ hipError_t lrm_launch_foothold_misses_posed(const float* tx, const float* ty, co
                                             const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, float margin,
                                             const int32_t* count_in, int32_t* miss_out, float* miss_m2_out, float* shift_x,
                                             float* shift_y, float* shift_z, int32_t* near_out, hipStream_t st);
+// lrm_foothold_support_posed_dev (lrm_foothold_support.hip): the same tables, NO tile_boxes (a wave boxes its own 64
+// targets); pose_live: device, nposes, or null; support_workspace: lrm_foothold_support_bytes(nposes, nlegs, nt) bytes,
+// 16-byte aligned, rewritten by every call; outputs [nlegs * nt] at l * nt + t and legs_mask_out[nt]; best_d2_out and
+// legs_mask_out may be null.  nposes == 0: the empty answers, no record is read.  Three launches on `st`.
+size_t lrm_foothold_support_bytes(size_t nposes, size_t nlegs, size_t nt);
+// out[0] poses per pose chunk, [1] slices S of the pose range per target chunk, [2] the most poses one slice walks,
+// [3] workgroups of the traversal (4 waves each; wave w takes target chunk w / S and the pose chunks c with c % S == w % S)
+void lrm_foothold_support_grid(size_t nt, size_t nposes, uint64_t out[4]);
+hipError_t lrm_launch_foothold_support(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                       const void* fh_records, size_t nposes, size_t nlegs, const uint8_t* pose_live,
+                                       void* support_workspace, int32_t* count_out, int32_t* best_pose_out, float* best_d2_out,
+                                       uint8_t* legs_mask_out, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

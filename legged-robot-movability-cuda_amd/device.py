@@ -257,6 +257,24 @@ def foothold_edges_layout(nedges, nlegs, device, edge_a, edge_b, which="a"):
     return pose, leg
 
 
+def foothold_support_layout(nt, nlegs, device, best_pose):
+    """(target_idx int32, pose_idx int32, leg_idx uint8, valid bool) of the [l*nt + t] order of PoseSet.foothold_support:
+    entry l*nt + t is (target t, pose best_pose[l, t], leg l), so that
+    ps.ik(tx, ty, tz, pose_idx, leg_idx, target_idx=target_idx) solves every target under its best pose in one launch.
+    Where best_pose is -1 (no pose reaches), valid is False, pose_idx is 0 and target_idx is -1, which ik() answers with
+    status 0 and nan angles.  Only tensor operations: no host synchronisation."""
+    torch = _torch()
+    bp = best_pose.reshape(-1)
+    if not (bp.dtype == torch.int32 and bp.numel() == nt * nlegs):
+        raise ValueError("best_pose: an int32 tensor of nlegs * nt pose indices")
+    bp = bp.to(device)
+    valid = bp >= 0
+    target = torch.arange(nt, dtype=torch.int32, device=device).repeat(nlegs)
+    target = torch.where(valid, target, torch.full_like(target, -1))
+    leg = torch.arange(nlegs, dtype=torch.uint8, device=device).repeat_interleave(nt)
+    return target, bp.clamp(min=0), leg, valid
+
+
 def positionability(bx, by, bz, tx, ty, tz, legs, quats, reference_culls=0, active=None, out=None):
     """lrm_positionability_dev: the orientation sweep of robot_full_struct on device-resident clouds and masks.
     reference_culls: 0 none, 2 the per-orientation cylinder culls.  -> (accepted uint8[nb] on the device, kernel ms)"""
@@ -338,7 +356,8 @@ class PoseSet:
     foothold table as well (32 bytes per (pose, leg): bounding sphere and nominal point, nominal (nlegs, 3) on the host
     in the BODY frame or None = zero), update() compiles it on the same stream, and footholds() counts and chooses the
     reachable targets per (pose, leg); foothold_edges() does the same for the targets two poses have in common, and
-    foothold_misses() finds, for a leg that reaches nothing, the nearest miss and the body shift that would reach it."""
+    foothold_misses() finds, for a leg that reaches nothing, the nearest miss and the body shift that would reach it;
+    foothold_support() turns the question round: per target and leg, how many poses reach it and which does it best."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -362,6 +381,7 @@ class PoseSet:
             self.fh_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         elif nominal is not None:
             raise ValueError("PoseSet: nominal without footholds=True")
+        self.support_workspace = None  # foothold_support(): grows with the largest cloud seen
         self.nposes = 0
 
     @property
@@ -569,6 +589,51 @@ class PoseSet:
                                                                    _dp(count), _dp(miss), _dp(m2), _dp(sx), _dp(sy), _dp(sz),
                                                                    _dp(near), _stream(self.workspace)))
         return miss, m2, shift if want_shift else None, near
+
+    def foothold_support(self, tx, ty, tz, pose_live=None, count=None, best_pose=None, best_d2=None, legs_mask=None):
+        """lrm_foothold_support_posed_dev: the per-TARGET view of footholds().  count[l, t] = the live poses under which leg l
+        reaches target t (reachability_global on target - body[p]; pose_live: uint8 [nposes] on the device, 0 = the pose
+        does not count, None = every pose), best_pose[l, t] = the reaching pose whose nominal point of leg l lies nearest
+        the target (footholds()'s d2 of that triple, ties to the smaller pose; -1 if none), best_d2[l, t] = that d2
+        (+inf if none), legs_mask[t] = bit l set iff count[l, t] > 0.
+        -> (count int32, best_pose int32, best_d2 float32, each [nlegs, nt]; legs_mask uint8[nt]).  pose_live and given
+        outputs must be contiguous.  The set keeps a support workspace sized for the largest cloud seen: a first or larger
+        call allocates it (through torch), every other call only launches, so update -> footholds ->
+        foothold_support(pose_live=all_legs) can be captured in a graph after one call on a cloud of the largest size.
+        It does not use the pair kernels' box buffer.  foothold_support_layout() turns best_pose into ik()'s indices."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        if self.fh_workspace is None:
+            raise ValueError("PoseSet: built without footholds=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        _check_out(pose_live, self.workspace, torch.uint8, self.nposes, "pose_live")
+        shape, n = (self.nlegs, nt), self.nlegs * nt
+        if count is None:
+            count = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if best_pose is None:
+            best_pose = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if best_d2 is None:
+            best_d2 = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if legs_mask is None:
+            legs_mask = torch.empty(nt, dtype=torch.uint8, device=self.device)
+        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
+        _check_out(best_pose, self.workspace, torch.int32, n, "per-leg best poses")
+        _check_out(best_d2, self.workspace, torch.float32, n, "per-leg squared distances")
+        _check_out(legs_mask, self.workspace, torch.uint8, nt, "per-target leg masks")
+        if nt == 0:
+            return count, best_pose, best_d2, legs_mask
+        need = _capi.load().lrm_foothold_support_workspace_bytes(self.nposes_max, self.nlegs, nt)
+        if self.support_workspace is None or self.support_workspace.numel() < need:
+            self.support_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_foothold_support_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
+                                                                    _dp(self.fh_workspace), self.nposes, self.nlegs, _dp(pose_live),
+                                                                    _dp(self.support_workspace), _dp(count), _dp(best_pose),
+                                                                    _dp(best_d2), _dp(legs_mask), _stream(self.workspace)))
+        return count, best_pose, best_d2, legs_mask
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
