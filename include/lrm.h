@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_foothold_misses_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_foothold_misses_posed_dev, lrm_body_clearance_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -603,6 +603,65 @@ int lrm_foothold_support_posed_cpu(const float* targets_aos, size_t nt, const fl
                                    const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
                                    const uint8_t* pose_live /* host, may be NULL */, int32_t* count_out,
                                    int32_t* best_pose_out, float* best_d2_out, uint8_t* legs_mask_out, double* ms);
+/* BODY CLEARANCE per pose: does the trunk of a posed body fit over the terrain, how far must it rise if not, and how much
+ * ground clearance is left if so.  The reference removes colliding bodies per orientation before it counts anything
+ * (eliminateFarAndColliding / eliminateBodyColliding, several_leg.cu:504-630, with in_cylinder of collision.cu.h:12-23 on
+ * bodies and targets taken into the orientation's frame); this is that predicate for bodies that each have their own
+ * quaternion and position.  Pose table, leg table, `workspace` and `fh_workspace` are those of lrm_footholds_posed_dev (no
+ * new table, no new compile step).  Four float32 scalars describe the body volume in the BODY frame, centred on the body
+ * origin, the body's z its axis: radius, plus_z (top), minus_z (the belly plane) and floor_z (how far below the body
+ * terrain is still looked at).  One optional input, live_in (uint8, nposes, device for _dev and host for _cpu, may be
+ * NULL): a pose with live_in[p] == 0 is skipped -- it costs nothing and gets the empty answer with free = 0.
+ * For pose p and target t, float32 without contraction, device and host identical:
+ *   q = t - body[p]          one subtraction per component, as everywhere in the posed calls;
+ *   v = qtInvRotate(quats[p], q)   the strict rotation reachability_global applies, bit for bit: lrm_qrot on the pose
+ *                            record's inv_rot (the same in every record of the pose; leg 0's is read);
+ *   column(t) = in_cylinder(radius, plus_z, floor_z, 0, v):  sqrtf(vx*vx + vy*vy + 0) < radius, vz < plus_z, vz > floor_z
+ *               (norm3df restated as sqrtf of the sum in that order);
+ *   hit(t)    = in_cylinder(radius, plus_z, minus_z, 0, v);
+ *   height(t) = vz - minus_z, one subtraction; -0 is stored and compared as +0.
+ * Every output has nposes entries, all written:
+ *   hits_out    (int32) the number of targets with hit;
+ *   top_out     (int32) the column target with the largest height, ties to the smaller index; -1 when the column is empty;
+ *   height_out  (float, may be NULL) that height, -inf when the column is empty.  A value > 0 is the lift along the body's z
+ *               that takes the highest intruder down to the belly plane (stated for exact arithmetic); a value <= 0 means
+ *               the belly clears the terrain under it by that much;
+ *   free_out    (uint8, may be NULL) 1 iff the pose is live and hits == 0.
+ * Consequences: for a live pose hits > 0 iff height > 0 iff free == 0 (a hit is a column target, floor_z <= minus_z, and
+ * x - y > 0 iff x > y); with floor_z == minus_z column and hit coincide; with the identity quaternion free_out is the
+ * negation of lrm_any_in_cylinder_dev on the same cylinder and centres wherever that byte is defined; a nan or infinite
+ * target is in no column; free_out is directly usable as pose_live of lrm_foothold_support_posed_dev, and all_legs_out of
+ * lrm_footholds_posed_dev as live_in, so that update -> footholds -> body_clearance(live_in = all_legs) ->
+ * foothold_support(pose_live = free) -> ik only counts bodies that stand AND fit.
+ * For a pose with a nan body or a non-unit quaternion qtInvRotate is not a rotation: its cull excludes nothing and it is
+ * tested against every target, as in lrm_footholds_posed_dev.  Such a pose is recognised by leg 0's foothold entry
+ * having cull_r2 = +inf.
+ * Checked first, in lrm_footholds_posed_dev's order: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX or
+ * more than 2^32 - 1 records, then the scalars give LRM_EINVAL: any of them nan, radius < 0, minus_z or floor_z not finite,
+ * floor_z > minus_z, plus_z <= minus_z (radius and plus_z may be +inf).  Then nposes == 0 is a no-op; NULL hits_out or
+ * top_out gives LRM_EINVAL; nt == 0 gives 0 / -1 / -inf everywhere, free_out = 1 for every live pose and 0 for a skipped one.
+ * Threading and streams: lrm_body_clearance_posed_dev is one of the pair kernels, with lrm_footholds_posed_dev's rules:
+ * the per-device tile-box buffer from 4096 targets on, one host thread at a time, no two pair launches on different
+ * clouds concurrently on one device; the first call for a larger cloud than the buffer holds allocates, every later call
+ * (and every call below 4096 targets) only launches, so compile -> footholds -> body_clearance can be captured in a graph
+ * after one call on a cloud of the largest size.  One launch behind the boxes' own; no atomics.  The box culls keep every
+ * column target: the cull sphere about body[p] bounds the cylinder (radius, plus_z, floor_z) with slack for |quat|^2 within
+ * 1e-5 of 1; its centre is the very point q is formed about, so unlike the foothold spheres it needs no absolute slack
+ * far from the origin (csrc/lrm_body_clearance.hip); an infinite radius or plus_z gives the sphere that excludes nothing.
+ * lrm_body_clearance_posed_cpu: AoS float3 targets, host tables and a host live_in, a serial loop over every (pose,
+ * target) with the same test function and no culling: the reference the GPU tests compare with bit for bit; *ms = the
+ * loop's time. */
+int lrm_body_clearance_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                                 const void* workspace, const void* fh_workspace, size_t nposes, size_t nlegs,
+                                 float radius, float plus_z, float minus_z, float floor_z,
+                                 const uint8_t* live_in /* device, nposes, may be NULL */,
+                                 int32_t* hits_out, int32_t* top_out, float* height_out /* may be NULL */,
+                                 uint8_t* free_out /* may be NULL */, void* stream);
+int lrm_body_clearance_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                                 const LrmLegDimensions* legs, size_t nlegs,
+                                 float radius, float plus_z, float minus_z, float floor_z,
+                                 const uint8_t* live_in /* host, may be NULL */, int32_t* hits_out, int32_t* top_out,
+                                 float* height_out, uint8_t* free_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

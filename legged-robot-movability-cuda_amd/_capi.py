@@ -133,12 +133,14 @@ def load():
         "lrm_foothold_support_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp],
         "lrm_foothold_support_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp],
         "lrm_dbg_foothold_support_grid": [sz, sz, vp],
+        "lrm_body_clearance_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp],
+        "lrm_body_clearance_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith("lrm_foothold_")):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
@@ -601,6 +603,31 @@ def dbg_foothold_support_grid(nt, nposes):
     out = np.zeros(4, np.uint64)
     check(load().lrm_dbg_foothold_support_grid(int(nt), int(nposes), _ptr(out)))
     return {"pose_chunk": int(out[0]), "slices": int(out[1]), "poses_per_slice": int(out[2]), "blocks": int(out[3])}
+
+
+def body_clearance_posed_cpu(targets, quats, body, legs, radius, plus_z, minus_z, floor_z=None, live_in=None, want_height=True,
+                              want_free=True):
+    """lrm_body_clearance_posed_cpu: per pose not skipped by live_in (uint8[nposes] or None; 0 skips) the number of targets
+    inside the body cylinder (radius, plus_z, minus_z) in the BODY frame, the target of the column (radius, plus_z, floor_z;
+    floor_z None = minus_z) that stands highest over the belly plane (-1 if none), that height vz - minus_z (-inf if none),
+    and whether the pose is live and free of hits.  Serial host loop over every (pose, target), no culling; want_* False
+    pass NULL.  -> (hits int32[nposes], top int32[nposes], height float32[nposes] or None, free uint8[nposes] or None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != len(quats):
+            raise ValueError("live_in: one byte per pose")
+    n = len(quats)
+    hits, top = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    height = np.zeros(n, np.float32) if want_height else None
+    free = np.zeros(n, np.uint8) if want_free else None
+    ms = C.c_double(0)
+    check(load().lrm_body_clearance_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), n, _ptr(legs), len(legs),
+                                              float(radius), float(plus_z), float(minus_z),
+                                              float(minus_z if floor_z is None else floor_z), _ptr(live_in), _ptr(hits), _ptr(top),
+                                              _ptr(height), _ptr(free), C.addressof(ms)))
+    return hits, top, height, free, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

@@ -20,6 +20,7 @@
 #include "lrm_compile_head.h"
 #include "lrm_footholds.h"
 #include "lrm_footholds_posed.h"
+#include "lrm_body_clearance.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -1818,6 +1819,84 @@ int lrm_foothold_support_posed_cpu(const float* targets, size_t nt, const float*
             if (count) mask |= (uint8_t)(1u << l);
         }
         if (legs_mask_out) legs_mask_out[t] = mask;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+// ---- body clearance per pose: terrain hits, worst point and lift (lrm_body_clearance.hip) -----------
+namespace {
+// lrm_footholds_posed_dev's range checks, then the four scalars', before any early return
+int body_clearance_args(size_t nt, size_t nposes, size_t nlegs, float radius, float plus_z, float minus_z, float floor_z) {
+    const int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (radius != radius || plus_z != plus_z || minus_z != minus_z || floor_z != floor_z)
+        return fail(LRM_EINVAL, "body clearance: nan scalar");
+    if (radius < 0.f) return fail(LRM_EINVAL, "body clearance: radius must be >= 0 or +inf");
+    if (!(std::fabs(minus_z) < INFINITY) || !(std::fabs(floor_z) < INFINITY))
+        return fail(LRM_EINVAL, "body clearance: minus_z and floor_z must be finite");
+    if (floor_z > minus_z) return fail(LRM_EINVAL, "body clearance: floor_z must not lie above minus_z");
+    if (plus_z <= minus_z) return fail(LRM_EINVAL, "body clearance: plus_z must lie above minus_z");
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_body_clearance_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                                 const void* fh_workspace, size_t nposes, size_t nlegs, float radius, float plus_z, float minus_z,
+                                 float floor_z, const uint8_t* live_in, int32_t* hits_out, int32_t* top_out, float* height_out,
+                                 uint8_t* free_out, void* stream) {
+    int rc = body_clearance_args(nt, nposes, nlegs, radius, plus_z, minus_z, floor_z);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!workspace || !fh_workspace || !hits_out || !top_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
+        return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_body_clearance_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, radius, plus_z, minus_z, floor_z,
+                                            live_in, hits_out, top_out, height_out, free_out, (hipStream_t)stream),
+            "posed body clearance launch");
+    return LRM_OK;
+}
+
+int lrm_body_clearance_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                 const LrmLegDimensions* legs, size_t nlegs, float radius, float plus_z, float minus_z, float floor_z,
+                                 const uint8_t* live_in, int32_t* hits_out, int32_t* top_out, float* height_out, uint8_t* free_out,
+                                 double* ms) {
+    int rc = body_clearance_args(nt, nposes, nlegs, radius, plus_z, minus_z, floor_z);
+    if (rc != LRM_OK) return rc;
+    if (!legs) return fail(LRM_EINVAL, "null argument");
+    if (nposes == 0) return LRM_OK;
+    if (!quats || !hits_out || !top_out || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes); // leg 0's record of every pose: inv_rot and body_pos are the same in all of them
+    host_pose_records(quats, body, nposes, legs, 1, recs.data());
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t p = 0; p < nposes; p++) {
+        const LrmPoseRecord& R = recs[p];
+        const bool live = !(live_in && !live_in[p]);
+        int32_t hits = 0;
+        uint64_t best = kLrmClearanceNone;
+        if (live) { // a skipped pose keeps the empty answer
+            for (size_t t = 0; t < nt; t++) { // every target: no sphere and no box is consulted
+                const LrmVec3 q{targets[3 * t] - R.body_pos[0], targets[3 * t + 1] - R.body_pos[1], targets[3 * t + 2] - R.body_pos[2]};
+                float h;
+                const unsigned in = lrm_clearance_test(R.head.inv_rot, q, radius, plus_z, minus_z, floor_z, &h);
+                if (in & LRM_CLEARANCE_HIT) hits++;
+                if (in & LRM_CLEARANCE_COLUMN) {
+                    const uint64_t key = lrm_clearance_key(h, (uint32_t)t);
+                    if (key < best) best = key;
+                }
+            }
+        }
+        const bool have = best != kLrmClearanceNone;
+        hits_out[p] = hits;
+        top_out[p] = have ? (int32_t)(uint32_t)best : -1;
+        if (height_out) height_out[p] = have ? lrm_clearance_key_height(best) : -INFINITY;
+        if (free_out) free_out[p] = live && hits == 0;
     }
     const auto t1 = std::chrono::high_resolution_clock::now();
     if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;

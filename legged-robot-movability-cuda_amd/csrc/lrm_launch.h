@@ -113,6 +113,13 @@ hipError_t lrm_launch_foothold_support(const float* tx, const float* ty, const f
                                        const void* fh_records, size_t nposes, size_t nlegs, const uint8_t* pose_live,
                                        void* support_workspace, int32_t* count_out, int32_t* best_pose_out, float* best_d2_out,
                                        uint8_t* legs_mask_out, hipStream_t st);
+// lrm_body_clearance_posed_dev (lrm_body_clearance.hip): the same tables and tile_boxes; the four scalars are checked by the
+// C ABI (floor_z <= minus_z < plus_z, radius >= 0, radius and plus_z may be +inf); live_in: device, nposes, or null;
+// outputs [nposes]; height_out and free_out may be null.  Reads leg 0's record and foothold entry of every live pose.
+hipError_t lrm_launch_body_clearance_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
+                                           const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, float radius,
+                                           float plus_z, float minus_z, float floor_z, const uint8_t* live_in, int32_t* hits_out,
+                                           int32_t* top_out, float* height_out, uint8_t* free_out, hipStream_t st);
 hipError_t lrm_launch_any_in_shape(int shape, const float* cx, const float* cy, const float* cz, size_t nc,
                                    const float* tx, const float* ty, const float* tz, size_t nt, float radius,
                                    float plus_z, float minus_z, float* tile_boxes /* workspace or null */,

@@ -357,7 +357,8 @@ class PoseSet:
     in the BODY frame or None = zero), update() compiles it on the same stream, and footholds() counts and chooses the
     reachable targets per (pose, leg); foothold_edges() does the same for the targets two poses have in common, and
     foothold_misses() finds, for a leg that reaches nothing, the nearest miss and the body shift that would reach it;
-    foothold_support() turns the question round: per target and leg, how many poses reach it and which does it best."""
+    foothold_support() turns the question round: per target and leg, how many poses reach it and which does it best;
+    body_clearance() asks whether the trunk itself fits: terrain inside the body cylinder, the worst point and the lift."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -634,6 +635,50 @@ class PoseSet:
                                                                     _dp(self.support_workspace), _dp(count), _dp(best_pose),
                                                                     _dp(best_d2), _dp(legs_mask), _stream(self.workspace)))
         return count, best_pose, best_d2, legs_mask
+
+    def body_clearance(self, tx, ty, tz, radius, plus_z, minus_z, floor_z=None, live_in=None, hits=None, top=None, height=None,
+                       free=None):
+        """lrm_body_clearance_posed_dev: does the trunk of every pose fit over the terrain.  The body volume is a cylinder
+        in the BODY frame about the body's z axis through the body origin: radius, top plus_z, belly plane minus_z (mm).
+        hits[p] = the targets inside it; top[p] = the target of the column under the body (the same cylinder down to
+        floor_z; None = minus_z) that stands highest over the belly plane (-1 if none); height[p] = its vz - minus_z
+        (-inf if none): > 0 is the lift along the body's z that clears the pose, <= 0 the ground clearance left;
+        free[p] = 1 iff the pose is live and hits[p] == 0.  live_in: uint8 [nposes] on the device, 0 = the pose is skipped
+        (0, -1, -inf, free 0), None = every pose; pass footholds()'s all_legs.
+        -> (hits int32, top int32, height float32, free uint8, each [nposes]).  live_in and given outputs must be
+        contiguous.  free is directly foothold_support()'s pose_live.  One launch behind the cloud's bounding boxes; it
+        only launches, so update -> footholds -> body_clearance can be captured in a graph after one warm call on the
+        largest cloud."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        if self.fh_workspace is None:
+            raise ValueError("PoseSet: built without footholds=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        radius, plus_z, minus_z = float(radius), float(plus_z), float(minus_z)
+        floor_z = minus_z if floor_z is None else float(floor_z)
+        _check_out(live_in, self.workspace, torch.uint8, self.nposes, "live_in")
+        n = self.nposes
+        if hits is None:
+            hits = torch.empty(n, dtype=torch.int32, device=self.device)
+        if top is None:
+            top = torch.empty(n, dtype=torch.int32, device=self.device)
+        if height is None:
+            height = torch.empty(n, dtype=torch.float32, device=self.device)
+        if free is None:
+            free = torch.empty(n, dtype=torch.uint8, device=self.device)
+        _check_out(hits, self.workspace, torch.int32, n, "per-pose hit counts")
+        _check_out(top, self.workspace, torch.int32, n, "per-pose top targets")
+        _check_out(height, self.workspace, torch.float32, n, "per-pose heights")
+        _check_out(free, self.workspace, torch.uint8, n, "per-pose free bytes")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_body_clearance_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
+                                                                  _dp(self.fh_workspace), self.nposes, self.nlegs, radius, plus_z,
+                                                                  minus_z, floor_z, _dp(live_in), _dp(hits), _dp(top), _dp(height),
+                                                                  _dp(free), _stream(self.workspace)))
+        return hits, top, height, free
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
