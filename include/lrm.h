@@ -662,6 +662,84 @@ int lrm_body_clearance_posed_cpu(const float* targets_aos, size_t nt, const floa
                                  float radius, float plus_z, float minus_z, float floor_z,
                                  const uint8_t* live_in /* host, may be NULL */, int32_t* hits_out, int32_t* top_out,
                                  float* height_out, uint8_t* free_out, double* ms);
+/* LEG LINK CLEARANCE per (pose, leg): do the leg's own links fit over the terrain under given joint angles.
+ * lrm_footholds_posed_dev says whether a foot reaches the ground and lrm_body_clearance_posed_dev whether the trunk fits;
+ * lrm_ik_posed_dev then returns angles that put the foot on the chosen foothold -- and the knee may stand inside a rock.  The
+ * reference has no such query (it culls colliding bodies, never legs).  Pose table, leg table, `workspace` and
+ * `ik_workspace` are those of lrm_ik_posed_dev (no new table, no new compile step).  coxa / femur / tibia: device float32,
+ * nlegs * nposes angles at [l*nposes + p] -- lrm_ik_posed_dev's outputs under the [l*nposes + p] layout of the foothold calls.
+ * radius[3] (host): the radii of the capsules about link 0 (coxa), 1 (femur) and 2 (tibia), each >= 0 and finite; a link with
+ * radius 0 is not tested at all.  margin >= 0, finite: how far outside a link a target still counts as near.  tip_clear >= 0,
+ * finite: how far short of the foot the tibia link stops (without it every stance would collide with its own foothold).
+ * live_in (uint8, nposes, device for _dev and host for _cpu, may be NULL): a pose with live_in[p] == 0 is skipped.
+ * Everything is float32 without contraction, only + - * /, comparisons, the correctly rounded square root and the sincos
+ * of the IK: device and host give the same bits (csrc/lrm_leg_clearance.h is the one source of both).
+ * Joints of (p, l) under angles (c, f, t), RELATIVE to body[p], with sc, cc = sincos(c), sf, cf = sincos(f),
+ * sa, ca = sincos(f + t), C, F, T the leg's link lengths, T' = T - tip_clear (0 unless T' > 0), from_coxa the last step of
+ * lrm_fk_posed_dev's chain:
+ *   J0 = from_coxa(0, 0, 0)  the coxa joint;      J1 = from_coxa(cc C, sc C, 0)  the femur joint;
+ *   J2 = from_coxa(cc h2, sc h2, F sf), h2 = C + F cf  the knee;
+ *   J3 = from_coxa(cc h3, sc h3, F sf + T' sa), h3 = C + (F cf + T' ca)  -- with tip_clear == 0 the bits of lrm_fk_posed_dev's tip
+ *   (before the body is added).  Link k runs from A = Jk to B = Jk+1.
+ * A leg is VALID iff all twelve coordinates are finite; nan angles (LRM_IK_NONE) and angles outside the sincos range
+ * (|x| >= 120) give nan joints.  An invalid leg is SKIPPED: it gets hits 0, links 0, worst -1, pen -inf and DOES NOT BLOCK
+ * free_out -- pass live_in = all_legs & body-free so that such legs do not occur in live poses.
+ * Target t against link k, q = t - body[p] (one subtraction per component):
+ *   ab = B - A; ap = q - A; den = (ab.x ab.x + ab.y ab.y) + ab.z ab.z; num = (ap.x ab.x + ap.y ab.y) + ap.z ab.z;
+ *   s = den > 0 ? num / den : 0, then clamped: s = !(s > 0) ? 0 : (s > 1 ? 1 : s);
+ *   e = ap - s ab (one multiply, one subtract per component); d = sqrt((e.x e.x + e.y e.y) + e.z e.z);
+ *   hit_k = d < radius[k]; near_k = d < radius[k] + margin (the sum formed once per call); pen_k = radius[k] - d (-0 stored
+ *   and compared as +0).  A nan d is neither near nor hit.  pen(t) = the largest pen_k over the links with near_k.
+ * Outputs with nlegs * nposes entries at [l*nposes + p], all written:
+ *   hits_out   (int32) the number of targets with some hit_k;
+ *   links_out  (uint8) bit k set iff link k has a hit;
+ *   worst_out  (int32) the near target with the largest pen, ties to the smaller index; -1 when no target is near;
+ *   pen_out    (float, may be NULL) that pen, -inf when none: > 0 is the depth of the deepest intrusion, <= 0 the
+ *              clearance left within the margin;
+ * and free_out[p] (uint8, nposes, may be NULL): 1 iff the pose is live and every leg has hits == 0.  A pose with
+ * live_in[p] == 0 gets 0 / 0 / -1 / -inf for every leg and free 0.
+ * Consequences: pen > 0 iff hits > 0 iff links != 0; with margin == 0 near and hit coincide, so worst is a hit or -1; a nan
+ * or infinite target is near nothing; free_out is directly usable as pose_live of lrm_foothold_support_posed_dev:
+ * update -> footholds -> body_clearance(live_in = all_legs) -> foothold_support(pose_live = free) -> ik -> leg_clearance.
+ * Checked first, in lrm_body_clearance_posed_dev's order: nt > INT32_MAX, nlegs outside 1..LRM_MAX_LEGS, nposes > INT32_MAX
+ * or more than 2^32 - 1 records, then the scalars give LRM_EINVAL: any of them nan, a radius, margin or tip_clear negative or
+ * not finite (NULL radius too).  Then nposes == 0 is a no-op; NULL hits_out, links_out, worst_out or angle array gives
+ * LRM_EINVAL; nt == 0 gives 0 / 0 / -1 / -inf everywhere, free_out = 1 for every live pose and 0 for a skipped one.
+ * Threading and streams: lrm_leg_clearance_posed_dev is one of the pair kernels, with lrm_footholds_posed_dev's rules: the
+ * per-device tile-box buffer from 4096 targets on, one host thread at a time, no two pair launches on different clouds
+ * concurrently on one device; the first call for a larger cloud than the buffer holds allocates, every later call (and every
+ * call below 4096 targets) only launches, so update -> footholds -> ik -> leg_clearance can be captured in a graph after one
+ * call on a cloud of the largest size.  One launch behind the boxes' own; no atomics.  The box cull keeps every near target:
+ * a tile or chunk box is skipped only if on some axis it lies further than (max radius + margin) * 1.0001 + 1e-5 * (the leg
+ * box's extent) from the box of the leg's four computed joints, both taken about body[p], so it needs no absolute slack far
+ * from the origin and no special case for non-unit quaternions (csrc/lrm_leg_clearance.hip); a margin so large that the
+ * inflation overflows culls nothing.
+ * lrm_leg_clearance_posed_cpu: AoS float3 targets, host tables, host angles_aos (nlegs * nposes triples {coxa, femur, tibia}
+ * at [l*nposes + p]: lrm_ik_posed_cpu's output in that layout) and a host live_in; a serial loop over every (pose, leg,
+ * target) with the same functions and no culling: the reference the GPU tests compare with bit for bit; *ms = the loop's time.
+ * lrm_leg_joints_posed_dev / _cpu: the joints themselves, for inspection and drawing: joints_out holds nlegs * nposes * 12
+ * floats, entry [l*nposes + p] = J0..J3 as x, y, z with body[p] added (one addition per component).  A nan coordinate is stored
+ * as the canonical quiet nan 0x7fc00000 (sign and payload of a propagated nan differ between host and device).  Checked first: nlegs >
+ * LRM_MAX_LEGS, nposes > INT32_MAX or more than 2^32 - 1 records, tip_clear nan, negative or not finite give LRM_EINVAL; then
+ * nposes == 0 or nlegs == 0 is a no-op; NULL arguments give LRM_EINVAL.  The _dev form is one launch, allocates nothing and
+ * uses no shared buffer. */
+int lrm_leg_clearance_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                                const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs,
+                                const float* coxa, const float* femur, const float* tibia /* device, nlegs*nposes at [l*nposes + p] */,
+                                const float radius[3] /* host */, float margin, float tip_clear,
+                                const uint8_t* live_in /* device, nposes, may be NULL */,
+                                int32_t* hits_out, uint8_t* links_out, int32_t* worst_out, float* pen_out /* may be NULL */,
+                                uint8_t* free_out /* nposes, may be NULL */, void* stream);
+int lrm_leg_clearance_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                                const LrmLegDimensions* legs, size_t nlegs, const float* angles_aos,
+                                const float radius[3], float margin, float tip_clear,
+                                const uint8_t* live_in /* host, may be NULL */, int32_t* hits_out, uint8_t* links_out,
+                                int32_t* worst_out, float* pen_out, uint8_t* free_out, double* ms);
+int lrm_leg_joints_posed_dev(const float* coxa, const float* femur, const float* tibia, size_t nposes, size_t nlegs,
+                             const void* workspace, const void* ik_workspace, float tip_clear,
+                             float* joints_out /* device, nlegs*nposes*12 */, void* stream);
+int lrm_leg_joints_posed_cpu(const float* angles_aos, const float* quats, const float* body, size_t nposes,
+                             const LrmLegDimensions* legs, size_t nlegs, float tip_clear, float* joints_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

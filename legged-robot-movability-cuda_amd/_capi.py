@@ -135,12 +135,16 @@ def load():
         "lrm_dbg_foothold_support_grid": [sz, sz, vp],
         "lrm_body_clearance_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp],
         "lrm_body_clearance_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp],
+        "lrm_leg_clearance_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_leg_clearance_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_leg_joints_posed_dev": [vp, vp, vp, sz, sz, vp, vp, fp, vp, vp],
+        "lrm_leg_joints_posed_cpu": [vp, vp, vp, sz, vp, sz, fp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
@@ -628,6 +632,55 @@ def body_clearance_posed_cpu(targets, quats, body, legs, radius, plus_z, minus_z
                                               float(minus_z if floor_z is None else floor_z), _ptr(live_in), _ptr(hits), _ptr(top),
                                               _ptr(height), _ptr(free), C.addressof(ms)))
     return hits, top, height, free, ms.value
+
+
+def _leg_angles(angles, nlegs, nposes):
+    angles = _f32(angles)
+    if angles.size != nlegs * nposes * 3:
+        raise ValueError("angles: one (coxa, femur, tibia) triple per (leg, pose), at [l*nposes + p]")
+    return angles.reshape(nlegs * nposes, 3)
+
+
+def leg_clearance_posed_cpu(targets, quats, body, legs, angles, radius, margin=0.0, tip_clear=0.0, live_in=None, want_pen=True,
+                            want_free=True):
+    """lrm_leg_clearance_posed_cpu: per (leg, pose) not skipped by live_in (uint8[nposes] or None; 0 skips) the number of
+    targets inside one of the leg's three links (capsules of radius[k] about coxa, femur, tibia under angles[l*nposes + p] =
+    (coxa, femur, tibia), the tibia ending tip_clear short of the foot), the bit mask of the links hit, the target within
+    margin of a link that stands deepest (-1 if none), its pen = radius - distance (-inf if none), and per pose whether it is
+    live and no leg is hit.  angles: float32 [nlegs*nposes, 3], apply_ik_posed_cpu's output under the [l*nposes + p] layout.
+    Serial host loop over every (pose, leg, target), no culling; want_* False pass NULL.
+    -> (hits int32[nlegs, nposes], links uint8[nlegs, nposes], worst int32[nlegs, nposes], pen float32[nlegs, nposes] or None,
+    free uint8[nposes] or None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    n, nl = len(quats), len(legs)
+    angles = _leg_angles(angles, nl, n)
+    radius = _f32(radius, (3,))
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != n:
+            raise ValueError("live_in: one byte per pose")
+    hits, links, worst = np.zeros((nl, n), np.int32), np.zeros((nl, n), np.uint8), np.zeros((nl, n), np.int32)
+    pen = np.zeros((nl, n), np.float32) if want_pen else None
+    free = np.zeros(n, np.uint8) if want_free else None
+    ms = C.c_double(0)
+    check(load().lrm_leg_clearance_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), n, _ptr(legs), nl, _ptr(angles),
+                                             _ptr(radius), float(margin), float(tip_clear), _ptr(live_in), _ptr(hits), _ptr(links),
+                                             _ptr(worst), _ptr(pen), _ptr(free), C.addressof(ms)))
+    return hits, links, worst, pen, free, ms.value
+
+
+def leg_joints_posed_cpu(angles, quats, body, legs, tip_clear=0.0):
+    """lrm_leg_joints_posed_cpu: the four joints (coxa joint, femur joint, knee, tibia end tip_clear short of the foot) of
+    every (leg, pose) under angles[l*nposes + p], body[p] added -> (joints float32[nlegs, nposes, 4, 3], ms)"""
+    quats, body, legs = _posed_tables(quats, body, legs)
+    n, nl = len(quats), len(legs)
+    angles = _leg_angles(angles, nl, n)
+    out = np.zeros((nl, n, 4, 3), np.float32)
+    ms = C.c_double(0)
+    check(load().lrm_leg_joints_posed_cpu(_ptr(angles), _ptr(quats), _ptr(body), n, _ptr(legs), nl, float(tip_clear), _ptr(out),
+                                          C.addressof(ms)))
+    return out, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

@@ -21,6 +21,7 @@
 #include "lrm_footholds.h"
 #include "lrm_footholds_posed.h"
 #include "lrm_body_clearance.h"
+#include "lrm_leg_clearance.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -1903,8 +1904,152 @@ int lrm_body_clearance_posed_cpu(const float* targets, size_t nt, const float* q
     return LRM_OK;
 }
 
+// ---- leg link clearance per (pose, leg): terrain hits on the leg's links (lrm_leg_clearance.hip) -----------
 namespace {
-int any_in_shape_impl(int shape, const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,
+int leg_scalar_ok(float v, const char* what) { // >= 0 and finite
+    if (v != v) return fail(LRM_EINVAL, "leg clearance: nan scalar");
+    if (v < 0.f || !(v < INFINITY)) return fail(LRM_EINVAL, what);
+    return LRM_OK;
+}
+// lrm_footholds_posed_dev's range checks, then the scalars', before any early return
+int leg_clearance_args(size_t nt, size_t nposes, size_t nlegs, const float* radius, float margin, float tip_clear) {
+    int rc = footholds_posed_args(nt, nposes, nlegs);
+    if (rc != LRM_OK) return rc;
+    if (!radius) return fail(LRM_EINVAL, "null argument");
+    for (int k = 0; k < 3; k++)
+        if (radius[k] != radius[k]) return fail(LRM_EINVAL, "leg clearance: nan scalar");
+    if (margin != margin || tip_clear != tip_clear) return fail(LRM_EINVAL, "leg clearance: nan scalar");
+    for (int k = 0; k < 3 && rc == LRM_OK; k++) rc = leg_scalar_ok(radius[k], "leg clearance: every radius must be >= 0 and finite");
+    if (rc == LRM_OK) rc = leg_scalar_ok(margin, "leg clearance: margin must be >= 0 and finite");
+    if (rc == LRM_OK) rc = leg_scalar_ok(tip_clear, "leg clearance: tip_clear must be >= 0 and finite");
+    return rc;
+}
+} // namespace
+
+int lrm_leg_clearance_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const void* workspace,
+                                const void* ik_workspace, size_t nposes, size_t nlegs, const float* coxa, const float* femur,
+                                const float* tibia, const float radius[3], float margin, float tip_clear, const uint8_t* live_in,
+                                int32_t* hits_out, uint8_t* links_out, int32_t* worst_out, float* pen_out, uint8_t* free_out,
+                                void* stream) {
+    int rc = leg_clearance_args(nt, nposes, nlegs, radius, margin, tip_clear);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!workspace || !ik_workspace || !hits_out || !links_out || !worst_out || !coxa || !femur || !tibia || (nt && (!tx || !ty || !tz)))
+        return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
+    float* boxes = nullptr;
+    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
+        rc = tile_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_leg_clearance_posed(tx, ty, tz, nt, workspace, ik_workspace, nposes, nlegs, boxes, coxa, femur, tibia, radius, margin,
+                                           tip_clear, live_in, hits_out, links_out, worst_out, pen_out, free_out, (hipStream_t)stream),
+            "posed leg clearance launch");
+    return LRM_OK;
+}
+
+int lrm_leg_clearance_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                const LrmLegDimensions* legs, size_t nlegs, const float* angles, const float radius[3], float margin,
+                                float tip_clear, const uint8_t* live_in, int32_t* hits_out, uint8_t* links_out, int32_t* worst_out,
+                                float* pen_out, uint8_t* free_out, double* ms) {
+    int rc = leg_clearance_args(nt, nposes, nlegs, radius, margin, tip_clear);
+    if (rc != LRM_OK) return rc;
+    if (!legs) return fail(LRM_EINVAL, "null argument");
+    if (nposes == 0) return LRM_OK;
+    if (!quats || !angles || !hits_out || !links_out || !worst_out || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const float reach[3] = {radius[0] + margin, radius[1] + margin, radius[2] + margin};
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t p = 0; p < nposes; p++) {
+        const bool live = !(live_in && !live_in[p]);
+        bool pose_free = live;
+        for (size_t l = 0; l < nlegs; l++) {
+            const LrmPoseRecord& R = recs[p * nlegs + l];
+            const size_t o = l * nposes + p;
+            int32_t hits = 0;
+            unsigned links = 0u;
+            uint64_t best = kLrmLegClearanceNone;
+            LrmVec3 J[4];
+            if (live) lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
+                                     angles[3 * o + 2], tip_clear, J);
+            if (live && lrm_leg_joints_finite(J)) { // a skipped pose and a skipped leg keep the empty answer
+                LrmLegLinks S;
+                lrm_leg_links(J, &S);
+                for (size_t t = 0; t < nt; t++) { // every target: no box is consulted
+                    const LrmVec3 q{targets[3 * t] - R.body_pos[0], targets[3 * t + 1] - R.body_pos[1], targets[3 * t + 2] - R.body_pos[2]};
+                    float pen = 0.f;
+                    const unsigned in = lrm_leg_clearance_test(S, radius, reach, q, &pen);
+                    if (in & 7u) hits++;
+                    links |= in & 7u;
+                    if (in & LRM_LEG_NEAR) {
+                        const uint64_t key = lrm_leg_clearance_key(pen, (uint32_t)t);
+                        if (key < best) best = key;
+                    }
+                }
+            }
+            const bool have = best != kLrmLegClearanceNone;
+            hits_out[o] = hits;
+            links_out[o] = (uint8_t)links;
+            worst_out[o] = have ? (int32_t)(uint32_t)best : -1;
+            if (pen_out) pen_out[o] = have ? lrm_leg_clearance_key_pen(best) : -INFINITY;
+            pose_free = pose_free && hits == 0;
+        }
+        if (free_out) free_out[p] = pose_free;
+    }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+int lrm_leg_joints_posed_dev(const float* coxa, const float* femur, const float* tibia, size_t nposes, size_t nlegs,
+                             const void* workspace, const void* ik_workspace, float tip_clear, float* joints_out, void* stream) {
+    int rc = ik_posed_tables(nposes, nlegs);
+    if (rc == LRM_OK) rc = leg_scalar_ok(tip_clear, "leg clearance: tip_clear must be >= 0 and finite");
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!workspace || !ik_workspace || !coxa || !femur || !tibia || !joints_out) return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
+    HIP_TRY(lrm_launch_leg_joints_posed(coxa, femur, tibia, nposes, nlegs, workspace, ik_workspace, tip_clear, joints_out,
+                                        (hipStream_t)stream),
+            "posed leg joints launch");
+    return LRM_OK;
+}
+
+int lrm_leg_joints_posed_cpu(const float* angles, const float* quats, const float* body, size_t nposes, const LrmLegDimensions* legs,
+                             size_t nlegs, float tip_clear, float* joints_out, double* ms) {
+    int rc = posed_args(nposes, nlegs, legs);
+    if (rc == LRM_OK) rc = leg_scalar_ok(tip_clear, "leg clearance: tip_clear must be >= 0 and finite");
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0 || nlegs == 0) return LRM_OK;
+    if (!angles || !quats || !joints_out) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    for (size_t p = 0; p < nposes; p++)
+        for (size_t l = 0; l < nlegs; l++) {
+            const LrmPoseRecord& R = recs[p * nlegs + l];
+            const size_t o = l * nposes + p;
+            LrmVec3 J[4];
+            lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
+                           angles[3 * o + 2], tip_clear, J);
+            for (int k = 0; k < 4; k++) {
+                joints_out[o * 12 + 3 * k] = lrm_leg_joint_out(J[k].x, R.body_pos[0]);
+                joints_out[o * 12 + 3 * k + 1] = lrm_leg_joint_out(J[k].y, R.body_pos[1]);
+                joints_out[o * 12 + 3 * k + 2] = lrm_leg_joint_out(J[k].z, R.body_pos[2]);
+            }
+        }
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
+    return LRM_OK;
+}
+
+namespace {
+int any_in_shape_impl(int shape,const float* cx, const float* cy, const float* cz, size_t nc, const float* tx,
                       const float* ty, const float* tz, size_t nt, float radius, float plus_z, float minus_z,
                       bool boxes_ready, uint8_t* out, void* stream) {
     if (!out || (nc && (!cx || !cy || !cz)) || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");

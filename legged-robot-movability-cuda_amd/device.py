@@ -358,7 +358,9 @@ class PoseSet:
     reachable targets per (pose, leg); foothold_edges() does the same for the targets two poses have in common, and
     foothold_misses() finds, for a leg that reaches nothing, the nearest miss and the body shift that would reach it;
     foothold_support() turns the question round: per target and leg, how many poses reach it and which does it best;
-    body_clearance() asks whether the trunk itself fits: terrain inside the body cylinder, the worst point and the lift."""
+    body_clearance() asks whether the trunk itself fits: terrain inside the body cylinder, the worst point and the lift;
+    leg_clearance() (with ik=True) asks the same of the legs under ik()'s angles: terrain inside the coxa, femur and tibia
+    links, and leg_joints() returns the joints it tests."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -679,6 +681,79 @@ class PoseSet:
                                                                   minus_z, floor_z, _dp(live_in), _dp(hits), _dp(top), _dp(height),
                                                                   _dp(free), _stream(self.workspace)))
         return hits, top, height, free
+
+    def _check_angles(self, angles):
+        torch = _torch()
+        if self.ik_workspace is None:
+            raise ValueError("PoseSet: built without ik=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        n = self.nlegs * self.nposes
+        if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
+                and tuple(angles.shape) == (3, n) and angles.is_contiguous()):
+            raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {n}) tensor on {self.workspace.device}")
+        return n
+
+    def leg_clearance(self, tx, ty, tz, angles, radius, margin=0.0, tip_clear=0.0, live_in=None, hits=None, links=None, worst=None,
+                      pen=None, free=None):
+        """lrm_leg_clearance_posed_dev: do the legs themselves fit over the terrain under the given joint angles.
+        angles: ik()'s (3, nlegs*nposes) tensor under footholds_layout (entry l*nposes + p).  radius: three capsule radii
+        (coxa, femur, tibia link; 0 = the link is not tested), margin: how far outside a link a target still counts as
+        near, tip_clear: how far short of the foot the tibia link stops (mm).  hits[l, p] = the targets inside a link;
+        links[l, p] = bit k set iff link k is hit; worst[l, p] = the near target that stands deepest (-1 if none);
+        pen[l, p] = its radius - distance (-inf if none): > 0 an intrusion, <= 0 the clearance left within the margin;
+        free[p] = 1 iff the pose is live and no leg is hit.  A leg with nan angles is skipped (all empty) and does not block
+        free.  live_in: uint8 [nposes] on the device, 0 = the pose is skipped (0, 0, -1, -inf, free 0), None = every pose.
+        -> (hits int32, links uint8, worst int32, pen float32, each [nlegs, nposes]; free uint8[nposes]).  live_in and
+        given outputs must be contiguous.  One launch behind the cloud's bounding boxes; it only launches, so
+        update -> footholds -> ik -> leg_clearance can be captured in a graph after one warm call on the largest cloud."""
+        torch = _torch()
+        nt = _check_f32(tx, ty, tz)
+        n = self._check_angles(angles)
+        if nt and tx.device != self.workspace.device:
+            raise ValueError("targets and poses must live on one device")
+        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if len(radius) != 3:
+            raise ValueError("radius: three values (coxa, femur, tibia link)")
+        _check_out(live_in, self.workspace, torch.uint8, self.nposes, "live_in")
+        shape = (self.nlegs, self.nposes)
+        if hits is None:
+            hits = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if links is None:
+            links = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if worst is None:
+            worst = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if pen is None:
+            pen = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if free is None:
+            free = torch.empty(self.nposes, dtype=torch.uint8, device=self.device)
+        _check_out(hits, self.workspace, torch.int32, n, "per-leg hit counts")
+        _check_out(links, self.workspace, torch.uint8, n, "per-leg link masks")
+        _check_out(worst, self.workspace, torch.int32, n, "per-leg worst targets")
+        _check_out(pen, self.workspace, torch.float32, n, "per-leg penetrations")
+        _check_out(free, self.workspace, torch.uint8, self.nposes, "per-pose free bytes")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_leg_clearance_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
+                                                                 _dp(self.ik_workspace), self.nposes, self.nlegs, _dp(angles[0]),
+                                                                 _dp(angles[1]), _dp(angles[2]), _capi._ptr(radius), float(margin),
+                                                                 float(tip_clear), _dp(live_in), _dp(hits), _dp(links), _dp(worst),
+                                                                 _dp(pen), _dp(free), _stream(self.workspace)))
+        return hits, links, worst, pen, free
+
+    def leg_joints(self, angles, tip_clear=0.0, out=None):
+        """lrm_leg_joints_posed_dev: the four joints of every (leg, pose) under angles (ik()'s (3, nlegs*nposes) tensor under
+        footholds_layout): coxa joint, femur joint, knee and the tibia's end tip_clear short of the foot, body position
+        added -> float32 (nlegs, nposes, 4, 3).  One launch."""
+        torch = _torch()
+        n = self._check_angles(angles)
+        if out is None:
+            out = torch.empty((self.nlegs, self.nposes, 4, 3), dtype=torch.float32, device=self.device)
+        _check_out(out, self.workspace, torch.float32, 12 * n, "joints")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_leg_joints_posed_dev(_dp(angles[0]), _dp(angles[1]), _dp(angles[2]), self.nposes, self.nlegs,
+                                                              _dp(self.workspace), _dp(self.ik_workspace), float(tip_clear), _dp(out),
+                                                              _stream(self.workspace)))
+        return out
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
