@@ -30,7 +30,13 @@ LRM_HD uint64_t lrm_clearance_key(float height, uint32_t index) {
     const uint32_t u = lrm_f2u(height);
     return ((uint64_t)((u >> 31) ? u : 0x7fffffffu - u) << 32) | index;
 }
-LRM_HD float lrm_clearance_key_height(uint64_t key) {
+// What a key holds: the column target's index (< nt) and height, or -1 and -inf for kLrmClearanceNone.
+struct LrmClearanceTop {
+    int32_t index;
+    float height;
+};
+LRM_HD LrmClearanceTop lrm_clearance_key_decode(uint64_t key) {
     const uint32_t h = (uint32_t)(key >> 32);
-    return lrm_u2f((h >> 31) ? h : 0x7fffffffu - h);
+    const bool have = key != kLrmClearanceNone;
+    return LrmClearanceTop{have ? (int32_t)(uint32_t)key : -1, have ? lrm_u2f((h >> 31) ? h : 0x7fffffffu - h) : -__builtin_inff()};
 }

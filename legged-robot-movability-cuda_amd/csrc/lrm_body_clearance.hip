@@ -42,6 +42,7 @@
 #include "lrm_point.h"
 #include "lrm_footholds_posed.h"
 #include "lrm_body_clearance.h"
+#include "lrm_target_walk.h"
 
 namespace {
 
@@ -50,14 +51,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kTargetTile = 1024; // the tiles of tile_aabb_kernel (lrm_kernels.hip)
 constexpr unsigned kMaxGrid = 16384; // 65 536 poses in flight; a wave strides over the rest (footholds_posed_kernel's cap)
 
-// the same helpers as lrm_footholds_posed.hip's
-__device__ __forceinline__ float box_dist2(const float* bb, float x, float y, float z) {
-    const float ex = fmaxf(fmaxf(bb[0] - x, x - bb[3]), 0.f);
-    const float ey = fmaxf(fmaxf(bb[1] - y, y - bb[4]), 0.f);
-    const float ez = fmaxf(fmaxf(bb[2] - z, z - bb[5]), 0.f);
-    return ex * ex + ey * ey + ez * ez;
-}
-__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
 
 // Minimum waves per SIMD asked of the compiler.  The kernel needs 32 VGPRs, so 8 waves fit a SIMD whatever is asked; what
 // the bound changes is the SGPR budget: asking for 8 leaves 78 SGPRs and spills 16 to VGPR lanes, asking for 4 gives 95
@@ -104,7 +97,7 @@ __global__ __launch_bounds__(kBlock, LRM_BODY_CLEARANCE_MIN_WAVES) void body_cle
         for (size_t tw0 = 0; tw0 < ntiles; tw0 += 64) {
             const size_t tl = tw0 + lane; // lane = tile
             unsigned long long near =
-                __ballot(tl < ntiles && (!boxes || !(box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f > thr)));
+                __ballot(tl < ntiles && (!boxes || !(lrm_box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f > thr)));
             while (near != 0ull) {
                 const int tb = __builtin_ctzll(near);
                 near &= near - 1ull;
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(kBlock, LRM_BODY_CLEARANCE_MIN_WAVES) void body_cle
                 // lane = chunk of this tile (empty chunks carry an inverted box: infinitely far, unless thr is +inf)
                 uint32_t cnear;
                 if (boxes) {
-                    cnear = (uint32_t)__ballot(lane < 16 && !(box_dist2(boxes + (ntiles + tile * 16 + (lane & 15)) * 6, body.x, body.y, body.z) *
+                    cnear = (uint32_t)__ballot(lane < 16 && !(lrm_box_dist2(boxes + (ntiles + tile * 16 + (lane & 15)) * 6, body.x, body.y, body.z) *
                                                                   0.999f > thr)) & 0xffffu;
                 } else {
                     const size_t left = nt - t0; // > 0: tile < ntiles
@@ -147,21 +140,17 @@ __global__ __launch_bounds__(kBlock, LRM_BODY_CLEARANCE_MIN_WAVES) void body_cle
                     unsigned in = lrm_clearance_test(m, LrmVec3{t.x - body.x, t.y - body.y, t.z - body.z}, radius, plus_z, minus_z, floor_z, &h);
                     if (!ok) in = 0u;
                     hits += (uint32_t)__builtin_popcountll(__ballot((in & LRM_CLEARANCE_HIT) != 0u));
-                    if (in & LRM_CLEARANCE_COLUMN) key = min_u64(key, lrm_clearance_key(h, ti));
+                    if (in & LRM_CLEARANCE_COLUMN) key = lrm_min_u64(key, lrm_clearance_key(h, ti));
                 }
             }
         }
 
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t lo = __shfl_xor((uint32_t)key, off), hi = __shfl_xor((uint32_t)(key >> 32), off);
-            key = min_u64(key, ((uint64_t)hi << 32) | lo);
-        }
+        key = lrm_wave_min_u64(key);
         if (lane == 0) {
-            const bool have = key != kLrmClearanceNone;
+            const LrmClearanceTop top = lrm_clearance_key_decode(key);
             hits_out[p] = (int32_t)hits;
-            top_out[p] = have ? (int32_t)(uint32_t)key : -1; // < nt when have
-            if (height_out) height_out[p] = have ? lrm_clearance_key_height(key) : -inf;
+            top_out[p] = top.index;
+            if (height_out) height_out[p] = top.height;
             if (free_out) free_out[p] = hits == 0u;
         }
     }
@@ -173,15 +162,10 @@ hipError_t lrm_launch_body_clearance_posed(const float* tx, const float* ty, con
                                            const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, float radius,
                                            float plus_z, float minus_z, float floor_z, const uint8_t* live_in, int32_t* hits_out,
                                            int32_t* top_out, float* height_out, uint8_t* free_out, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    size_t g = (nposes + kWaves - 1) / kWaves;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const float* boxes = nt ? tile_boxes : nullptr;
-    hipLaunchKernelGGL(body_clearance_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
-                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, radius, plus_z, minus_z, floor_z,
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nposes, kWaves, kMaxGrid, st);
+    if (w.err != hipSuccess) return w.err;
+    hipLaunchKernelGGL(body_clearance_posed_kernel, w.grid, dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, w.boxes, radius, plus_z, minus_z, floor_z,
                        live_in, hits_out, top_out, height_out, free_out);
     return hipGetLastError();
 }

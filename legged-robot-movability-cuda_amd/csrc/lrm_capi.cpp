@@ -1383,6 +1383,19 @@ int footholds_posed_args(size_t nt, size_t nposes, size_t nlegs) {
     if (nposes * nlegs > (size_t)UINT32_MAX) return fail(LRM_EINVAL, "posed queries: more than 2^32 - 1 (pose, leg) records");
     return LRM_OK;
 }
+// the box workspace of a cloud whose kernel culls: null below 4096 targets, where every tile is read (reach_any_impl's threshold)
+int cull_boxes(size_t nt, float** boxes) {
+    *boxes = nullptr;
+    return nt >= 4096 ? tile_boxes(nt, boxes) : LRM_OK;
+}
+// the wall time of the scope it lives in, to *ms (may be null) when the scope ends
+struct ScopeMs {
+    double* ms;
+    std::chrono::high_resolution_clock::time_point t0 = std::chrono::high_resolution_clock::now();
+    ~ScopeMs() {
+        if (ms) *ms = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count() * 1000.0;
+    }
+};
 void host_pose_foothold_entries(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const float* nominal,
                                 LrmPoseFootEntry* out) {
     for (size_t p = 0; p < nposes; p++)
@@ -1426,11 +1439,9 @@ int lrm_footholds_posed_dev(const float* tx, const float* ty, const float* tz, s
     if (!workspace || !fh_workspace || !count_out || !best_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
     if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
         return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
-    float* boxes = nullptr;
-    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
-        rc = tile_boxes(nt, &boxes);
-        if (rc != LRM_OK) return rc;
-    }
+    float* boxes;
+    rc = cull_boxes(nt, &boxes);
+    if (rc != LRM_OK) return rc;
     HIP_TRY(lrm_launch_footholds_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, count_out, best_out, best_d2_out,
                                        all_legs_out, (hipStream_t)stream), "posed footholds launch");
     return LRM_OK;
@@ -1448,7 +1459,7 @@ int lrm_footholds_posed_cpu(const float* targets, size_t nt, const float* quats,
     host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
     std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
     host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t p = 0; p < nposes; p++) {
         bool all = true;
         for (size_t l = 0; l < nlegs; l++) {
@@ -1467,19 +1478,13 @@ int lrm_footholds_posed_cpu(const float* targets, size_t nt, const float* quats,
             }
             const size_t o = l * nposes + p;
             count_out[o] = count;
-            best_out[o] = count ? (int32_t)(uint32_t)best : -1;
-            if (best_d2_out) {
-                const uint32_t hi = (uint32_t)(best >> 32);
-                float d2;
-                std::memcpy(&d2, &hi, sizeof d2);
-                best_d2_out[o] = count ? d2 : INFINITY;
-            }
+            const LrmFootholdChoice choice = lrm_foothold_key_decode(best, count != 0);
+            best_out[o] = choice.index;
+            if (best_d2_out) best_d2_out[o] = choice.d2;
             all = all && count > 0;
         }
         if (all_legs_out) all_legs_out[p] = all;
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -1506,11 +1511,9 @@ int lrm_foothold_lists_posed_dev(const float* tx, const float* ty, const float* 
             HIP_TRY(hipMemsetAsync(written_out, 0, nposes * nlegs * sizeof(int32_t), (hipStream_t)stream), "hipMemsetAsync written_out");
         return LRM_OK;
     }
-    float* boxes = nullptr;
-    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
-        rc = tile_boxes(nt, &boxes);
-        if (rc != LRM_OK) return rc;
-    }
+    float* boxes;
+    rc = cull_boxes(nt, &boxes);
+    if (rc != LRM_OK) return rc;
     HIP_TRY(lrm_launch_foothold_lists_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, offsets, capacity, idx_out,
                                             d2_out, written_out, (hipStream_t)stream), "posed foothold lists launch");
     return LRM_OK;
@@ -1534,7 +1537,7 @@ int lrm_foothold_lists_posed_cpu(const float* targets, size_t nt, const float* q
     std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
     host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
     const int64_t cap = capacity > (size_t)INT64_MAX ? INT64_MAX : (int64_t)capacity;
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t p = 0; p < nposes; p++) {
         for (size_t l = 0; l < nlegs; l++) {
             const LrmPoseRecord& R = recs[p * nlegs + l];
@@ -1557,8 +1560,6 @@ int lrm_foothold_lists_posed_cpu(const float* targets, size_t nt, const float* q
             if (written_out) written_out[o] = (int32_t)(n < room ? n : room);
         }
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -1584,11 +1585,9 @@ int lrm_foothold_edges_posed_dev(const float* tx, const float* ty, const float* 
     if (nposes && (!workspace || !fh_workspace)) return fail(LRM_EINVAL, "null argument"); // without poses no record is ever read
     if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
         return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
-    float* boxes = nullptr;
-    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
-        rc = tile_boxes(nt, &boxes);
-        if (rc != LRM_OK) return rc;
-    }
+    float* boxes;
+    rc = cull_boxes(nt, &boxes);
+    if (rc != LRM_OK) return rc;
     HIP_TRY(lrm_launch_foothold_edges_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, edge_a, edge_b, nedges,
                                             count_out, best_out, best_d2_out, all_legs_out, (hipStream_t)stream),
             "posed foothold edges launch");
@@ -1610,7 +1609,7 @@ int lrm_foothold_edges_posed_cpu(const float* targets, size_t nt, const float* q
         host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
         host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
     }
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t e = 0; e < nedges; e++) {
         const int64_t a = edge_a[e], b = edge_b[e];
         const bool valid = a >= 0 && b >= 0 && (uint64_t)a < nposes && (uint64_t)b < nposes;
@@ -1637,19 +1636,13 @@ int lrm_foothold_edges_posed_cpu(const float* targets, size_t nt, const float* q
             }
             const size_t o = l * nedges + e;
             count_out[o] = count;
-            best_out[o] = count ? (int32_t)(uint32_t)best : -1;
-            if (best_d2_out) {
-                const uint32_t hi = (uint32_t)(best >> 32);
-                float d2;
-                std::memcpy(&d2, &hi, sizeof d2);
-                best_d2_out[o] = count ? d2 : INFINITY;
-            }
+            const LrmFootholdChoice choice = lrm_foothold_key_decode(best, count != 0);
+            best_out[o] = choice.index;
+            if (best_d2_out) best_d2_out[o] = choice.d2;
             all = all && count > 0;
         }
         if (all_legs_out) all_legs_out[e] = all;
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -1675,11 +1668,9 @@ int lrm_foothold_misses_posed_dev(const float* tx, const float* ty, const float*
     if (!shift_x != !shift_y || !shift_x != !shift_z) return fail(LRM_EINVAL, "foothold misses: give all three shift components or none");
     if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
         return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
-    float* boxes = nullptr;
-    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
-        rc = tile_boxes(nt, &boxes);
-        if (rc != LRM_OK) return rc;
-    }
+    float* boxes;
+    rc = cull_boxes(nt, &boxes);
+    if (rc != LRM_OK) return rc;
     HIP_TRY(lrm_launch_foothold_misses_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, margin, count_in, miss_out,
                                              miss_m2_out, shift_x, shift_y, shift_z, near_out, (hipStream_t)stream),
             "posed foothold misses launch");
@@ -1700,7 +1691,7 @@ int lrm_foothold_misses_posed_cpu(const float* targets, size_t nt, const float* 
     host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
     std::vector<LrmPoseFootEntry> ent(nposes * nlegs);
     host_pose_foothold_entries(quats, nposes, legs, nlegs, nullptr, ent.data()); // the sphere does not depend on the nominal point
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t p = 0; p < nposes; p++) {
         for (size_t l = 0; l < nlegs; l++) {
             const size_t o = l * nposes + p;
@@ -1730,13 +1721,9 @@ int lrm_foothold_misses_posed_cpu(const float* targets, size_t nt, const float* 
                 }
             }
             const bool have = best != kLrmFootholdNone;
-            miss_out[o] = have ? (int32_t)(uint32_t)best : -1;
-            if (miss_m2_out) {
-                const uint32_t hi = (uint32_t)(best >> 32);
-                float m2;
-                std::memcpy(&m2, &hi, sizeof m2);
-                miss_m2_out[o] = have ? m2 : INFINITY;
-            }
+            const LrmFootholdChoice choice = lrm_foothold_key_decode(best, have);
+            miss_out[o] = choice.index;
+            if (miss_m2_out) miss_m2_out[o] = choice.d2;
             if (shift_x) {
                 shift_x[o] = best_d.x;
                 shift_y[o] = best_d.y;
@@ -1745,8 +1732,6 @@ int lrm_foothold_misses_posed_cpu(const float* targets, size_t nt, const float* 
             if (near_out) near_out[o] = near;
         }
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -1790,7 +1775,7 @@ int lrm_foothold_support_posed_cpu(const float* targets, size_t nt, const float*
         host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
         host_pose_foothold_entries(quats, nposes, legs, nlegs, nominal, ent.data());
     }
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t t = 0; t < nt; t++) {
         const LrmVec3 tg{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
         uint8_t mask = 0;
@@ -1810,19 +1795,13 @@ int lrm_foothold_support_posed_cpu(const float* targets, size_t nt, const float*
             }
             const size_t o = l * nt + t;
             count_out[o] = count;
-            best_pose_out[o] = count ? (int32_t)(uint32_t)best : -1;
-            if (best_d2_out) {
-                const uint32_t hi = (uint32_t)(best >> 32);
-                float d2;
-                std::memcpy(&d2, &hi, sizeof d2);
-                best_d2_out[o] = count ? d2 : INFINITY;
-            }
+            const LrmFootholdChoice choice = lrm_foothold_key_decode(best, count != 0);
+            best_pose_out[o] = choice.index;
+            if (best_d2_out) best_d2_out[o] = choice.d2;
             if (count) mask |= (uint8_t)(1u << l);
         }
         if (legs_mask_out) legs_mask_out[t] = mask;
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -1853,11 +1832,9 @@ int lrm_body_clearance_posed_dev(const float* tx, const float* ty, const float* 
     if (!workspace || !fh_workspace || !hits_out || !top_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
     if (((uintptr_t)workspace | (uintptr_t)fh_workspace) & 15)
         return fail(LRM_EINVAL, "posed footholds: the workspaces must be 16-byte aligned");
-    float* boxes = nullptr;
-    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
-        rc = tile_boxes(nt, &boxes);
-        if (rc != LRM_OK) return rc;
-    }
+    float* boxes;
+    rc = cull_boxes(nt, &boxes);
+    if (rc != LRM_OK) return rc;
     HIP_TRY(lrm_launch_body_clearance_posed(tx, ty, tz, nt, workspace, fh_workspace, nposes, nlegs, boxes, radius, plus_z, minus_z, floor_z,
                                             live_in, hits_out, top_out, height_out, free_out, (hipStream_t)stream),
             "posed body clearance launch");
@@ -1875,7 +1852,7 @@ int lrm_body_clearance_posed_cpu(const float* targets, size_t nt, const float* q
     if (!quats || !hits_out || !top_out || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
     std::vector<LrmPoseRecord> recs(nposes); // leg 0's record of every pose: inv_rot and body_pos are the same in all of them
     host_pose_records(quats, body, nposes, legs, 1, recs.data());
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t p = 0; p < nposes; p++) {
         const LrmPoseRecord& R = recs[p];
         const bool live = !(live_in && !live_in[p]);
@@ -1893,14 +1870,12 @@ int lrm_body_clearance_posed_cpu(const float* targets, size_t nt, const float* q
                 }
             }
         }
-        const bool have = best != kLrmClearanceNone;
+        const LrmClearanceTop top = lrm_clearance_key_decode(best);
         hits_out[p] = hits;
-        top_out[p] = have ? (int32_t)(uint32_t)best : -1;
-        if (height_out) height_out[p] = have ? lrm_clearance_key_height(best) : -INFINITY;
+        top_out[p] = top.index;
+        if (height_out) height_out[p] = top.height;
         if (free_out) free_out[p] = live && hits == 0;
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -1937,11 +1912,9 @@ int lrm_leg_clearance_posed_dev(const float* tx, const float* ty, const float* t
     if (!workspace || !ik_workspace || !hits_out || !links_out || !worst_out || !coxa || !femur || !tibia || (nt && (!tx || !ty || !tz)))
         return fail(LRM_EINVAL, "null argument");
     if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
-    float* boxes = nullptr;
-    if (nt >= 4096) { // below that every tile is read (reach_any_impl's threshold)
-        rc = tile_boxes(nt, &boxes);
-        if (rc != LRM_OK) return rc;
-    }
+    float* boxes;
+    rc = cull_boxes(nt, &boxes);
+    if (rc != LRM_OK) return rc;
     HIP_TRY(lrm_launch_leg_clearance_posed(tx, ty, tz, nt, workspace, ik_workspace, nposes, nlegs, boxes, coxa, femur, tibia, radius, margin,
                                            tip_clear, live_in, hits_out, links_out, worst_out, pen_out, free_out, (hipStream_t)stream),
             "posed leg clearance launch");
@@ -1962,7 +1935,7 @@ int lrm_leg_clearance_posed_cpu(const float* targets, size_t nt, const float* qu
     host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
     host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
     const float reach[3] = {radius[0] + margin, radius[1] + margin, radius[2] + margin};
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t p = 0; p < nposes; p++) {
         const bool live = !(live_in && !live_in[p]);
         bool pose_free = live;
@@ -1990,17 +1963,15 @@ int lrm_leg_clearance_posed_cpu(const float* targets, size_t nt, const float* qu
                     }
                 }
             }
-            const bool have = best != kLrmLegClearanceNone;
+            const LrmLegClearanceWorst worst = lrm_leg_clearance_key_decode(best);
             hits_out[o] = hits;
             links_out[o] = (uint8_t)links;
-            worst_out[o] = have ? (int32_t)(uint32_t)best : -1;
-            if (pen_out) pen_out[o] = have ? lrm_leg_clearance_key_pen(best) : -INFINITY;
+            worst_out[o] = worst.index;
+            if (pen_out) pen_out[o] = worst.pen;
             pose_free = pose_free && hits == 0;
         }
         if (free_out) free_out[p] = pose_free;
     }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 
@@ -2029,7 +2000,7 @@ int lrm_leg_joints_posed_cpu(const float* angles, const float* quats, const floa
     std::vector<LrmIkLeg> iks(nposes * nlegs);
     host_pose_records(quats, body, nposes, legs, nlegs, recs.data());
     host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const ScopeMs timer{ms};
     for (size_t p = 0; p < nposes; p++)
         for (size_t l = 0; l < nlegs; l++) {
             const LrmPoseRecord& R = recs[p * nlegs + l];
@@ -2043,8 +2014,6 @@ int lrm_leg_joints_posed_cpu(const float* angles, const float* quats, const floa
                 joints_out[o * 12 + 3 * k + 2] = lrm_leg_joint_out(J[k].z, R.body_pos[2]);
             }
         }
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    if (ms) *ms = std::chrono::duration<double>(t1 - t0).count() * 1000.0;
     return LRM_OK;
 }
 

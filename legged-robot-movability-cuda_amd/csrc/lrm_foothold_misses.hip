@@ -49,6 +49,7 @@
 #include "lrm_point.h"
 #include "lrm_footholds.h"
 #include "lrm_footholds_posed.h"
+#include "lrm_target_walk.h"
 
 namespace {
 
@@ -58,19 +59,6 @@ constexpr int kTargetTile = 1024; // the tiles of tile_aabb_kernel (lrm_kernels.
 constexpr int kQueue = 128;
 constexpr unsigned kMaxGrid = 16384; // 65 536 poses in flight; a wave strides over the rest
 
-// the same helpers as lrm_footholds_posed.hip's
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ float box_dist2(const float* bb, float x, float y, float z) {
-    const float ex = fmaxf(fmaxf(bb[0] - x, x - bb[3]), 0.f);
-    const float ey = fmaxf(fmaxf(bb[1] - y, y - bb[4]), 0.f);
-    const float ez = fmaxf(fmaxf(bb[2] - z, z - bb[5]), 0.f);
-    return ex * ex + ey * ey + ez * ez;
-}
-__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
 
 // Minimum waves per SIMD asked of the compiler (DESIGN.md 3.14 has the resource figures behind the choice).
 #ifndef LRM_FOOTHOLD_MISSES_MIN_WAVES
@@ -117,7 +105,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
         const LrmPoseRecord& R0 = lrm_fresh(recs[r0]);
         const LrmVec3 body{R0.body_pos[0], R0.body_pos[1], R0.body_pos[2]}; // the same in every record of the pose
         // stage the pose's tables: every lane is done with the previous pose's
-        wave_lds_fence();
+        lrm_wave_lds_fence();
         for (uint32_t l = 0; l < nlegs; l++)
             if ((live >> l) & 1u) // wave-uniform
                 reinterpret_cast<float*>(my_lists[l])[lane] = reinterpret_cast<const float*>(&recs[r0 + l].head.lists[0][0])[lane];
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
             my_cull[lane][2] = body.z + E.cull_center[2];
             my_cull[lane][3] = wanted ? rs * rs : -1.f;
         }
-        wave_lds_fence();
+        lrm_wave_lds_fence();
 
         int count = 0;       // survivors waiting in this wave's queue
         uint32_t near_n = 0; // lane l: leg l's misses
@@ -173,7 +161,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                 }
 #pragma unroll
                 for (int k = 0; k < LRM_MAX_LEGS; k++)
-                    if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+                    if ((uint32_t)k == l) key[k] = lrm_min_u64(key[k], kk); // l is wave-uniform: one branch taken
             }
         };
 
@@ -185,7 +173,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                 const float* tb = boxes + tl * 6;
                 for (uint32_t l = 0; l < nlegs; l++) { // wave-uniform
                     if (!((live >> l) & 1u)) continue;
-                    tnear = tnear || !(box_dist2(tb, my_cull[l][0], my_cull[l][1], my_cull[l][2]) * 0.999f > my_cull[l][3]);
+                    tnear = tnear || !(lrm_box_dist2(tb, my_cull[l][0], my_cull[l][1], my_cull[l][2]) * 0.999f > my_cull[l][3]);
                 }
             }
             unsigned long long near = __ballot(tnear);
@@ -203,7 +191,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                         const uint32_t l = l0 + (lane >> 4);
                         bool touch = false;
                         if (l < nlegs && ((live >> l) & 1u))
-                            touch = !(box_dist2(cb, my_cull[l][0], my_cull[l][1], my_cull[l][2]) * 0.999f > my_cull[l][3]);
+                            touch = !(lrm_box_dist2(cb, my_cull[l][0], my_cull[l][1], my_cull[l][2]) * 0.999f > my_cull[l][3]);
                         const unsigned long long mm = __ballot(touch);
                         cnear |= (uint32_t)((mm | (mm >> 16) | (mm >> 32) | (mm >> 48)) & 0xffffull);
                     }
@@ -252,7 +240,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                         qi[pos] = ti;
                     }
                     count += __builtin_popcountll(m);
-                    wave_lds_fence();
+                    lrm_wave_lds_fence();
                     if (count >= 64) {
                         process(64);
                         count -= 64;
@@ -260,9 +248,9 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                         float mx = 0.f, my = 0.f, mz = 0.f;
                         uint32_t mi = 0u;
                         if (lane < count) { mx = qx[64 + lane]; my = qy[64 + lane]; mz = qz[64 + lane]; mi = qi[64 + lane]; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                         if (lane < count) { qx[lane] = mx; qy[lane] = my; qz[lane] = mz; qi[lane] = mi; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                     }
                 }
             }
@@ -274,19 +262,15 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
 #pragma unroll
         for (int k = 0; k < LRM_MAX_LEGS; k++) {
             if ((uint32_t)k >= nlegs) break; // wave-uniform
-            uint64_t v = key[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
-                v = min_u64(v, ((uint64_t)hi << 32) | lo);
-            }
+            const uint64_t v = lrm_wave_min_u64(key[k]);
             if (lane == k) best = v;
         }
         if (mine) {
             const bool have = best != kLrmFootholdNone; // an eligible miss has m2 < +inf: its key is below ~0
             const uint32_t wi = (uint32_t)best;         // < nt when have
-            miss_out[o] = have ? (int32_t)wi : -1;
-            if (m2_out) m2_out[o] = have ? __uint_as_float((uint32_t)(best >> 32)) : inf;
+            const LrmFootholdChoice c = lrm_foothold_key_decode(best, have);
+            miss_out[o] = c.index;
+            if (m2_out) m2_out[o] = c.d2;
             if (near_out) near_out[o] = (int32_t)near_n;
             if (shift_x) { // wave-uniform
                 LrmVec3 d{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
@@ -310,15 +294,10 @@ hipError_t lrm_launch_foothold_misses_posed(const float* tx, const float* ty, co
                                             const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, float margin,
                                             const int32_t* count_in, int32_t* miss_out, float* miss_m2_out, float* shift_x,
                                             float* shift_y, float* shift_z, int32_t* near_out, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    size_t g = (nposes + kWaves - 1) / kWaves;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const float* boxes = nt ? tile_boxes : nullptr;
-    hipLaunchKernelGGL(foothold_misses_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
-                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, margin, count_in, miss_out,
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nposes, kWaves, kMaxGrid, st);
+    if (w.err != hipSuccess) return w.err;
+    hipLaunchKernelGGL(foothold_misses_posed_kernel, w.grid, dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, w.boxes, margin, count_in, miss_out,
                        miss_m2_out, shift_x, shift_y, shift_z, near_out);
     return hipGetLastError();
 }

@@ -55,6 +55,7 @@
 #include "lrm_point.h"
 #include "lrm_footholds.h"
 #include "lrm_footholds_posed.h"
+#include "lrm_target_walk.h"
 
 namespace {
 
@@ -80,12 +81,6 @@ inline SupportLayout support_layout(size_t nposes, size_t nlegs, size_t nt) {
     return L;
 }
 
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
@@ -229,12 +224,12 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_SUPPORT_MIN_WAVES) void footho
             if (inside) in_legs |= 1u << l;
         }
         if (any_legs == 0u) return;
-        wave_lds_fence(); // every lane is done with the previous pose's tables
+        lrm_wave_lds_fence(); // every lane is done with the previous pose's tables
         for (uint32_t mm = any_legs; mm != 0u; mm &= mm - 1u) {
             const uint32_t l = (uint32_t)__builtin_ctz(mm);
             reinterpret_cast<float*>(my_lists[l])[lane] = reinterpret_cast<const float*>(&recs[r0 + l].head.lists[0][0])[lane];
         }
-        wave_lds_fence();
+        lrm_wave_lds_fence();
         for (uint32_t mm = any_legs; mm != 0u; mm &= mm - 1u) {
             const uint32_t l = (uint32_t)__builtin_ctz(mm);
             bool hit = false;
@@ -249,7 +244,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_SUPPORT_MIN_WAVES) void footho
             for (int k = 0; k < LRM_MAX_LEGS; k++)
                 if ((uint32_t)k == l) { // l is wave-uniform: one branch taken
                     count[k] += hit ? 1 : 0;
-                    key[k] = min_u64(key[k], kk);
+                    key[k] = lrm_min_u64(key[k], kk);
                 }
         }
     };
@@ -307,10 +302,10 @@ __global__ __launch_bounds__(kBlock) void foothold_support_finish_kernel(const u
     for (uint32_t l = 0; l < nlegs; l++) {
         const size_t o = (size_t)l * nt + t;
         const int32_t n = counts[o];
-        const uint64_t best = keys[o];
+        const LrmFootholdChoice c = lrm_foothold_key_decode(keys[o], n != 0);
         count_out[o] = n;
-        best_pose_out[o] = n ? (int32_t)(uint32_t)best : -1;
-        if (best_d2_out) best_d2_out[o] = n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+        best_pose_out[o] = c.index;
+        if (best_d2_out) best_d2_out[o] = c.d2;
         if (n) mask |= 1u << l;
     }
     if (legs_mask_out) legs_mask_out[t] = (uint8_t)mask;

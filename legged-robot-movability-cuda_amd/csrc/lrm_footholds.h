@@ -27,3 +27,16 @@ LRM_HD uint64_t lrm_foothold_key(float d2, uint32_t index) {
     return ((uint64_t)bits.u << 32) | index;
 }
 constexpr uint64_t kLrmFootholdNone = ~(uint64_t)0;
+// What a key holds: the candidate's index and d2, or -1 and +inf when there is none (have false: the key is not read).
+struct LrmFootholdChoice {
+    int32_t index;
+    float d2;
+};
+LRM_HD LrmFootholdChoice lrm_foothold_key_decode(uint64_t key, bool have) {
+    union {
+        uint32_t u;
+        float f;
+    } bits;
+    bits.u = (uint32_t)(key >> 32);
+    return LrmFootholdChoice{have ? (int32_t)(uint32_t)key : -1, have ? bits.f : __builtin_inff()};
+}

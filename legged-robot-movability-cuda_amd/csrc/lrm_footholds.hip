@@ -22,6 +22,7 @@
 #include "lrm_point.h"
 #include "lrm_point_fast.h"
 #include "lrm_footholds.h"
+#include "lrm_target_walk.h"
 
 namespace {
 
@@ -30,19 +31,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kTargetTile = 1024; // the tiles of tile_aabb_kernel (lrm_kernels.hip)
 constexpr int kQueue = 128;
 
-// the same helpers as lrm_kernels.hip's
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ float box_dist2(const float* bb, float x, float y, float z) {
-    const float ex = fmaxf(fmaxf(bb[0] - x, x - bb[3]), 0.f);
-    const float ey = fmaxf(fmaxf(bb[1] - y, y - bb[4]), 0.f);
-    const float ez = fmaxf(fmaxf(bb[2] - z, z - bb[5]), 0.f);
-    return ex * ex + ey * ey + ez * ez;
-}
-__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
 
 #ifndef LRM_FOOTHOLDS_MIN_WAVES
 #define LRM_FOOTHOLDS_MIN_WAVES 8 // as LRM_ANY_WAVE_MIN_WAVES: 64 VGPRs + 128-144 B/lane of scratch, config 3 in 1.52 ms; 5 waves (93 VGPRs, no VGPR spill): 1.81 ms
@@ -107,7 +95,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_MIN_WAVES) void footholds_wav
                 const uint64_t kk = hit ? lrm_foothold_key(lrm_foothold_d2(t, body, s_nom[l]), ti) : kLrmFootholdNone;
 #pragma unroll
                 for (int k = 0; k < LRM_MAX_LEGS; k++)
-                    if (k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+                    if (k == l) key[k] = lrm_min_u64(key[k], kk); // l is wave-uniform: one branch taken
             }
         };
 
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_MIN_WAVES) void footholds_wav
             // rounding of the bound itself
             const size_t tl = tw0 + lane;
             unsigned long long near =
-                __ballot(tl < ntiles && (!boxes || box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f <= r2max));
+                __ballot(tl < ntiles && (!boxes || lrm_box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f <= r2max));
             while (near != 0ull) {
                 const int tb = __builtin_ctzll(near);
                 near &= near - 1ull;
@@ -131,7 +119,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_MIN_WAVES) void footholds_wav
                         const int l = l0 + (lane >> 4);
                         bool touch = false;
                         if (l < nlegs)
-                            touch = box_dist2(cb, body.x + s_sphere[l][0], body.y + s_sphere[l][1], body.z + s_sphere[l][2]) * 0.999f <=
+                            touch = lrm_box_dist2(cb, body.x + s_sphere[l][0], body.y + s_sphere[l][1], body.z + s_sphere[l][2]) * 0.999f <=
                                     s_sphere[l][3];
                         const unsigned long long mm = __ballot(touch);
                         cnear |= (uint32_t)((mm | (mm >> 16) | (mm >> 32) | (mm >> 48)) & 0xffffull);
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_MIN_WAVES) void footholds_wav
                         qi[pos] = ti;
                     }
                     count += __builtin_popcountll(m);
-                    wave_lds_fence();
+                    lrm_wave_lds_fence();
                     if (count >= 64) {
                         process(64);
                         count -= 64;
@@ -185,34 +173,30 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLDS_MIN_WAVES) void footholds_wav
                         float mx = 0.f, my = 0.f, mz = 0.f;
                         uint32_t mi = 0u;
                         if (lane < count) { mx = qx[64 + lane]; my = qy[64 + lane]; mz = qz[64 + lane]; mi = qi[64 + lane]; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                         if (lane < count) { qx[lane] = mx; qy[lane] = my; qz[lane] = mz; qi[lane] = mi; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                     }
                 }
             }
         }
         if (count > 0) process(count);
-        wave_lds_fence(); // the queue is refilled by this wave's next body
+        lrm_wave_lds_fence(); // the queue is refilled by this wave's next body
 
         // per leg: the wave's smallest key; lane l keeps leg l's
         uint64_t best = kLrmFootholdNone;
 #pragma unroll
         for (int k = 0; k < LRM_MAX_LEGS; k++) {
             if (k >= nlegs) break; // wave-uniform
-            uint64_t v = key[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
-                v = min_u64(v, ((uint64_t)hi << 32) | lo);
-            }
+            const uint64_t v = lrm_wave_min_u64(key[k]);
             if (lane == k) best = v;
         }
         if (lane < nlegs) {
             const size_t o = (size_t)lane * nb + b;
+            const LrmFootholdChoice c = lrm_foothold_key_decode(best, legs_n != 0u);
             count_out[o] = (int32_t)legs_n;
-            best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
-            if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+            best_out[o] = c.index;
+            if (best_d2_out) best_d2_out[o] = c.d2;
         }
     }
 }
@@ -223,17 +207,13 @@ hipError_t lrm_launch_footholds(const float* bx, const float* by, const float* b
                                 const float* ty, const float* tz, size_t nt, const LrmCompiledLeg* legs_dev, int nlegs,
                                 float* tile_boxes, const LrmFootNominal& nominal, int32_t* count_out, int32_t* best_out,
                                 float* best_d2_out, bool fast, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    const dim3 grid((unsigned)((nb + kWaves - 1) / kWaves));
-    const float* boxes = nt ? tile_boxes : nullptr;
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nb, kWaves, 0 /* a wave per body, no cap */, st);
+    if (w.err != hipSuccess) return w.err;
     if (fast)
-        hipLaunchKernelGGL(footholds_wave_kernel<true>, grid, dim3(kBlock), 0, st, bx, by, bz, nb, tx, ty, tz, nt, legs_dev, nlegs,
-                           boxes, nominal, count_out, best_out, best_d2_out);
+        hipLaunchKernelGGL(footholds_wave_kernel<true>, w.grid, dim3(kBlock), 0, st, bx, by, bz, nb, tx, ty, tz, nt, legs_dev, nlegs,
+                           w.boxes, nominal, count_out, best_out, best_d2_out);
     else
-        hipLaunchKernelGGL(footholds_wave_kernel<false>, grid, dim3(kBlock), 0, st, bx, by, bz, nb, tx, ty, tz, nt, legs_dev, nlegs,
-                           boxes, nominal, count_out, best_out, best_d2_out);
+        hipLaunchKernelGGL(footholds_wave_kernel<false>, w.grid, dim3(kBlock), 0, st, bx, by, bz, nb, tx, ty, tz, nt, legs_dev, nlegs,
+                           w.boxes, nominal, count_out, best_out, best_d2_out);
     return hipGetLastError();
 }

@@ -43,6 +43,7 @@
 #include "lrm_point.h"
 #include "lrm_footholds.h"
 #include "lrm_footholds_posed.h"
+#include "lrm_target_walk.h"
 
 namespace {
 
@@ -69,19 +70,6 @@ __global__ __launch_bounds__(kBlock) void pose_footholds_compile_kernel(const fl
     out[t] = E;
 }
 
-// the same helpers as lrm_footholds.hip's
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ float box_dist2(const float* bb, float x, float y, float z) {
-    const float ex = fmaxf(fmaxf(bb[0] - x, x - bb[3]), 0.f);
-    const float ey = fmaxf(fmaxf(bb[1] - y, y - bb[4]), 0.f);
-    const float ez = fmaxf(fmaxf(bb[2] - z, z - bb[5]), 0.f);
-    return ex * ex + ey * ey + ez * ez;
-}
-__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
 
 #ifndef LRM_FOOTHOLDS_POSED_MIN_WAVES
 #define LRM_FOOTHOLDS_POSED_MIN_WAVES 8 // footholds_wave_kernel's setting
@@ -112,11 +100,11 @@ __device__ __forceinline__ void footholds_posed_traverse(
     for (uint32_t p = blockIdx.x * kWaves + wave; p < nposes; p += gridDim.x * kWaves) { // wave-uniform
         const uint32_t r0 = p * nlegs; // nposes * nlegs < 2^32 (checked by the C ABI)
         // stage the pose's tables: every lane is done with the previous pose's
-        wave_lds_fence();
+        lrm_wave_lds_fence();
         for (uint32_t l = 0; l < nlegs; l++)
             reinterpret_cast<float*>(my_lists[l])[lane] = reinterpret_cast<const float*>(&recs[r0 + l].head.lists[0][0])[lane];
         if ((uint32_t)lane < nlegs * 4) my_sphere[lane >> 2][lane & 3] = reinterpret_cast<const float*>(&fh[r0 + (lane >> 2)])[lane & 3];
-        wave_lds_fence();
+        lrm_wave_lds_fence();
         const LrmPoseRecord& R0 = lrm_fresh(recs[r0]);
         const LrmVec3 body{R0.body_pos[0], R0.body_pos[1], R0.body_pos[2]}; // the same in every record of the pose
         float r2max = 0.f;
@@ -183,7 +171,7 @@ __device__ __forceinline__ void footholds_posed_traverse(
                     const uint64_t kk = hit ? lrm_foothold_key(lrm_foothold_d2(t, body, E.nominal_w), ti) : kLrmFootholdNone;
 #pragma unroll
                     for (int k = 0; k < LRM_MAX_LEGS; k++)
-                        if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+                        if ((uint32_t)k == l) key[k] = lrm_min_u64(key[k], kk); // l is wave-uniform: one branch taken
                 }
             }
         };
@@ -193,7 +181,7 @@ __device__ __forceinline__ void footholds_posed_traverse(
             // rounding of the bound itself
             const size_t tl = tw0 + lane;
             unsigned long long near =
-                __ballot(tl < ntiles && (!boxes || box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f <= r2max));
+                __ballot(tl < ntiles && (!boxes || lrm_box_dist2(boxes + tl * 6, body.x, body.y, body.z) * 0.999f <= r2max));
             while (near != 0ull) {
                 const int tb = __builtin_ctzll(near);
                 near &= near - 1ull;
@@ -208,7 +196,7 @@ __device__ __forceinline__ void footholds_posed_traverse(
                         const uint32_t l = l0 + (lane >> 4);
                         bool touch = false;
                         if (l < nlegs)
-                            touch = box_dist2(cb, body.x + my_sphere[l][0], body.y + my_sphere[l][1], body.z + my_sphere[l][2]) * 0.999f <=
+                            touch = lrm_box_dist2(cb, body.x + my_sphere[l][0], body.y + my_sphere[l][1], body.z + my_sphere[l][2]) * 0.999f <=
                                     my_sphere[l][3];
                         const unsigned long long mm = __ballot(touch);
                         cnear |= (uint32_t)((mm | (mm >> 16) | (mm >> 32) | (mm >> 48)) & 0xffffull);
@@ -254,7 +242,7 @@ __device__ __forceinline__ void footholds_posed_traverse(
                         qi[pos] = ti;
                     }
                     count += __builtin_popcountll(m);
-                    wave_lds_fence();
+                    lrm_wave_lds_fence();
                     if (count >= 64) {
                         process(64);
                         count -= 64;
@@ -262,9 +250,9 @@ __device__ __forceinline__ void footholds_posed_traverse(
                         float mx = 0.f, my = 0.f, mz = 0.f;
                         uint32_t mi = 0u;
                         if (lane < count) { mx = qx[64 + lane]; my = qy[64 + lane]; mz = qz[64 + lane]; mi = qi[64 + lane]; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                         if (lane < count) { qx[lane] = mx; qy[lane] = my; qz[lane] = mz; qi[lane] = mi; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                     }
                 }
             }
@@ -279,20 +267,16 @@ __device__ __forceinline__ void footholds_posed_traverse(
 #pragma unroll
             for (int k = 0; k < LRM_MAX_LEGS; k++) {
                 if ((uint32_t)k >= nlegs) break; // wave-uniform
-                uint64_t v = key[k];
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
-                    v = min_u64(v, ((uint64_t)hi << 32) | lo);
-                }
+                const uint64_t v = lrm_wave_min_u64(key[k]);
                 if (lane == k) best = v;
             }
             const bool mine = (uint32_t)lane < nlegs;
             if (mine) {
                 const size_t o = (size_t)lane * nposes + p;
+                const LrmFootholdChoice c = lrm_foothold_key_decode(best, legs_n != 0u);
                 count_out[o] = (int32_t)legs_n;
-                best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
-                if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+                best_out[o] = c.index;
+                if (best_d2_out) best_d2_out[o] = c.d2;
             }
             if (all_legs_out) { // wave-uniform
                 const unsigned long long have = __ballot(mine && legs_n != 0u);
@@ -435,7 +419,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
         }
         const uint32_t ra0 = pa * nlegs, rb0 = pb * nlegs; // nposes * nlegs < 2^32 (checked by the C ABI)
         // stage both poses' tables: every lane is done with the previous edge's
-        wave_lds_fence();
+        lrm_wave_lds_fence();
         for (uint32_t l = 0; l < nlegs; l++) {
             reinterpret_cast<float*>(lists_a[l])[lane] = reinterpret_cast<const float*>(&recs[ra0 + l].head.lists[0][0])[lane];
             reinterpret_cast<float*>(lists_b[l])[lane] = reinterpret_cast<const float*>(&recs[rb0 + l].head.lists[0][0])[lane];
@@ -444,7 +428,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
             const uint32_t k = (uint32_t)lane & 31u;
             if (k < nlegs * 4) s_sphere[wave][lane >> 5][k >> 2][k & 3] = reinterpret_cast<const float*>(&fh[(lane < 32 ? ra0 : rb0) + (k >> 2)])[k & 3];
         }
-        wave_lds_fence();
+        lrm_wave_lds_fence();
         const LrmPoseRecord& RA = lrm_fresh(recs[ra0]);
         const LrmPoseRecord& RB = lrm_fresh(recs[rb0]);
         const LrmVec3 body_a{RA.body_pos[0], RA.body_pos[1], RA.body_pos[2]}; // the same in every record of the pose
@@ -496,15 +480,15 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
                                         : kLrmFootholdNone;
 #pragma unroll
                 for (int k = 0; k < LRM_MAX_LEGS; k++)
-                    if ((uint32_t)k == l) key[k] = min_u64(key[k], kk); // l is wave-uniform: one branch taken
+                    if ((uint32_t)k == l) key[k] = lrm_min_u64(key[k], kk); // l is wave-uniform: one branch taken
             }
         };
 
         for (size_t tg0 = 0; tg0 < ntiles; tg0 += 64) {
             // lane = tile: near only when the box is within reach of BOTH bodies (0.999: the rounding of the bound itself)
             const size_t tl = tg0 + lane;
-            unsigned long long near = __ballot(tl < ntiles && (!boxes || (box_dist2(boxes + tl * 6, body_a.x, body_a.y, body_a.z) * 0.999f <= r2a &&
-                                                                          box_dist2(boxes + tl * 6, body_b.x, body_b.y, body_b.z) * 0.999f <= r2b)));
+            unsigned long long near = __ballot(tl < ntiles && (!boxes || (lrm_box_dist2(boxes + tl * 6, body_a.x, body_a.y, body_a.z) * 0.999f <= r2a &&
+                                                                          lrm_box_dist2(boxes + tl * 6, body_b.x, body_b.y, body_b.z) * 0.999f <= r2b)));
             while (near != 0ull) {
                 const int tb = __builtin_ctzll(near);
                 near &= near - 1ull;
@@ -519,8 +503,8 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
                         const uint32_t l = l0 + (lane >> 4);
                         bool touch = false;
                         if (l < nlegs)
-                            touch = box_dist2(cb, body_a.x + sph_a[l][0], body_a.y + sph_a[l][1], body_a.z + sph_a[l][2]) * 0.999f <= sph_a[l][3] &&
-                                    box_dist2(cb, body_b.x + sph_b[l][0], body_b.y + sph_b[l][1], body_b.z + sph_b[l][2]) * 0.999f <= sph_b[l][3];
+                            touch = lrm_box_dist2(cb, body_a.x + sph_a[l][0], body_a.y + sph_a[l][1], body_a.z + sph_a[l][2]) * 0.999f <= sph_a[l][3] &&
+                                    lrm_box_dist2(cb, body_b.x + sph_b[l][0], body_b.y + sph_b[l][1], body_b.z + sph_b[l][2]) * 0.999f <= sph_b[l][3];
                         const unsigned long long mm = __ballot(touch);
                         cnear |= (uint32_t)((mm | (mm >> 16) | (mm >> 32) | (mm >> 48)) & 0xffffull);
                     }
@@ -567,7 +551,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
                         qi[pos] = ti;
                     }
                     count += __builtin_popcountll(m);
-                    wave_lds_fence();
+                    lrm_wave_lds_fence();
                     if (count >= 64) {
                         process(64);
                         count -= 64;
@@ -575,9 +559,9 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
                         float mx = 0.f, my = 0.f, mz = 0.f;
                         uint32_t mi = 0u;
                         if (lane < count) { mx = qx[64 + lane]; my = qy[64 + lane]; mz = qz[64 + lane]; mi = qi[64 + lane]; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                         if (lane < count) { qx[lane] = mx; qy[lane] = my; qz[lane] = mz; qi[lane] = mi; }
-                        wave_lds_fence();
+                        lrm_wave_lds_fence();
                     }
                 }
             }
@@ -589,19 +573,15 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
 #pragma unroll
         for (int k = 0; k < LRM_MAX_LEGS; k++) {
             if ((uint32_t)k >= nlegs) break; // wave-uniform
-            uint64_t v = key[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)v, off), hi = __shfl_xor((uint32_t)(v >> 32), off);
-                v = min_u64(v, ((uint64_t)hi << 32) | lo);
-            }
+            const uint64_t v = lrm_wave_min_u64(key[k]);
             if (lane == k) best = v;
         }
         if (mine) {
             const size_t o = (size_t)lane * nedges + e;
+            const LrmFootholdChoice c = lrm_foothold_key_decode(best, legs_n != 0u);
             count_out[o] = (int32_t)legs_n;
-            best_out[o] = legs_n ? (int32_t)(uint32_t)best : -1;
-            if (best_d2_out) best_d2_out[o] = legs_n ? __uint_as_float((uint32_t)(best >> 32)) : __builtin_inff();
+            best_out[o] = c.index;
+            if (best_d2_out) best_d2_out[o] = c.d2;
         }
         if (all_legs_out) { // wave-uniform
             const unsigned long long have = __ballot(mine && legs_n != 0u);
@@ -626,15 +606,10 @@ hipError_t lrm_launch_pose_footholds_compile(const float* quats, size_t nposes, 
 hipError_t lrm_launch_footholds_posed(const float* tx, const float* ty, const float* tz, size_t nt, const void* records,
                                       const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes, int32_t* count_out,
                                       int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    size_t g = (nposes + kWaves - 1) / kWaves;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const float* boxes = nt ? tile_boxes : nullptr;
-    hipLaunchKernelGGL(footholds_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
-                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, count_out, best_out, best_d2_out,
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nposes, kWaves, kMaxGrid, st);
+    if (w.err != hipSuccess) return w.err;
+    hipLaunchKernelGGL(footholds_posed_kernel, w.grid, dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, w.boxes, count_out, best_out, best_d2_out,
                        all_legs_out);
     return hipGetLastError();
 }
@@ -643,16 +618,11 @@ hipError_t lrm_launch_foothold_lists_posed(const float* tx, const float* ty, con
                                            const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
                                            const int64_t* offsets, size_t capacity, int32_t* idx_out, float* d2_out,
                                            int32_t* written_out, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    size_t g = (nposes + kWaves - 1) / kWaves;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const float* boxes = nt ? tile_boxes : nullptr;
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nposes, kWaves, kMaxGrid, st);
+    if (w.err != hipSuccess) return w.err;
     const int64_t cap = capacity > (size_t)INT64_MAX ? INT64_MAX : (int64_t)capacity;
-    hipLaunchKernelGGL(foothold_lists_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
-                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, offsets, cap, idx_out, d2_out,
+    hipLaunchKernelGGL(foothold_lists_posed_kernel, w.grid, dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, w.boxes, offsets, cap, idx_out, d2_out,
                        written_out);
     return hipGetLastError();
 }
@@ -661,15 +631,10 @@ hipError_t lrm_launch_foothold_edges_posed(const float* tx, const float* ty, con
                                            const void* fh_records, size_t nposes, size_t nlegs, float* tile_boxes,
                                            const int32_t* edge_a, const int32_t* edge_b, size_t nedges, int32_t* count_out,
                                            int32_t* best_out, float* best_d2_out, uint8_t* all_legs_out, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    size_t g = (nedges + kWaves - 1) / kWaves;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const float* boxes = nt ? tile_boxes : nullptr;
-    hipLaunchKernelGGL(foothold_edges_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
-                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, edge_a, edge_b, (uint32_t)nedges,
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nedges, kWaves, kMaxGrid, st);
+    if (w.err != hipSuccess) return w.err;
+    hipLaunchKernelGGL(foothold_edges_posed_kernel, w.grid, dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmPoseFootEntry*)fh_records, (uint32_t)nposes, (uint32_t)nlegs, w.boxes, edge_a, edge_b, (uint32_t)nedges,
                        count_out, best_out, best_d2_out, all_legs_out);
     return hipGetLastError();
 }

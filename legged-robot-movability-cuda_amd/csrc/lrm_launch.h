@@ -64,6 +64,22 @@ hipError_t lrm_launch_reach_any(const float* bx, const float* by, const float* b
                                 uint8_t* all_legs_out, bool fast, hipStream_t st);
 // tile_aabb_kernel alone: the two-level boxes of a target cloud (17 x ntiles x 6 floats of workspace, as above)
 hipError_t lrm_launch_tile_boxes(const float* tx, const float* ty, const float* tz, size_t nt, float* tile_boxes, hipStream_t st);
+// The prologue of the launchers whose waves each walk the whole target cloud for one of n items (bodies, poses, edges):
+// the cloud's boxes into tile_boxes when there is a workspace and a cloud; boxes = what the kernel gets (null = every tile
+// near); grid = workgroups of `waves` items, at most max_grid of them when that is not 0 (a wave strides over the rest).
+struct LrmWalkLaunch {
+    hipError_t err;
+    const float* boxes;
+    dim3 grid;
+};
+inline LrmWalkLaunch lrm_walk_launch(const float* tx, const float* ty, const float* tz, size_t nt, float* tile_boxes, size_t n,
+                                     unsigned waves, unsigned max_grid, hipStream_t st) {
+    hipError_t err = hipSuccess;
+    if (tile_boxes && nt) err = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
+    size_t g = (n + waves - 1) / waves;
+    if (max_grid && g > max_grid) g = max_grid;
+    return LrmWalkLaunch{err, nt ? tile_boxes : nullptr, dim3((unsigned)g)};
+}
 // lrm_footholds_dev (lrm_footholds.hip): outputs [nlegs * nb] at l * nb + b; best_d2_out may be null; tile_boxes null =
 // no culling (small clouds), otherwise workspace that this call fills with the cloud's boxes first
 struct LrmFootNominal; // lrm_footholds.h

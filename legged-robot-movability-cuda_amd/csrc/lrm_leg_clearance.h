@@ -97,9 +97,15 @@ LRM_HD uint64_t lrm_leg_clearance_key(float pen, uint32_t index) {
     const uint32_t u = lrm_f2u(pen);
     return ((uint64_t)((u >> 31) ? u : 0x7fffffffu - u) << 32) | index;
 }
-LRM_HD float lrm_leg_clearance_key_pen(uint64_t key) {
+// What a key holds: the near target's index (< nt) and pen, or -1 and -inf for kLrmLegClearanceNone.
+struct LrmLegClearanceWorst {
+    int32_t index;
+    float pen;
+};
+LRM_HD LrmLegClearanceWorst lrm_leg_clearance_key_decode(uint64_t key) {
     const uint32_t h = (uint32_t)(key >> 32);
-    return lrm_u2f((h >> 31) ? h : 0x7fffffffu - h);
+    const bool have = key != kLrmLegClearanceNone;
+    return LrmLegClearanceWorst{have ? (int32_t)(uint32_t)key : -1, have ? lrm_u2f((h >> 31) ? h : 0x7fffffffu - h) : -__builtin_inff()};
 }
 
 #if defined(__HIPCC__)

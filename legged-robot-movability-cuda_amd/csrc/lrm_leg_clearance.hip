@@ -51,6 +51,7 @@
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_leg_clearance.h"
+#include "lrm_target_walk.h"
 
 namespace {
 
@@ -59,7 +60,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kTargetTile = 1024; // the tiles of tile_aabb_kernel (lrm_kernels.hip)
 constexpr unsigned kMaxGrid = 16384; // 65 536 poses in flight; a wave strides over the rest (body_clearance_posed_kernel's cap)
 
-__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return b < a ? b : a; }
 __device__ __forceinline__ float uni(float v) { // a value every lane computed alike, moved to an SGPR
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
@@ -184,25 +184,21 @@ __global__ __launch_bounds__(kBlock, LRM_LEG_CLEARANCE_MIN_WAVES) void leg_clear
                             if (!ok) in = 0u;
                             hits += (uint32_t)__builtin_popcountll(__ballot((in & 7u) != 0u));
                             mybits |= in & 7u;
-                            if (in & LRM_LEG_NEAR) key = min_u64(key, lrm_leg_clearance_key(pen, ti));
+                            if (in & LRM_LEG_NEAR) key = lrm_min_u64(key, lrm_leg_clearance_key(pen, ti));
                         }
                     }
                 }
             }
 
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const uint32_t klo = __shfl_xor((uint32_t)key, off), khi = __shfl_xor((uint32_t)(key >> 32), off);
-                key = min_u64(key, ((uint64_t)khi << 32) | klo);
-            }
+            key = lrm_wave_min_u64(key);
             const unsigned links = (__ballot(mybits & 1u) != 0ull ? 1u : 0u) | (__ballot(mybits & 2u) != 0ull ? 2u : 0u) |
                                    (__ballot(mybits & 4u) != 0ull ? 4u : 0u);
             if (lane == 0) {
-                const bool have = key != kLrmLegClearanceNone;
+                const LrmLegClearanceWorst worst = lrm_leg_clearance_key_decode(key);
                 hits_out[o] = (int32_t)hits;
                 links_out[o] = (uint8_t)links;
-                worst_out[o] = have ? (int32_t)(uint32_t)key : -1; // < nt when have
-                if (pen_out) pen_out[o] = have ? lrm_leg_clearance_key_pen(key) : -inf;
+                worst_out[o] = worst.index;
+                if (pen_out) pen_out[o] = worst.pen;
             }
             pose_free = pose_free && hits == 0u;
         }
@@ -241,15 +237,10 @@ hipError_t lrm_launch_leg_clearance_posed(const float* tx, const float* ty, cons
                                           const float* femur, const float* tibia, const float radius[3], float margin,
                                           float tip_clear, const uint8_t* live_in, int32_t* hits_out, uint8_t* links_out,
                                           int32_t* worst_out, float* pen_out, uint8_t* free_out, hipStream_t st) {
-    if (tile_boxes && nt) {
-        const hipError_t e = lrm_launch_tile_boxes(tx, ty, tz, nt, tile_boxes, st);
-        if (e != hipSuccess) return e;
-    }
-    size_t g = (nposes + kWaves - 1) / kWaves;
-    if (g > kMaxGrid) g = kMaxGrid;
-    const float* boxes = nt ? tile_boxes : nullptr;
-    hipLaunchKernelGGL(leg_clearance_posed_kernel, dim3((unsigned)g), dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
-                       (const LrmIkLeg*)ik_records, (uint32_t)nposes, (uint32_t)nlegs, boxes, coxa, femur, tibia, radius[0], radius[1],
+    const LrmWalkLaunch w = lrm_walk_launch(tx, ty, tz, nt, tile_boxes, nposes, kWaves, kMaxGrid, st);
+    if (w.err != hipSuccess) return w.err;
+    hipLaunchKernelGGL(leg_clearance_posed_kernel, w.grid, dim3(kBlock), 0, st, tx, ty, tz, nt, (const LrmPoseRecord*)records,
+                       (const LrmIkLeg*)ik_records, (uint32_t)nposes, (uint32_t)nlegs, w.boxes, coxa, femur, tibia, radius[0], radius[1],
                        radius[2], margin, tip_clear, live_in, hits_out, links_out, worst_out, pen_out, free_out);
     return hipGetLastError();
 }

@@ -84,7 +84,7 @@ def picked(lrm, nposes, nt, seed):
     return quats, body, np.ascontiguousarray(targets[pick])
 
 
-@pytest.mark.parametrize("nt", [1, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025])
+@pytest.mark.parametrize("nt", [0, 1, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025])
 def test_cloud_sizes_without_boxes(lrm, torch_cuda, nt):
     quats, body, targets = picked(lrm, 150, nt, seed=nt % 89)
     check(lrm, torch_cuda, targets, quats, body, legs6(lrm), mixed=nt >= 63)

@@ -83,7 +83,7 @@ def check(lrm, torch, targets, quats, body, legs, margin, count_in=None, both=Tr
     return want
 
 
-@pytest.mark.parametrize("nt", [0, 1, 63, 64, 65, TILE - 1, TILE + 1, 4095, 4096, 4097, (GROUP + 1) * TILE + 1])
+@pytest.mark.parametrize("nt", [0, 1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 4095, 4096, 4097, (GROUP + 1) * TILE + 1])
 def test_every_cloud_size(lrm, torch_cuda, nt):
     legs, _ = pc.leg_families(lrm)["m2_6_tilted"]
     quats, body, targets = fm.scene(lrm, 16 if nt > 20000 else 64, nt, seed=nt % 97)
