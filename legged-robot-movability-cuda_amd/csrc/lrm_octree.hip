@@ -386,10 +386,14 @@ __global__ __launch_bounds__(kOctBlock) void oct_boxes_kernel(const float* __res
     }
 }
 
-// does the box [lo, hi] hold a point p with -H < p - c <= H on every axis (in_box's asymmetric test)?  Conservative.
+// can the box [lo, hi] hold a point p that in_box keeps, -H < fl(p - c) <= H on every axis?  Conservative with respect to in_box's OWN
+// float subtraction: rounding is monotone, so fl(lo - c) <= fl(p - c) <= fl(hi - c) for every p in the box, and a kept p needs
+// fl(lo - c) <= H and fl(hi - c) > -H.  (The earlier form, lo <= fl(c + H) and hi >= fl(c - H), dropped a chunk whose foothold lay one
+// ulp beyond fl(c + H) while fl(p - c) rounded down onto H: tests/test_gpu_octree_shapes.py, the faces of the elongated box.)
+// A box of nan (a chunk of nan rows) and the (+big, -big) box of an empty chunk meet nothing.
 __device__ __forceinline__ bool box_meets(const float* bb, const float* c, const float* H) {
-    return bb[0] <= c[0] + H[0] && bb[3] >= c[0] - H[0] && bb[1] <= c[1] + H[1] && bb[4] >= c[1] - H[1] &&
-           bb[2] <= c[2] + H[2] && bb[5] >= c[2] - H[2];
+    return bb[0] - c[0] <= H[0] && bb[3] - c[0] > -H[0] && bb[1] - c[1] <= H[1] && bb[4] - c[1] > -H[1] &&
+           bb[2] - c[2] <= H[2] && bb[5] - c[2] > -H[2];
 }
 
 #ifndef LRM_OCT_DEFER_MIN_WAVES
