@@ -740,6 +740,68 @@ int lrm_leg_joints_posed_dev(const float* coxa, const float* femur, const float*
                              float* joints_out /* device, nlegs*nposes*12 */, void* stream);
 int lrm_leg_joints_posed_cpu(const float* angles_aos, const float* quats, const float* body, size_t nposes,
                              const LrmLegDimensions* legs, size_t nlegs, float tip_clear, float* joints_out, double* ms);
+/* STATIC STABILITY per stance: does the robot stand, and which legs can it lift.  lrm_footholds_posed_dev says that every leg
+ * has a foothold (all_legs), lrm_body_clearance_posed_dev that the trunk fits and lrm_leg_clearance_posed_dev that the legs
+ * fit; none of them says that the centre of mass lies over the polygon the chosen footholds span, nor which feet can leave
+ * the ground (one leg, a tripod, any subset) with the robot still statically stable.  The reference has no such query (its
+ * leg_number_for_stab only counts legs).  No table: the call reads the cloud, the quaternions and the body positions.
+ * A STANCE s (of nstances) has a pose p = pose_idx[s] (pose_idx == NULL: p = s) and one foot index per leg,
+ * foot[l*nstances + s] (int32): lrm_footholds_posed_dev's best_out as it stands, or lrm_foothold_edges_posed_dev's best_out
+ * with pose_idx = edge_a or edge_b.  Everything is float32 without contraction; only + - * /, comparisons and the correctly
+ * rounded square root are used: device and host give the same bits (csrc/lrm_stance.h is the one source of both).
+ * Foot of leg l: VALID iff 0 <= foot < nt and q = t[foot] - body[p] (one subtraction per component; body == NULL: 0) has
+ *   three finite coordinates.  Its plane point is f_l = (q.x, q.y) with plane == NULL (gravity along -z of the caller's
+ *   frame); with plane = {u[3], v[3]} (host, six finite floats: a basis of the plane normal to gravity, supplied by the
+ *   caller) it is f_l = ((q.x u.x + q.y u.y) + q.z u.z, (q.x v.x + q.y v.y) + q.z v.z).
+ * Centre of mass: c3 = qtRotate(quats[p], com) through the coefficient sums of the pose records (the chain of the foothold
+ *   table's nominal point), com a host float[3] in the BODY frame; com == NULL or all zero gives exactly 0 whatever the
+ *   quaternion.  c3 is projected like a foot: c.  Like the feet, c is relative to body[p].
+ * DEAD stance: live_in[s] == 0 (uint8, nstances, device for _dev and host for _cpu, may be NULL), or p outside [0, nposes), or
+ *   c not finite.
+ * Ordered pairs (i, j), i != j, both feet valid: a = f_i; e = f_j - a; len2 = e.x e.x + e.y e.y; the pair is USABLE iff
+ *   len2 > 0 and len2 < inf;
+ *   left_ij has bit k set, for every valid foot k, iff e.x (f_k.y - a.y) - e.y (f_k.x - a.x) >= 0 (bits i and j come out set
+ *   by the arithmetic);
+ *   s_ij = (e.x (c.y - a.y) - e.y (c.x - a.x)) / sqrt(len2); a nan s_ij counts as -inf, -0 is stored and compared as +0.
+ * Lift sets: lift (host, uint8, nmasks entries, 1 <= nmasks <= 256); bit l set = leg l is in the air.  The planted set is
+ *   S = valid_feet & ~lift[m].  popcount(S) < 3: the margin is -inf.  Otherwise margin = min s_ij over the usable pairs with
+ *   i, j in S and (S & ~left_ij) == 0 -- the counter-clockwise hull edges of the planted feet -- ties to the smaller code
+ *   i*8 + j; no such pair: -inf.
+ * Outputs at [m*nstances + s], all written:
+ *   margin_out (float)  > 0: the distance (mm) of the centre of mass from the nearest edge of the support polygon;
+ *   edge_out   (uint8, may be NULL) the code i*8 + j of that edge, 255 when the margin is -inf;
+ *   stable_out (uint8)  margin > min_margin (min_margin: host float, finite, >= 0);
+ * and feet_out[s] (uint8, nstances, may be NULL): the valid-feet bits, 0 for a dead stance.  A dead stance gets
+ * -inf / 255 / 0 for every lift set.
+ * Consequences: collinear or coincident feet give a margin <= 0, never stable; row m of stable_out is a uint8[nstances],
+ * directly usable as live_in / pose_live of the other posed calls (with pose_idx == NULL a stance is a pose):
+ * update -> footholds -> stance_stability -> body_clearance(live_in = stable row 0) -> ...; for a centre of mass OUTSIDE
+ * the polygon the margin is the most negative half-plane distance, not the Euclidean distance to the polygon; on nearly
+ * collinear hull vertices the arithmetic itself decides which edges count.
+ * Checked first (all LRM_EINVAL): nlegs outside 1..LRM_MAX_LEGS; nmasks outside 1..256; nt, nposes or nstances > INT32_MAX;
+ * nmasks * nstances past 2^32 - 1; NULL lift; a lift bit at or above nlegs; min_margin nan, negative or infinite; a
+ * non-finite com or plane value; pose_idx == NULL with nstances > nposes.  Then nstances == 0 is a no-op; NULL foot, quats,
+ * margin_out or stable_out (or a NULL cloud with nt > 0) gives LRM_EINVAL; nt == 0 makes every foot invalid.
+ * lrm_stance_stability_dev: device pointers are the cloud, quats (nposes x 4), body (nposes x 3, may be NULL), pose_idx, foot,
+ * live_in and the outputs; com, plane and lift are host pointers and travel in the kernel's arguments.  ONE launch: no
+ * allocation, no host synchronisation, no shared buffer -- it can be captured in a graph and may run concurrently with
+ * anything, the pair kernels included, from any host thread.
+ * lrm_stance_stability_cpu: AoS float3 targets, host arrays; a serial loop over every (stance, lift set) with the same
+ * functions: the reference the GPU tests compare with bit for bit; *ms = the loop's time. */
+int lrm_stance_stability_dev(const float* tx, const float* ty, const float* tz, size_t nt,
+                             const float* quats /* device, nposes x 4 */, const float* body /* device, nposes x 3, may be NULL */,
+                             size_t nposes, const int32_t* pose_idx /* device, nstances, may be NULL */,
+                             const int32_t* foot /* device, nlegs*nstances at [l*nstances + s] */, size_t nstances, size_t nlegs,
+                             const float* com /* host, 3, may be NULL */, const float* plane /* host, 6, may be NULL */,
+                             const uint8_t* lift /* host, nmasks */, size_t nmasks, float min_margin,
+                             const uint8_t* live_in /* device, nstances, may be NULL */,
+                             float* margin_out, uint8_t* edge_out /* may be NULL */, uint8_t* stable_out,
+                             uint8_t* feet_out /* nstances, may be NULL */, void* stream);
+int lrm_stance_stability_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body, size_t nposes,
+                             const int32_t* pose_idx, const int32_t* foot, size_t nstances, size_t nlegs,
+                             const float* com, const float* plane, const uint8_t* lift, size_t nmasks, float min_margin,
+                             const uint8_t* live_in /* host, may be NULL */, float* margin_out, uint8_t* edge_out,
+                             uint8_t* stable_out, uint8_t* feet_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

@@ -17,6 +17,7 @@ from ._capi import (  # noqa: F401
     foothold_support_posed_cpu, dbg_foothold_support_grid,
     body_clearance_posed_cpu,
     leg_clearance_posed_cpu, leg_joints_posed_cpu,
+    stance_stability_cpu, stance_lift,
 )
 from . import device  # noqa: F401
 from .device import PoseSet, ik, fk, foothold_offsets, foothold_edges_layout, foothold_support_layout  # noqa: F401

@@ -139,12 +139,14 @@ def load():
         "lrm_leg_clearance_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp],
         "lrm_leg_joints_posed_dev": [vp, vp, vp, sz, sz, vp, vp, fp, vp, vp],
         "lrm_leg_joints_posed_cpu": [vp, vp, vp, sz, vp, sz, fp, vp, vp],
+        "lrm_stance_stability_dev": [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
+        "lrm_stance_stability_cpu": [vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
@@ -681,6 +683,67 @@ def leg_joints_posed_cpu(angles, quats, body, legs, tip_clear=0.0):
     check(load().lrm_leg_joints_posed_cpu(_ptr(angles), _ptr(quats), _ptr(body), n, _ptr(legs), nl, float(tip_clear), _ptr(out),
                                           C.addressof(ms)))
     return out, ms.value
+
+
+def stance_lift(lift, nlegs):
+    """The lift sets of the stance stability calls as uint8: None = [0] (every foot planted), "each" = [0, 1<<0, ...,
+    1<<(nlegs-1)] (nothing lifted, then each leg alone), otherwise 1 to 256 bit masks (bit l = leg l is in the air)."""
+    if lift is None:
+        return np.zeros(1, np.uint8)
+    if isinstance(lift, str):
+        if lift != "each":
+            raise ValueError('lift: None, "each" or 1 to 256 bit masks')
+        return np.array([0] + [1 << l for l in range(nlegs)], np.uint8)
+    a = np.asarray(lift)
+    if a.ndim != 1 or not 1 <= a.size <= 256 or a.dtype.kind not in "iub" or (a.size and (a.min() < 0 or a.max() > 255)):
+        raise ValueError('lift: None, "each" or 1 to 256 bit masks in 0..255')
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def _stance_host(com, plane):
+    com = None if com is None else _f32(com, (3,))
+    plane = None if plane is None else _f32(plane, (6,))
+    return com, plane
+
+
+def stance_stability_cpu(targets, foot, quats, body=None, pose_idx=None, com=None, plane=None, lift=None, min_margin=0.0,
+                         live_in=None, want_edge=True, want_feet=True):
+    """lrm_stance_stability_cpu: per stance s (pose pose_idx[s], or pose s with pose_idx None; one target index per leg,
+    foot int32[nlegs, nstances]: footholds_posed_cpu's best) and per lift set m (stance_lift), the distance of the centre of
+    mass (com, BODY frame, rotated by the pose; None = the body origin) from the nearest edge of the support polygon of the
+    planted feet, in the plane normal to gravity (plane None: the caller's x, y; else two 3-vectors spanning it): margin
+    (-inf: fewer than three planted feet, a degenerate polygon or a dead stance), the edge's code i*8 + j (255 with -inf),
+    stable = margin > min_margin, and per stance the bit mask of the valid feet.  live_in: uint8[nstances] or None; 0 = dead.
+    Serial host loop over every (stance, lift set); want_* False pass NULL.
+    -> (margin float32[nmasks, nstances], edge uint8[nmasks, nstances] or None, stable uint8[nmasks, nstances],
+    feet uint8[nstances] or None, ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats = _f32(quats, (-1, 4))
+    n = len(quats)
+    body = None if body is None else _f32(body, (n, 3))
+    foot = np.ascontiguousarray(foot, np.int32)
+    if foot.ndim != 2:
+        raise ValueError("foot: int32 [nlegs, nstances]")
+    nl, ns = foot.shape
+    if pose_idx is not None:
+        pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
+        if len(pose_idx) != ns:
+            raise ValueError("pose_idx: one pose per stance")
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != ns:
+            raise ValueError("live_in: one byte per stance")
+    com, plane = _stance_host(com, plane)
+    lift = stance_lift(lift, nl)
+    nm = len(lift)
+    margin, stable = np.zeros((nm, ns), np.float32), np.zeros((nm, ns), np.uint8)
+    edge = np.zeros((nm, ns), np.uint8) if want_edge else None
+    feet = np.zeros(ns, np.uint8) if want_feet else None
+    ms = C.c_double(0)
+    check(load().lrm_stance_stability_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), n, _ptr(pose_idx), _ptr(foot), ns, nl,
+                                          _ptr(com), _ptr(plane), _ptr(lift), nm, float(min_margin), _ptr(live_in), _ptr(margin),
+                                          _ptr(edge), _ptr(stable), _ptr(feet), C.addressof(ms)))
+    return margin, edge, stable, feet, ms.value
 
 
 def apply_rbdl_equiv(xyz, leg):

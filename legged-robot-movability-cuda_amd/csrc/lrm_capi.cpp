@@ -22,6 +22,7 @@
 #include "lrm_footholds_posed.h"
 #include "lrm_body_clearance.h"
 #include "lrm_leg_clearance.h"
+#include "lrm_stance.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -2014,6 +2015,117 @@ int lrm_leg_joints_posed_cpu(const float* angles, const float* quats, const floa
                 joints_out[o * 12 + 3 * k + 2] = lrm_leg_joint_out(J[k].z, R.body_pos[2]);
             }
         }
+    return LRM_OK;
+}
+
+// ---- static stability per stance: support-polygon margin per lift set (lrm_stance.hip) -----------
+namespace {
+// every range and scalar check, before any early return; fills *P
+int stance_args(size_t nt, size_t nposes, const int32_t* pose_idx, size_t nstances, size_t nlegs, const float* com, const float* plane,
+                const uint8_t* lift, size_t nmasks, float min_margin, LrmStanceParams* P) {
+    if (nlegs < 1 || nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "stance stability: nlegs must be 1..LRM_MAX_LEGS");
+    if (nmasks < 1 || nmasks > LRM_STANCE_MAX_MASKS) return fail(LRM_EINVAL, "stance stability: nmasks must be 1..256");
+    if (nt > (size_t)INT32_MAX || nposes > (size_t)INT32_MAX || nstances > (size_t)INT32_MAX)
+        return fail(LRM_EINVAL, "stance stability: nt, nposes and nstances must not exceed INT32_MAX");
+    if ((uint64_t)nmasks * (uint64_t)nstances > 0xffffffffull) return fail(LRM_EINVAL, "stance stability: more than 2^32 - 1 answers");
+    if (!lift) return fail(LRM_EINVAL, "null argument");
+    for (size_t m = 0; m < nmasks; m++)
+        if (lift[m] >> nlegs) return fail(LRM_EINVAL, "stance stability: a lift set names a leg at or above nlegs");
+    if (min_margin != min_margin || min_margin < 0.f || !(min_margin < INFINITY))
+        return fail(LRM_EINVAL, "stance stability: min_margin must be >= 0 and finite");
+    for (int k = 0; k < 3; k++)
+        if (com && !lrm_stance_finite(com[k])) return fail(LRM_EINVAL, "stance stability: com must be finite");
+    for (int k = 0; k < 6; k++)
+        if (plane && !lrm_stance_finite(plane[k])) return fail(LRM_EINVAL, "stance stability: plane must be finite");
+    if (!pose_idx && nstances > nposes) return fail(LRM_EINVAL, "stance stability: without pose_idx, stance s takes pose s: nstances <= nposes");
+    *P = LrmStanceParams{};
+    for (int k = 0; k < 3; k++) {
+        P->com[k] = com ? com[k] : 0.f;
+        P->u[k] = plane ? plane[k] : 0.f;
+        P->v[k] = plane ? plane[3 + k] : 0.f;
+    }
+    P->on = plane ? 1u : 0u;
+    P->min_margin = min_margin;
+    P->nmasks = (uint32_t)nmasks;
+    for (size_t m = 0; m < nmasks; m++) P->lift[m] = lift[m];
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_stance_stability_dev(const float* tx, const float* ty, const float* tz, size_t nt, const float* quats, const float* body,
+                             size_t nposes, const int32_t* pose_idx, const int32_t* foot, size_t nstances, size_t nlegs, const float* com,
+                             const float* plane, const uint8_t* lift, size_t nmasks, float min_margin, const uint8_t* live_in,
+                             float* margin_out, uint8_t* edge_out, uint8_t* stable_out, uint8_t* feet_out, void* stream) {
+    LrmStanceParams P;
+    const int rc = stance_args(nt, nposes, pose_idx, nstances, nlegs, com, plane, lift, nmasks, min_margin, &P);
+    if (rc != LRM_OK) return rc;
+    if (nstances == 0) return LRM_OK;
+    if (!foot || !quats || !margin_out || !stable_out || (nt && (!tx || !ty || !tz))) return fail(LRM_EINVAL, "null argument");
+    HIP_TRY(lrm_launch_stance_stability(tx, ty, tz, nt, quats, body, nposes, pose_idx, foot, nstances, nlegs, P, live_in, margin_out,
+                                        edge_out, stable_out, feet_out, (hipStream_t)stream),
+            "stance stability launch");
+    return LRM_OK;
+}
+
+int lrm_stance_stability_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                             const int32_t* pose_idx, const int32_t* foot, size_t nstances, size_t nlegs, const float* com,
+                             const float* plane, const uint8_t* lift, size_t nmasks, float min_margin, const uint8_t* live_in,
+                             float* margin_out, uint8_t* edge_out, uint8_t* stable_out, uint8_t* feet_out, double* ms) {
+    LrmStanceParams P;
+    const int rc = stance_args(nt, nposes, pose_idx, nstances, nlegs, com, plane, lift, nmasks, min_margin, &P);
+    if (rc != LRM_OK) return rc;
+    if (nstances == 0) return LRM_OK;
+    if (!foot || !quats || !margin_out || !stable_out || (nt && !targets)) return fail(LRM_EINVAL, "null argument");
+    const ScopeMs timer{ms};
+    for (size_t s = 0; s < nstances; s++) {
+        const int64_t p = pose_idx ? (int64_t)pose_idx[s] : (int64_t)s;
+        bool live = !(live_in && !live_in[s]) && p >= 0 && (uint64_t)p < nposes;
+        LrmStancePt c{0.f, 0.f};
+        if (live) c = lrm_stance_com(P, quats + 4 * p, &live);
+        LrmStancePt f[LRM_MAX_LEGS] = {};
+        uint32_t feet = 0u;
+        for (size_t l = 0; live && l < nlegs; l++) {
+            const int32_t ft = foot[l * nstances + s];
+            if (!lrm_stance_foot_in_cloud(ft, nt)) continue;
+            const float* t = targets + 3 * (size_t)ft;
+            const float* b = body ? body + 3 * p : nullptr;
+            const LrmVec3 q{t[0] - (b ? b[0] : 0.f), t[1] - (b ? b[1] : 0.f), t[2] - (b ? b[2] : 0.f)};
+            if (!lrm_stance_foot_valid(q)) continue;
+            f[l] = lrm_stance_project(P, q);
+            feet |= 1u << l;
+        }
+        // every ordered pair of valid feet, once per stance
+        uint32_t pair[64];
+        uint32_t word[64];
+        for (int i = 0; i < 8; i++)
+            for (int j = 0; j < 8; j++) {
+                const int code = i * 8 + j;
+                pair[code] = 0u;
+                word[code] = 0u;
+                if (i == j || !((feet >> i) & 1u) || !((feet >> j) & 1u)) continue;
+                const LrmStanceEdge E = lrm_stance_edge(f[i], f[j]);
+                uint32_t left = 0u;
+                for (int k = 0; k < 8; k++)
+                    if (((feet >> k) & 1u) && lrm_stance_left(E, f[k])) left |= 1u << k;
+                pair[code] = lrm_stance_pair_bits(left, i, j, lrm_stance_edge_usable(E));
+                word[code] = lrm_stance_word(lrm_stance_signed(E, c));
+            }
+        for (size_t m = 0; m < nmasks; m++) { // every (stance, lift set)
+            const uint32_t S = lrm_stance_planted(feet, P.lift[m]);
+            uint64_t key = kLrmStanceNone;
+            for (int code = 0; code < 64 && lrm_stance_stands(S); code++) {
+                if (!lrm_stance_pair_counts(pair[code], S)) continue;
+                const uint64_t kc = lrm_stance_key(word[code], (uint32_t)code);
+                if (kc < key) key = kc;
+            }
+            const LrmStanceAnswer A = lrm_stance_key_decode(key);
+            const size_t o = m * nstances + s;
+            margin_out[o] = A.margin;
+            if (edge_out) edge_out[o] = A.edge;
+            stable_out[o] = lrm_stance_stable(A.margin, P.min_margin);
+        }
+        if (feet_out) feet_out[s] = (uint8_t)feet;
+    }
     return LRM_OK;
 }
 

@@ -343,6 +343,64 @@ def apply_oct(x, y, z, leg, settings=None, rank=0, world=1, exchange=None):
         return _capi.apply_oct_dev(_dp(x), _dp(y), _dp(z), n, leg, settings, rank, world, exchange)
 
 
+def stance_stability(tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None, plane=None, lift=None, min_margin=0.0,
+                     live_in=None, margin=None, edge=None, stable=None, feet=None):
+    """lrm_stance_stability_dev: does the robot stand, and which legs can it lift.  A stance s is a pose (pose_idx[s], int32 on
+    the device; None: pose s) and one target index per leg, foot int32 [nlegs, nstances]: PoseSet.footholds()'s best as it
+    stands, or foothold_edges()'s best with pose_idx = edge_a or edge_b.  quats float32 (nposes, 4) and body float32
+    (nposes, 3) or None are the tensors given to update().  com: the centre of mass in the BODY frame (3 host floats, None =
+    the body origin); plane: None = gravity along -z of the caller's frame, else two host 3-vectors spanning the plane normal to
+    gravity; lift: None = [0], "each" = [0, 1<<0, ..., 1<<(nlegs-1)], or 1 to 256 bit masks (bit l = leg l is in the air).
+    margin[m, s] = the distance of the projected centre of mass from the nearest edge of the support polygon of the feet
+    planted under lift set m (-inf: fewer than three, a degenerate polygon or a dead stance; negative: outside);
+    edge[m, s] = that edge's code i*8 + j (255 with -inf); stable[m, s] = margin > min_margin; feet[s] = the valid feet.
+    live_in: uint8 [nstances] on the device, 0 = dead.  -> (margin float32, edge uint8, stable uint8, each [nmasks,
+    nstances]; feet uint8 [nstances]).  Every tensor must be contiguous.  stable[m] is directly the live_in / pose_live of the
+    other posed calls.  One launch, no allocation beyond missing outputs, no shared buffer: it can be captured in a graph
+    and may run next to anything."""
+    torch = _torch()
+    nt = _check_f32(tx, ty, tz)
+    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
+        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
+    nposes = quats.shape[0]
+    if nt and tx.device != quats.device:
+        raise ValueError("targets and poses must live on one device")
+    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
+                                 and tuple(body.shape) == (nposes, 3)):
+        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
+    if not (foot.is_cuda and foot.device == quats.device and foot.dtype == torch.int32 and foot.dim() == 2 and foot.is_contiguous()
+            and 1 <= foot.shape[0] <= 8):
+        raise ValueError("foot: expected a contiguous int32 tensor of shape (nlegs, nstances), 1 to 8 legs, on the poses' device")
+    nl, ns = foot.shape
+    _check_out(pose_idx, quats, torch.int32, ns, "pose_idx")
+    _check_out(live_in, quats, torch.uint8, ns, "live_in")
+    if pose_idx is not None and pose_idx.numel() != ns or live_in is not None and live_in.numel() != ns:
+        raise ValueError("pose_idx / live_in: one entry per stance")
+    if pose_idx is None and ns > nposes:
+        raise ValueError("without pose_idx stance s takes pose s: nstances <= nposes")
+    com, plane = _capi._stance_host(com, plane)
+    lift = _capi.stance_lift(lift, nl)
+    nm = len(lift)
+    if margin is None:
+        margin = torch.empty((nm, ns), dtype=torch.float32, device=quats.device)
+    if edge is None:
+        edge = torch.empty((nm, ns), dtype=torch.uint8, device=quats.device)
+    if stable is None:
+        stable = torch.empty((nm, ns), dtype=torch.uint8, device=quats.device)
+    if feet is None:
+        feet = torch.empty(ns, dtype=torch.uint8, device=quats.device)
+    _check_out(margin, quats, torch.float32, nm * ns, "margins")
+    _check_out(edge, quats, torch.uint8, nm * ns, "edge codes")
+    _check_out(stable, quats, torch.uint8, nm * ns, "stable bytes")
+    _check_out(feet, quats, torch.uint8, ns, "per-stance feet")
+    with torch.cuda.device(quats.device):
+        _capi.check(_capi.load().lrm_stance_stability_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _dp(pose_idx),
+                                                          _dp(foot), ns, nl, _capi._ptr(com), _capi._ptr(plane), _capi._ptr(lift), nm,
+                                                          float(min_margin), _dp(live_in), _dp(margin), _dp(edge), _dp(stable), _dp(feet),
+                                                          _stream(quats)))
+    return margin, edge, stable, feet
+
+
 class PoseSet:
     """A pose table for batched multi-pose queries (lrm_pose_compile_dev / lrm_reach_dist_posed_dev).
 
@@ -360,7 +418,8 @@ class PoseSet:
     foothold_support() turns the question round: per target and leg, how many poses reach it and which does it best;
     body_clearance() asks whether the trunk itself fits: terrain inside the body cylinder, the worst point and the lift;
     leg_clearance() (with ik=True) asks the same of the legs under ik()'s angles: terrain inside the coxa, femur and tibia
-    links, and leg_joints() returns the joints it tests."""
+    links, and leg_joints() returns the joints it tests; stance_stability() asks whether the chosen footholds carry the
+    centre of mass, and which legs can be lifted."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -681,6 +740,24 @@ class PoseSet:
                                                                   minus_z, floor_z, _dp(live_in), _dp(hits), _dp(top), _dp(height),
                                                                   _dp(free), _stream(self.workspace)))
         return hits, top, height, free
+
+    def stance_stability(self, tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None, plane=None, lift=None, min_margin=0.0,
+                         live_in=None, margin=None, edge=None, stable=None, feet=None):
+        """device.stance_stability() on this set's poses: quats (and body) are the tensors of the last update() -- the set keeps
+        compiled records, not the poses -- so their pose count must be the set's, foot is [nlegs, nstances] with the set's
+        legs, and everything lives on the set's device.  foot = footholds()'s best (a stance per pose), or foothold_edges()'s
+        best with pose_idx = edge_a or edge_b.  -> (margin, edge, stable [nmasks, nstances]; feet [nstances]); stable[0] is
+        body_clearance()'s live_in.  It only launches: update -> footholds -> stance_stability can be captured in a graph."""
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if quats.dim() != 2 or quats.shape[0] != self.nposes:
+            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
+        if quats.device != self.workspace.device:
+            raise ValueError("quats and poses must live on one device")
+        if foot.dim() != 2 or foot.shape[0] != self.nlegs:
+            raise ValueError(f"foot: expected an int32 tensor of shape ({self.nlegs}, nstances)")
+        return stance_stability(tx, ty, tz, foot, quats, body, pose_idx, com, plane, lift, min_margin, live_in, margin, edge, stable,
+                                feet)
 
     def _check_angles(self, angles):
         torch = _torch()
