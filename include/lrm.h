@@ -802,6 +802,73 @@ int lrm_stance_stability_cpu(const float* targets_aos, size_t nt, const float* q
                              const float* com, const float* plane, const uint8_t* lift, size_t nmasks, float min_margin,
                              const uint8_t* live_in /* host, may be NULL */, float* margin_out, uint8_t* edge_out,
                              uint8_t* stable_out, uint8_t* feet_out, double* ms);
+/* LEG-LEG SELF CLEARANCE per set: do the legs fit next to each other.  lrm_footholds_posed_dev chooses per leg and
+ * lrm_ik_posed_dev solves per leg, so nothing stops two legs from crossing or from choosing the same point;
+ * lrm_body_clearance_posed_dev and lrm_leg_clearance_posed_dev test trunk and legs against the TERRAIN only.  This call tests the
+ * links of every two DIFFERENT legs against each other (trunk against leg links is out of scope).  The reference has no such
+ * query.  It reads no cloud and no new table: `workspace` and `ik_workspace` are the pose table and the IK table of
+ * lrm_leg_clearance_posed_dev; the body position is not read (both legs are relative to the same body).
+ * A SET s (of nsets) is a pose p = pose_idx[s] (int32; pose_idx == NULL: p = s) and three angles per leg at [l*nsets + s]:
+ * lrm_ik_posed_dev's output under footholds_layout (a set per pose), or under foothold_edges_layout with pose_idx = edge_a or
+ * edge_b -- the form lrm_stance_stability_dev takes.  radius[3] (host), margin and tip_clear are lrm_leg_clearance_posed_dev's.
+ * Everything is float32 without contraction, only + - * /, comparisons, the correctly rounded square root and the sincos of the
+ * IK: device and host give the same bits (csrc/lrm_self_clearance.h is the one source of both).
+ * Joints: J0..J3 of (p, l) are lrm_leg_clearance_posed_dev's, tip_clear included.  A leg is VALID iff its twelve coordinates
+ *   are finite.  An invalid leg takes part in no pair, gets the empty answer and does not block free_out.
+ * Pairs: for legs i < j, both valid, and links ka, kb in 0..2 with radius[ka] != 0 and radius[kb] != 0: segment 1 is link ka
+ *   of the leg with the SMALLER index, A1 = J_i[ka], B1 = J_i[ka+1]; segment 2 is A2 = J_j[kb], B2 = J_j[kb+1].  Both legs read
+ *   the same d of a pair; it is computed once, in this order.
+ * Distance, with dot(u, v) = (u.x v.x + u.y v.y) + u.z v.z and clamp01(x) = !(x > 0) ? 0 : (x > 1 ? 1 : x):
+ *   d1 = B1 - A1; d2 = B2 - A2; r = A1 - A2; a = dot(d1,d1); e = dot(d2,d2); f = dot(d2,r); c = dot(d1,r); b = dot(d1,d2);
+ *   if !(a > 0) && !(e > 0): s = t = 0;
+ *   else if !(a > 0): s = 0; t = clamp01(f / e);
+ *   else if !(e > 0): t = 0; s = clamp01(-c / a);
+ *   else: den = a*e - b*b; s = den > 0 ? clamp01((b*f - c*e) / den) : 0; tn = b*s + f;
+ *         if !(tn > 0): t = 0; s = clamp01(-c / a);  else if tn > e: t = 1; s = clamp01((b - c) / a);  else: t = tn / e;
+ *   w = (r + s*d1) - t*d2 per component; d = sqrt(dot(w, w));
+ *   then, in this order, the four endpoint distances of lrm_leg_clearance_posed_dev's point-to-link formula (ab the link's
+ *   B - A, den = dot(ab, ab)) are folded in: A1 and B1 against segment 2, then A2 and B2 against segment 1, each by
+ *   d = dk < d ? dk : d.  Every candidate is a distance between two points of the segments, so d never under-reports; the
+ *   fold bounds what the clamped step alone over-reports on nearly parallel links (measured: DESIGN.md 3.20).
+ * Per pair: rr = radius[ka] + radius[kb]; hit = d < rr; near = d < rr + margin (the nine sums rr + margin formed once per
+ *   call); pen = (rr - d) + 0.  A nan d is neither near nor hit.
+ * Outputs per (set, leg) at [l*nsets + s], all written:
+ *   hits_out  (int32) the number of pairs with a hit in which leg l is one of the two legs;
+ *   with_out  (uint8) bit j set iff some link of l hits some link of leg j;
+ *   links_out (uint8) bit k set iff link k of leg l is in a hit;
+ *   worst_out (uint8) the near pair of leg l with the largest pen, as code j*9 + own_link*3 + other_link (j the other leg),
+ *             ties to the smaller code; 255 when none is near;
+ *   pen_out   (float, may be NULL) that pen, -inf when none;
+ * and free_out[s] (uint8, nsets, may be NULL): 1 iff the set is live and no leg has a hit.
+ * A DEAD set -- live_in[s] == 0 (uint8, nsets, device for _dev and host for _cpu, may be NULL), or p outside [0, nposes) --
+ * gets 0 / 0 / 0 / 255 / -inf and free 0; it touches no table and no angle.
+ * Consequences: with[i] has bit j set iff with[j] has bit i set; the sum of hits over the legs of a set is even; pen > 0 iff
+ * hits > 0 iff with != 0 iff links != 0; with margin == 0 worst is a hit or 255; with nlegs == 1 everything is empty and
+ * free = live; free_out is directly a live_in / pose_live of the other posed calls:
+ * ... -> ik -> self_clearance -> leg_clearance(live_in = free).
+ * Checked first, in lrm_leg_clearance_posed_dev's order and by its rules (all LRM_EINVAL): nlegs outside 1..LRM_MAX_LEGS; nsets
+ * or nposes > INT32_MAX, or nlegs * nsets past 2^32 - 1; a radius, margin or tip_clear that is nan, negative or infinite (NULL
+ * radius too); pose_idx == NULL with nsets > nposes.  Then nsets == 0 is a no-op; a NULL table, angle array, hits_out,
+ * with_out, links_out or worst_out gives LRM_EINVAL.
+ * lrm_self_clearance_posed_dev: ONE launch, a wave per set: no allocation, no host synchronisation, no atomics, no shared
+ * buffer -- it can be captured in a graph and may run concurrently with anything, the pair kernels included, from any host
+ * thread.  Bit-deterministic.
+ * lrm_self_clearance_posed_cpu: host quats (nposes x 4), legs and angles_aos (nlegs * nsets triples {coxa, femur, tibia} at
+ * [l*nsets + s]: lrm_ik_posed_cpu's output in that layout), host pose_idx and live_in; it compiles its own tables and runs a
+ * serial loop over every (set, pair) with the same functions: the reference the GPU tests compare with bit for bit; *ms =
+ * the loop's time. */
+int lrm_self_clearance_posed_dev(const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs,
+                                 const int32_t* pose_idx /* device, nsets, may be NULL */, size_t nsets,
+                                 const float* coxa, const float* femur, const float* tibia /* device, nlegs*nsets at [l*nsets + s] */,
+                                 const float radius[3] /* host */, float margin, float tip_clear,
+                                 const uint8_t* live_in /* device, nsets, may be NULL */,
+                                 int32_t* hits_out, uint8_t* with_out, uint8_t* links_out, uint8_t* worst_out,
+                                 float* pen_out /* may be NULL */, uint8_t* free_out /* nsets, may be NULL */, void* stream);
+int lrm_self_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                 const int32_t* pose_idx /* host, may be NULL */, size_t nsets, const float* angles_aos,
+                                 const float radius[3], float margin, float tip_clear,
+                                 const uint8_t* live_in /* host, may be NULL */, int32_t* hits_out, uint8_t* with_out,
+                                 uint8_t* links_out, uint8_t* worst_out, float* pen_out, uint8_t* free_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a
@@ -926,6 +993,11 @@ void lrm_multi_release(void);
 int lrm_dbg_exact_math_host(const float* a, const float* b, size_t n, float* at2, float* sn, float* cs);
 int lrm_dbg_exact_math_dev(const float* a, const float* b, size_t n, float* at2, float* sn, float* cs,
                            void* stream);
+/* The link-pair distance of lrm_self_clearance_posed_dev (csrc/lrm_self_clearance.h) on n hand-made segment pairs: segs holds
+ * 12 floats per pair, A1, B1, A2, B2 as x, y, z; out[i] = d of pair i.  Host build and device build (one pair per lane); the
+ * tests hold the branchy distance to the text above on them. */
+int lrm_dbg_link_pair_dist_host(const float* segs, size_t n, float* out);
+int lrm_dbg_link_pair_dist_dev(const float* segs, size_t n, float* out, void* stream);
 /* The device's correctly rounded square root (csrc/lrm_exact_math.h, lrm_sqrtf) against the
  * compiler's IEEE sqrtf on ALL 2^32 float bit patterns: writes the number of patterns whose results
  * differ bitwise (nan payloads included) and the first such pattern.  Synchronous. */

@@ -141,12 +141,16 @@ def load():
         "lrm_leg_joints_posed_cpu": [vp, vp, vp, sz, vp, sz, fp, vp, vp],
         "lrm_stance_stability_dev": [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
         "lrm_stance_stability_cpu": [vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
+        "lrm_self_clearance_posed_dev": [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_self_clearance_posed_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_dbg_link_pair_dist_host": [vp, sz, vp],
+        "lrm_dbg_link_pair_dist_dev": [vp, sz, vp, vp],
     }
     for name, argtypes in sig.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
@@ -744,6 +748,55 @@ def stance_stability_cpu(targets, foot, quats, body=None, pose_idx=None, com=Non
                                           _ptr(com), _ptr(plane), _ptr(lift), nm, float(min_margin), _ptr(live_in), _ptr(margin),
                                           _ptr(edge), _ptr(stable), _ptr(feet), C.addressof(ms)))
     return margin, edge, stable, feet, ms.value
+
+
+def self_clearance_posed_cpu(quats, legs, angles, radius, margin=0.0, tip_clear=0.0, pose_idx=None, live_in=None, want_pen=True,
+                             want_free=True):
+    """lrm_self_clearance_posed_cpu: do the legs fit next to each other.  A set s is a pose (pose_idx[s], or pose s with
+    pose_idx None) and one (coxa, femur, tibia) triple per leg, angles float32 [nlegs*nsets, 3] at [l*nsets + s]:
+    apply_ik_posed_cpu's output under the [l*nposes + p] layout.  Every link of a leg (capsules of radius[k] about coxa,
+    femur, tibia, the tibia ending tip_clear short of the foot; radius 0 = not tested) is tested against every link of every
+    OTHER leg: per (leg, set) the number of link pairs that hit, the bit mask of the legs hit, the bit mask of the own links
+    in a hit, the pair within margin that stands deepest as code other*9 + own_link*3 + other_link (255 if none) and its
+    pen = radius sum - distance (-inf if none); per set whether it is live and no leg is hit.  live_in: uint8[nsets] or None;
+    0 = dead, as is a pose index outside the poses.  Serial host loop over every (set, pair); want_* False pass NULL.
+    -> (hits int32, with_ uint8, links uint8, worst uint8, pen float32 or None, each [nlegs, nsets]; free uint8[nsets] or
+    None; ms)"""
+    quats = _f32(quats, (-1, 4))
+    legs = _f32(legs, (-1, 14))
+    n, nl = len(quats), len(legs)
+    angles = _f32(angles)
+    if nl == 0 or angles.size % (3 * nl):
+        raise ValueError("angles: one (coxa, femur, tibia) triple per (leg, set), at [l*nsets + s]")
+    ns = angles.size // (3 * nl)
+    angles = angles.reshape(nl * ns, 3)
+    radius = _f32(radius, (3,))
+    if pose_idx is not None:
+        pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
+        if len(pose_idx) != ns:
+            raise ValueError("pose_idx: one pose per set")
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != ns:
+            raise ValueError("live_in: one byte per set")
+    hits = np.zeros((nl, ns), np.int32)
+    with_, links, worst = (np.zeros((nl, ns), np.uint8) for _ in range(3))
+    pen = np.zeros((nl, ns), np.float32) if want_pen else None
+    free = np.zeros(ns, np.uint8) if want_free else None
+    ms = C.c_double(0)
+    check(load().lrm_self_clearance_posed_cpu(_ptr(quats), n, _ptr(legs), nl, _ptr(pose_idx), ns, _ptr(angles), _ptr(radius),
+                                              float(margin), float(tip_clear), _ptr(live_in), _ptr(hits), _ptr(with_), _ptr(links),
+                                              _ptr(worst), _ptr(pen), _ptr(free), C.addressof(ms)))
+    return hits, with_, links, worst, pen, free, ms.value
+
+
+def dbg_link_pair_dist_host(segs):
+    """lrm_dbg_link_pair_dist_host: the link-pair distance of the self clearance calls on hand-made segment pairs, segs
+    float32 [n, 12] = A1, B1, A2, B2 -> float32[n]"""
+    segs = _f32(segs, (-1, 12))
+    out = np.zeros(len(segs), np.float32)
+    check(load().lrm_dbg_link_pair_dist_host(_ptr(segs), len(segs), _ptr(out)))
+    return out
 
 
 def apply_rbdl_equiv(xyz, leg):

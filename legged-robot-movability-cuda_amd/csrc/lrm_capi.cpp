@@ -23,6 +23,7 @@
 #include "lrm_body_clearance.h"
 #include "lrm_leg_clearance.h"
 #include "lrm_stance.h"
+#include "lrm_self_clearance.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -1887,18 +1888,23 @@ int leg_scalar_ok(float v, const char* what) { // >= 0 and finite
     if (v < 0.f || !(v < INFINITY)) return fail(LRM_EINVAL, what);
     return LRM_OK;
 }
-// lrm_footholds_posed_dev's range checks, then the scalars', before any early return
-int leg_clearance_args(size_t nt, size_t nposes, size_t nlegs, const float* radius, float margin, float tip_clear) {
-    int rc = footholds_posed_args(nt, nposes, nlegs);
-    if (rc != LRM_OK) return rc;
+// the capsule scalars of the leg clearance and the self clearance calls: a radius array, every radius, margin and tip_clear
+// >= 0 and finite; a nan anywhere is reported first
+int leg_capsule_args(const float* radius, float margin, float tip_clear) {
     if (!radius) return fail(LRM_EINVAL, "null argument");
     for (int k = 0; k < 3; k++)
         if (radius[k] != radius[k]) return fail(LRM_EINVAL, "leg clearance: nan scalar");
     if (margin != margin || tip_clear != tip_clear) return fail(LRM_EINVAL, "leg clearance: nan scalar");
+    int rc = LRM_OK;
     for (int k = 0; k < 3 && rc == LRM_OK; k++) rc = leg_scalar_ok(radius[k], "leg clearance: every radius must be >= 0 and finite");
     if (rc == LRM_OK) rc = leg_scalar_ok(margin, "leg clearance: margin must be >= 0 and finite");
     if (rc == LRM_OK) rc = leg_scalar_ok(tip_clear, "leg clearance: tip_clear must be >= 0 and finite");
     return rc;
+}
+// lrm_footholds_posed_dev's range checks, then the scalars', before any early return
+int leg_clearance_args(size_t nt, size_t nposes, size_t nlegs, const float* radius, float margin, float tip_clear) {
+    const int rc = footholds_posed_args(nt, nposes, nlegs);
+    return rc != LRM_OK ? rc : leg_capsule_args(radius, margin, tip_clear);
 }
 } // namespace
 
@@ -2126,6 +2132,110 @@ int lrm_stance_stability_cpu(const float* targets, size_t nt, const float* quats
         }
         if (feet_out) feet_out[s] = (uint8_t)feet;
     }
+    return LRM_OK;
+}
+
+// ---- leg-leg self clearance per set: link pairs of different legs (lrm_self_clearance.hip) -----------
+namespace {
+// leg_clearance_args' order and rules without the cloud: the ranges, the scalars, then the set-to-pose rule
+int self_clearance_args(size_t nposes, size_t nlegs, const int32_t* pose_idx, size_t nsets, const float* radius, float margin,
+                        float tip_clear) {
+    if (nlegs == 0 || nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "nlegs must be 1..LRM_MAX_LEGS");
+    if (nposes > (size_t)INT32_MAX || nsets > (size_t)INT32_MAX)
+        return fail(LRM_EINVAL, "self clearance: nposes and nsets must not exceed INT32_MAX");
+    if ((uint64_t)nlegs * (uint64_t)nsets > 0xffffffffull) return fail(LRM_EINVAL, "self clearance: more than 2^32 - 1 (set, leg) answers");
+    const int rc = leg_capsule_args(radius, margin, tip_clear); // the capsules are lrm_leg_clearance_posed_dev's: one check, its messages
+    if (rc != LRM_OK) return rc;
+    if (!pose_idx && nsets > nposes) return fail(LRM_EINVAL, "self clearance: without pose_idx, set s takes pose s: nsets <= nposes");
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_self_clearance_posed_dev(const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs, const int32_t* pose_idx,
+                                 size_t nsets, const float* coxa, const float* femur, const float* tibia, const float radius[3],
+                                 float margin, float tip_clear, const uint8_t* live_in, int32_t* hits_out, uint8_t* with_out,
+                                 uint8_t* links_out, uint8_t* worst_out, float* pen_out, uint8_t* free_out, void* stream) {
+    const int rc = self_clearance_args(nposes, nlegs, pose_idx, nsets, radius, margin, tip_clear);
+    if (rc != LRM_OK) return rc;
+    if (nsets == 0) return LRM_OK;
+    if (!workspace || !ik_workspace || !coxa || !femur || !tibia || !hits_out || !with_out || !links_out || !worst_out)
+        return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
+    HIP_TRY(lrm_launch_self_clearance_posed(workspace, ik_workspace, nposes, nlegs, pose_idx, nsets, coxa, femur, tibia, radius, margin,
+                                            tip_clear, live_in, hits_out, with_out, links_out, worst_out, pen_out, free_out,
+                                            (hipStream_t)stream),
+            "posed self clearance launch");
+    return LRM_OK;
+}
+
+int lrm_self_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* pose_idx,
+                                 size_t nsets, const float* angles, const float radius[3], float margin, float tip_clear,
+                                 const uint8_t* live_in, int32_t* hits_out, uint8_t* with_out, uint8_t* links_out, uint8_t* worst_out,
+                                 float* pen_out, uint8_t* free_out, double* ms) {
+    const int rc = self_clearance_args(nposes, nlegs, pose_idx, nsets, radius, margin, tip_clear);
+    if (rc != LRM_OK) return rc;
+    if (nsets == 0) return LRM_OK;
+    if (!legs || (nposes && !quats) || !angles || !hits_out || !with_out || !links_out || !worst_out) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, nullptr, nposes, legs, nlegs, recs.data()); // the body position is not read
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const LrmSelfRadii R = lrm_self_radii(radius, margin);
+    const uint32_t npairs = lrm_self_npairs((uint32_t)nlegs);
+    const ScopeMs timer{ms};
+    for (size_t s = 0; s < nsets; s++) {
+        const int64_t p = pose_idx ? (int64_t)pose_idx[s] : (int64_t)s;
+        const bool live = !(live_in && !live_in[s]) && p >= 0 && (uint64_t)p < nposes;
+        LrmVec3 J[LRM_MAX_LEGS][4];
+        uint32_t legs_ok = 0u;
+        for (size_t l = 0; live && l < nlegs; l++) { // the joints once per (set, leg)
+            const size_t o = l * nsets + s;
+            lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(recs[p * nlegs + l].head), iks[p * nlegs + l], angles[3 * o],
+                           angles[3 * o + 1], angles[3 * o + 2], tip_clear, J[l]);
+            if (lrm_leg_joints_finite(J[l])) legs_ok |= 1u << l;
+        }
+        LrmSelfLeg A[LRM_MAX_LEGS];
+        for (size_t l = 0; l < nlegs; l++) A[l] = lrm_self_leg_empty();
+        for (uint32_t code = 0; live && code < npairs; code++) { // every pair once; both legs read the same d
+            const uint32_t pk = lrm_self_pair_of(code);
+            const uint32_t i = lrm_self_pair_i(pk), j = lrm_self_pair_j(pk), ka = lrm_self_pair_ka(pk), kb = lrm_self_pair_kb(pk);
+            if (!((legs_ok >> i) & 1u) || !((legs_ok >> j) & 1u) || !((R.tested >> (ka * 3u + kb)) & 1u)) continue;
+            const float d = lrm_self_pair_dist(J[i][ka], J[i][ka + 1], J[j][kb], J[j][kb + 1]);
+            float pen = 0.f;
+            const unsigned bits = lrm_self_clearance_test(d, R.rr[ka * 3u + kb], R.reach[ka * 3u + kb], &pen);
+            if (!bits) continue;
+            lrm_self_leg_take(&A[i], i, pk, bits, pen);
+            lrm_self_leg_take(&A[j], j, pk, bits, pen);
+        }
+        bool set_free = live;
+        for (size_t l = 0; l < nlegs; l++) {
+            const size_t o = l * nsets + s;
+            const LrmSelfWorst W = lrm_self_key_decode(A[l].key);
+            hits_out[o] = A[l].hits;
+            with_out[o] = (uint8_t)A[l].with;
+            links_out[o] = (uint8_t)A[l].links;
+            worst_out[o] = W.code;
+            if (pen_out) pen_out[o] = W.pen;
+            set_free = set_free && A[l].hits == 0;
+        }
+        if (free_out) free_out[s] = set_free;
+    }
+    return LRM_OK;
+}
+
+// ---- diagnostics: lrm_self_clearance.h's pair distance on arrays (host build / device build) -----------
+int lrm_dbg_link_pair_dist_host(const float* segs, size_t n, float* out) {
+    if (n && (!segs || !out)) return fail(LRM_EINVAL, "null argument");
+    for (size_t i = 0; i < n; i++) {
+        const float* g = segs + 12 * i;
+        out[i] = lrm_self_pair_dist(LrmVec3{g[0], g[1], g[2]}, LrmVec3{g[3], g[4], g[5]}, LrmVec3{g[6], g[7], g[8]}, LrmVec3{g[9], g[10], g[11]});
+    }
+    return LRM_OK;
+}
+int lrm_dbg_link_pair_dist_dev(const float* segs, size_t n, float* out, void* stream) {
+    if (n && (!segs || !out)) return fail(LRM_EINVAL, "null argument");
+    if (n == 0) return LRM_OK;
+    HIP_TRY(lrm_launch_link_pair_dist(segs, n, out, (hipStream_t)stream), "link pair distance launch");
     return LRM_OK;
 }
 

@@ -401,6 +401,21 @@ def stance_stability(tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None
     return margin, edge, stable, feet
 
 
+def dbg_link_pair_dist(segs, out=None):
+    """lrm_dbg_link_pair_dist_dev: the link-pair distance of self_clearance() on segment pairs, segs float32 (n, 12) =
+    A1, B1, A2, B2 on the device -> float32 (n,); one pair per lane."""
+    torch = _torch()
+    if not (segs.is_cuda and segs.dtype == torch.float32 and segs.dim() == 2 and segs.shape[1] == 12 and segs.is_contiguous()):
+        raise ValueError("segs: expected a contiguous float32 CUDA tensor of shape (n, 12)")
+    n = segs.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=segs.device)
+    _check_out(out, segs, torch.float32, n, "distances")
+    with torch.cuda.device(segs.device):
+        _capi.check(_capi.load().lrm_dbg_link_pair_dist_dev(_dp(segs), n, _dp(out), _stream(segs)))
+    return out
+
+
 class PoseSet:
     """A pose table for batched multi-pose queries (lrm_pose_compile_dev / lrm_reach_dist_posed_dev).
 
@@ -419,7 +434,8 @@ class PoseSet:
     body_clearance() asks whether the trunk itself fits: terrain inside the body cylinder, the worst point and the lift;
     leg_clearance() (with ik=True) asks the same of the legs under ik()'s angles: terrain inside the coxa, femur and tibia
     links, and leg_joints() returns the joints it tests; stance_stability() asks whether the chosen footholds carry the
-    centre of mass, and which legs can be lifted."""
+    centre of mass, and which legs can be lifted; self_clearance() (with ik=True) asks whether the legs fit next to each
+    other under ik()'s angles: links of different legs against each other."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -816,6 +832,67 @@ class PoseSet:
                                                                  float(tip_clear), _dp(live_in), _dp(hits), _dp(links), _dp(worst),
                                                                  _dp(pen), _dp(free), _stream(self.workspace)))
         return hits, links, worst, pen, free
+
+    def self_clearance(self, angles, radius, margin=0.0, tip_clear=0.0, pose_idx=None, live_in=None, hits=None, with_=None, links=None,
+                       worst=None, pen=None, free=None):
+        """lrm_self_clearance_posed_dev: do the legs fit next to each other under the given joint angles.  A set s is a pose
+        (pose_idx[s], int32 on the device; None: pose s) and one angle triple per leg: angles is ik()'s (3, nlegs*nsets)
+        tensor, entry l*nsets + s -- under footholds_layout a set per pose, under foothold_edges_layout a set per edge
+        with pose_idx = edge_a or edge_b.  radius, margin and tip_clear are leg_clearance()'s.  Every link of a leg is tested
+        against every link of every OTHER leg: hits[l, s] = the link pairs that hit; with_[l, s] = bit j set iff leg j is hit;
+        links[l, s] = bit k set iff the own link k is in a hit; worst[l, s] = the pair within margin that stands deepest, as
+        code j*9 + own_link*3 + other_link (255 if none); pen[l, s] = its radius sum - distance (-inf if none); free[s] = 1 iff
+        the set is live and no leg is hit.  A leg with nan angles takes part in no pair and does not block free.  live_in: uint8
+        [nsets] on the device, 0 = dead (0, 0, 0, 255, -inf, free 0), as is a pose index outside the set's poses.
+        -> (hits int32, with_ uint8, links uint8, worst uint8, pen float32, each [nlegs, nsets]; free uint8[nsets]); free is
+        leg_clearance()'s live_in.  pose_idx, live_in and given outputs must be contiguous.  One launch, no allocation beyond
+        missing outputs, no shared buffer: update -> footholds -> ik -> self_clearance -> leg_clearance can be captured in a
+        graph, and the call may run next to anything."""
+        torch = _torch()
+        if self.ik_workspace is None:
+            raise ValueError("PoseSet: built without ik=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
+                and angles.shape[0] == 3 and angles.shape[1] % self.nlegs == 0 and angles.is_contiguous()):
+            raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {self.nlegs} * nsets) tensor on {self.workspace.device}")
+        ns = angles.shape[1] // self.nlegs
+        n = self.nlegs * ns
+        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if len(radius) != 3:
+            raise ValueError("radius: three values (coxa, femur, tibia link)")
+        _check_out(pose_idx, self.workspace, torch.int32, ns, "pose_idx")
+        _check_out(live_in, self.workspace, torch.uint8, ns, "live_in")
+        if pose_idx is not None and pose_idx.numel() != ns or live_in is not None and live_in.numel() != ns:
+            raise ValueError("pose_idx / live_in: one entry per set")
+        if pose_idx is None and ns > self.nposes:
+            raise ValueError("without pose_idx set s takes pose s: nsets <= nposes")
+        shape = (self.nlegs, ns)
+        if hits is None:
+            hits = torch.empty(shape, dtype=torch.int32, device=self.device)
+        if with_ is None:
+            with_ = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if links is None:
+            links = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if worst is None:
+            worst = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if pen is None:
+            pen = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if free is None:
+            free = torch.empty(ns, dtype=torch.uint8, device=self.device)
+        _check_out(hits, self.workspace, torch.int32, n, "per-leg hit counts")
+        _check_out(with_, self.workspace, torch.uint8, n, "per-leg leg masks")
+        _check_out(links, self.workspace, torch.uint8, n, "per-leg link masks")
+        _check_out(worst, self.workspace, torch.uint8, n, "per-leg worst pairs")
+        _check_out(pen, self.workspace, torch.float32, n, "per-leg penetrations")
+        _check_out(free, self.workspace, torch.uint8, ns, "per-set free bytes")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_self_clearance_posed_dev(_dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
+                                                                  _dp(pose_idx), ns, _dp(angles[0]), _dp(angles[1]), _dp(angles[2]),
+                                                                  _capi._ptr(radius), float(margin), float(tip_clear), _dp(live_in),
+                                                                  _dp(hits), _dp(with_), _dp(links), _dp(worst), _dp(pen), _dp(free),
+                                                                  _stream(self.workspace)))
+        return hits, with_, links, worst, pen, free
 
     def leg_joints(self, angles, tip_clear=0.0, out=None):
         """lrm_leg_joints_posed_dev: the four joints of every (leg, pose) under angles (ik()'s (3, nlegs*nposes) tensor under
