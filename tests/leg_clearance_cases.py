@@ -7,7 +7,9 @@ operation, written from that text and not from csrc/lrm_leg_clearance.h.
 brute_np does not restate the joint chain: it takes the joints from lrm_fk_posed_cpu (an older call with tests of its
 own) on legs whose link lengths are zeroed or shortened, with a zero body -- the identities the joint tests assert of
 lrm_leg_joints_posed_cpu bit for bit (J3 = the tip with tibia_length T', J2 with tibia_length 0, J1 with femur and tibia 0,
-J0 with all three 0)."""
+J0 with all three 0).  The joints here therefore come from the library's own FK; that they are where a leg of these dimensions
+has them, and that d is the distance to a link, is checked against the independent float64 model of tests/leg_model64.py in
+tests/test_clearance_float64_cpu.py."""
 import numpy as np
 
 import footholds_posed_cases as fc
@@ -95,7 +97,8 @@ def joints_from_fk(lrm, angles, quats, body, legs, tip_clear):
 def brute_np(targets, body, joints, radius, margin, live_in=None, detail=False):
     """joints: float32[nlegs, nposes, 4, 3] RELATIVE to the body.  -> dict(hits, links, worst, pen [nlegs, nposes], free
     [nposes]); detail=True adds valid [nlegs, nposes] and near_any [nlegs, nposes] (some target near some link) and, per
-    (leg, pose), the hit mask over the targets in "hit" [nlegs, nposes, nt]"""
+    (leg, pose), the hit mask over the targets in "hit" [nlegs, nposes, nt] and the float32 distance of every decision in "d"
+    [nlegs, nposes, 3, nt] (inf where none was computed: a dead pose, an invalid leg, a link with radius 0)"""
     targets = np.ascontiguousarray(targets, F).reshape(-1, 3)
     nl, n = joints.shape[:2]
     nt = len(targets)
@@ -106,6 +109,7 @@ def brute_np(targets, body, joints, radius, margin, live_in=None, detail=False):
     free = np.zeros(n, np.uint8)
     valid, near_any = np.zeros((nl, n), bool), np.zeros((nl, n), bool)
     hitm = np.zeros((nl, n, nt), bool) if detail else None
+    dm = np.full((nl, n, 3, nt), np.inf, F) if detail else None
     zero, one = F(0), F(1)
     with np.errstate(all="ignore"):
         for p in range(n):
@@ -133,6 +137,8 @@ def brute_np(targets, body, joints, radius, margin, live_in=None, detail=False):
                     s = np.where(~(s > zero), zero, np.where(s > one, one, s)).astype(F)
                     e = (ap - (s[:, None] * ab).astype(F)).astype(F)
                     d = np.sqrt((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]).astype(F)
+                    if detail:
+                        dm[l, p, k] = d
                     hk, nk = d < radius[k], d < reach[k]
                     pk = ((radius[k] - d) + zero).astype(F)
                     best = np.where(nk & (~near | (pk > best)), pk, best)
@@ -152,7 +158,7 @@ def brute_np(targets, body, joints, radius, margin, live_in=None, detail=False):
             free[p] = int((hits[:, p] == 0).all())
     out = {"hits": hits, "links": links, "worst": worst, "pen": pen, "free": free}
     if detail:
-        out.update(valid=valid, near_any=near_any, hit=hitm)
+        out.update(valid=valid, near_any=near_any, hit=hitm, d=dm)
     return out
 
 

@@ -4,7 +4,9 @@ rounding per operation in float32 and the same formulas in float64, written from
 csrc/lrm_self_clearance.h; hand-made and random segment pairs; and brute_np, the per-(set, leg) answers from that distance.
 
 brute_np does not restate the joint chain: it takes RELATIVE joints from leg_clearance_cases.joints_from_fk (lrm_fk_posed_cpu
-on shortened legs, body None), one pose per set."""
+on shortened legs, body None), one pose per set.  The joints here therefore come from the library's own FK, and pair_dist_np
+restates the contract's formulas; the independent check -- joints from the leg's geometry and the true minimum distance between
+two segments, in float64 -- lives in tests/leg_model64.py and tests/test_clearance_float64_cpu.py."""
 import numpy as np
 
 import leg_clearance_cases as lc

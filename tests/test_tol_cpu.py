@@ -128,8 +128,8 @@ def test_second_candidate_is_rarely_evaluated(lrm):
 
 def test_plane_table_does_not_depend_on_the_builder_threads(lrm, monkeypatch):
     """the table's rows are classified on several host threads and numbered afterwards, serially: one thread or eight, the
-    same table (same statistics, same answers, same doubt bits).  (The builder is also clean under -fsanitize=thread and
-    -fsanitize=address,undefined on the CPU build.)"""
+    same table (same statistics, same answers, same doubt bits).  (tests/test_host_sanitize_cpu.py runs the builder under
+    -fsanitize=thread and -fsanitize=address,undefined in a stand-alone program.)"""
     pts = random_cloud(50_000, seed=5)
     leg = lrm.get_M2_leg(0.9)
     q = QUATS[2]
