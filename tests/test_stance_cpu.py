@@ -8,6 +8,7 @@ import pytest
 
 import pair_cases as pc
 import stance_cases as sc
+import stance_model64 as sm
 
 F = np.float32
 EINVAL = -1  # LRM_EINVAL
@@ -222,9 +223,10 @@ def test_every_einval(lrm):
 
 
 def test_agreement_with_the_float64_hull(lrm, main):
-    """|margin - margin64| <= 1e-2 mm wherever both are finite and the relative coordinates stay below 2000 mm (the arithmetic's
-    error is about 4 eps |c - a|, some 5e-4 mm here); stable agrees wherever margin64 is further than that from min_margin;
-    -inf answers agree exactly.  Nothing is left out: the cap of 1 % is not used."""
+    """|margin - margin64| <= stance_model64.BAND["main"] (3e-4 mm: four times the worst that tests/test_stance_float64_cpu.py
+    measures on this scene against the independent model, itself a wider comparison than this one, whose hull takes the restated
+    float32 plane points) wherever both are finite and the relative coordinates stay below 2000 mm; stable agrees wherever
+    margin64 is further than that from min_margin; -inf answers agree exactly.  Nothing is left out: the cap of 1 % is not used."""
     targets, foot, quats, body, legs = main
     lift = sc.lift_each(6)
     for min_margin in (0.0, 25.0):
@@ -235,7 +237,7 @@ def test_agreement_with_the_float64_hull(lrm, main):
         fin = np.isfinite(m64)
         assert np.isfinite(got["margin"][fin]).all() and fin.mean() > 0.5
         diff = np.abs(got["margin"][fin].astype(np.float64) - m64[fin])
-        print(f"worst |margin - margin64| = {diff.max():.3e} mm over {int(fin.sum())} answers")
-        assert diff.max() <= 1e-2
-        clear = np.abs(m64 - min_margin) > 1e-2
+        print(f"worst |margin - margin64| = {diff.max():.3e} mm over {int(fin.sum())} answers (band {sm.BAND['main']:g})")
+        assert diff.max() <= sm.BAND["main"]
+        clear = np.abs(m64 - min_margin) > sm.BAND["main"]
         assert np.array_equal(got["stable"][clear], (m64 > min_margin)[clear].astype(np.uint8))
