@@ -805,7 +805,7 @@ int lrm_stance_stability_cpu(const float* targets_aos, size_t nt, const float* q
 /* LEG-LEG SELF CLEARANCE per set: do the legs fit next to each other.  lrm_footholds_posed_dev chooses per leg and
  * lrm_ik_posed_dev solves per leg, so nothing stops two legs from crossing or from choosing the same point;
  * lrm_body_clearance_posed_dev and lrm_leg_clearance_posed_dev test trunk and legs against the TERRAIN only.  This call tests the
- * links of every two DIFFERENT legs against each other (trunk against leg links is out of scope).  The reference has no such
+ * links of every two DIFFERENT legs against each other (trunk against leg links: lrm_trunk_clearance_posed_dev).  The reference has no such
  * query.  It reads no cloud and no new table: `workspace` and `ik_workspace` are the pose table and the IK table of
  * lrm_leg_clearance_posed_dev; the body position is not read (both legs are relative to the same body).
  * A SET s (of nsets) is a pose p = pose_idx[s] (int32; pose_idx == NULL: p = s) and three angles per leg at [l*nsets + s]:
@@ -869,6 +869,70 @@ int lrm_self_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLeg
                                  const float radius[3], float margin, float tip_clear,
                                  const uint8_t* live_in /* host, may be NULL */, int32_t* hits_out, uint8_t* with_out,
                                  uint8_t* links_out, uint8_t* worst_out, float* pen_out, uint8_t* free_out, double* ms);
+/* TRUNK-LEG CLEARANCE per set: do the legs stay out of the robot's own trunk.  lrm_ik_posed_dev picks among its candidates by
+ * residual and seed and sends a joint to its limit where a limit is violated; lrm_self_clearance_posed_dev tests leg against
+ * leg and lrm_body_clearance_posed_dev the trunk against the TERRAIN.  This call tests the links of every leg against the trunk
+ * itself: the body cylinder of lrm_body_clearance_posed_dev -- trunk_radius, plus_z, minus_z (float32), BODY frame, axis z,
+ * centred on the body origin; there is no floor_z.  The reference has no such query.  It reads no cloud, no body position
+ * and no new table: `workspace`, `ik_workspace`, nposes, nlegs, pose_idx, nsets, the angles at [l*nsets + s], radius[3] (host),
+ * margin, tip_clear and live_in are lrm_self_clearance_posed_dev's, with the same meaning (a set per pose, or per edge with
+ * pose_idx = edge_a or edge_b).  links (uint8): bit k set = link k (0 coxa, 1 femur, 2 tibia) is tested; the coxa link starts
+ * at the leg's mount on the trunk, so callers usually pass 0b110.  A link with radius[k] == 0 is not tested either.
+ * Everything is float32 without contraction, only + - * /, comparisons, the correctly rounded square root and the sincos of the
+ * IK: device and host give the same bits (csrc/lrm_trunk_clearance.h is the one source of both).
+ * Joints: J0..J3 of (p, l) are lrm_leg_clearance_posed_dev's, relative to the body, tip_clear included.  A leg is VALID iff its
+ *   twelve coordinates are finite.  An invalid leg gets the empty answer and does not block free_out.
+ * Body frame: each joint is taken into the body frame as lrm_body_clearance_posed_dev takes a target: with m = the pose
+ *   record's inv_rot (the coefficient sums of qtInvRotate(quats[p], .)),
+ *   v.x = 2 * ((m[0] J.x + m[1] J.y) + m[2] J.z) + J.x, v.y and v.z likewise with m[3..5] and m[6..8].
+ * Point to cylinder: for a body-frame point P = (x, y, z), with R = trunk_radius:
+ *   rho = sqrt(x*x + y*y); dr = rho > R ? rho - R : 0; dz = z > plus_z ? z - plus_z : (z < minus_z ? minus_z - z : 0);
+ *   h(P) = dr*dr + dz*dz -- the squared distance to the solid cylinder, 0 inside, convex along a segment.
+ *   (Every comparison with a nan is false, so a nan rho or z counts 0 in its term; the joints of a valid leg are finite.)
+ * Link k runs from A = v_k to B = v_(k+1); e = B - A per component; P(u) = A + u*e per component (A.x + u*e.x, ...).
+ *   best = h(A); hB = h(B): best = hB < best ? hB : best; [lo, hi] = [0, 1]; then N = 32 rounds (LRM_TRUNK_ROUNDS) of
+ *     w = (hi - lo) / 3; m1 = lo + w; m2 = hi - w; h1 = h(P(m1)); h2 = h(P(m2));
+ *     best = h1 < best ? h1 : best; best = h2 < best ? h2 : best; if (h1 <= h2) hi = m2; else lo = m1;
+ *   d_k = sqrt(best).  Every candidate is the distance of a point of the link, so d never under-reports; what the search
+ *   over-reports is measured, not assumed.
+ * Per tested link: hit_k = d_k < radius[k]; near_k = d_k < radius[k] + margin (the three sums formed once per call);
+ *   pen_k = (radius[k] - d_k) + 0.  A nan d is neither near nor hit.
+ * Outputs per (set, leg) at [l*nsets + s], all written:
+ *   links_out (uint8) bit k set iff link k hits the trunk;
+ *   worst_out (uint8) the near link with the largest pen, ties to the smaller k; 255 when none is near;
+ *   pen_out   (float, may be NULL) that pen, -inf when none;
+ * and free_out[s] (uint8, nsets, may be NULL): 1 iff the set is live and no valid leg has a hit.
+ * A DEAD set -- live_in[s] == 0 (uint8, nsets, device for _dev and host for _cpu, may be NULL), or p outside [0, nposes) --
+ * gets 0 / 255 / -inf and free 0; it touches no table and no angle.
+ * Consequences: pen > 0 iff links != 0; with margin == 0 worst is a hit or 255; links == 0 (or three radii of 0) gives the
+ * empty answer everywhere and free = live; a link wholly inside the cylinder has d = 0 and pen = radius[k]; free_out is
+ * directly a live_in / pose_live of the other posed calls:
+ * ... -> ik -> trunk_clearance -> self_clearance(live_in = free) -> leg_clearance(live_in = free).
+ * Checked first, in lrm_self_clearance_posed_dev's order and by its rules (all LRM_EINVAL): nlegs outside 1..LRM_MAX_LEGS; nsets
+ * or nposes > INT32_MAX, or nlegs * nsets past 2^32 - 1; a radius, margin or tip_clear that is nan, negative or infinite (NULL
+ * radius too); pose_idx == NULL with nsets > nposes; then a nan or infinite trunk_radius, plus_z or minus_z; trunk_radius < 0;
+ * plus_z <= minus_z; a links bit at or above 3.  Then nsets == 0 is a no-op; a NULL table, angle array, links_out or worst_out
+ * gives LRM_EINVAL.
+ * lrm_trunk_clearance_posed_dev: ONE launch, a lane per (set, leg): no allocation, no host synchronisation, no atomics, no
+ * shared buffer -- it can be captured in a graph and may run concurrently with anything, the pair kernels included, from any
+ * host thread.  Bit-deterministic; the answer of a leg depends on its own record and angles only.
+ * lrm_trunk_clearance_posed_cpu: host quats (nposes x 4), legs and angles_aos (nlegs * nsets triples {coxa, femur, tibia} at
+ * [l*nsets + s]), host pose_idx and live_in; it compiles its own tables and runs a serial loop over every (set, leg) with the
+ * same functions: the reference the GPU tests compare with bit for bit; *ms = the loop's time. */
+int lrm_trunk_clearance_posed_dev(const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs,
+                                  const int32_t* pose_idx /* device, nsets, may be NULL */, size_t nsets,
+                                  const float* coxa, const float* femur, const float* tibia /* device, nlegs*nsets at [l*nsets + s] */,
+                                  const float radius[3] /* host */, float margin, float tip_clear,
+                                  float trunk_radius, float plus_z, float minus_z, uint8_t links,
+                                  const uint8_t* live_in /* device, nsets, may be NULL */,
+                                  uint8_t* links_out, uint8_t* worst_out, float* pen_out /* may be NULL */,
+                                  uint8_t* free_out /* nsets, may be NULL */, void* stream);
+int lrm_trunk_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                                  const int32_t* pose_idx /* host, may be NULL */, size_t nsets, const float* angles_aos,
+                                  const float radius[3], float margin, float tip_clear,
+                                  float trunk_radius, float plus_z, float minus_z, uint8_t links,
+                                  const uint8_t* live_in /* host, may be NULL */, uint8_t* links_out, uint8_t* worst_out,
+                                  float* pen_out, uint8_t* free_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a
@@ -998,6 +1062,12 @@ int lrm_dbg_exact_math_dev(const float* a, const float* b, size_t n, float* at2,
  * tests hold the branchy distance to the text above on them. */
 int lrm_dbg_link_pair_dist_host(const float* segs, size_t n, float* out);
 int lrm_dbg_link_pair_dist_dev(const float* segs, size_t n, float* out, void* stream);
+/* The link-to-cylinder distance of lrm_trunk_clearance_posed_dev (csrc/lrm_trunk_clearance.h) on n hand-made links in the BODY
+ * frame: segs holds 6 floats per link, A and B as x, y, z; out[i] = d of link i against the cylinder (trunk_radius, plus_z,
+ * minus_z), which is not checked here.  Host build and device build (one link per lane); the tests hold the search to the text
+ * above on them and measure it against float64. */
+int lrm_dbg_trunk_link_dist_host(const float* segs, size_t n, float trunk_radius, float plus_z, float minus_z, float* out);
+int lrm_dbg_trunk_link_dist_dev(const float* segs, size_t n, float trunk_radius, float plus_z, float minus_z, float* out, void* stream);
 /* The device's correctly rounded square root (csrc/lrm_exact_math.h, lrm_sqrtf) against the
  * compiler's IEEE sqrtf on ALL 2^32 float bit patterns: writes the number of patterns whose results
  * differ bitwise (nan payloads included) and the first such pattern.  Synchronous. */

@@ -143,6 +143,10 @@ def load():
         "lrm_stance_stability_cpu": [vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
         "lrm_self_clearance_posed_dev": [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp],
         "lrm_self_clearance_posed_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_trunk_clearance_posed_dev": [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, fp, fp, fp, fp, fp, C.c_uint8, vp, vp, vp, vp, vp, vp],
+        "lrm_trunk_clearance_posed_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, fp, fp, fp, fp, fp, C.c_uint8, vp, vp, vp, vp, vp, vp],
+        "lrm_dbg_trunk_link_dist_host": [vp, sz, fp, fp, fp, vp],
+        "lrm_dbg_trunk_link_dist_dev": [vp, sz, fp, fp, fp, vp, vp],
         "lrm_dbg_link_pair_dist_host": [vp, sz, vp],
         "lrm_dbg_link_pair_dist_dev": [vp, sz, vp, vp],
     }
@@ -150,7 +154,7 @@ def load():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
@@ -788,6 +792,59 @@ def self_clearance_posed_cpu(quats, legs, angles, radius, margin=0.0, tip_clear=
                                               float(margin), float(tip_clear), _ptr(live_in), _ptr(hits), _ptr(with_), _ptr(links),
                                               _ptr(worst), _ptr(pen), _ptr(free), C.addressof(ms)))
     return hits, with_, links, worst, pen, free, ms.value
+
+
+def _links_mask(links):
+    links = int(links)
+    if not 0 <= links <= 255:
+        raise ValueError("links: a bit mask of the links to test (bit 0 coxa, 1 femur, 2 tibia)")
+    return links
+
+
+def trunk_clearance_posed_cpu(quats, legs, angles, radius, trunk_radius, plus_z, minus_z, margin=0.0, tip_clear=0.0, links=0b110,
+                              pose_idx=None, live_in=None, want_pen=True, want_free=True):
+    """lrm_trunk_clearance_posed_cpu: do the legs stay out of the robot's own trunk.  Sets, angles float32 [nlegs*nsets, 3] at
+    [l*nsets + s], radius, margin, tip_clear, pose_idx and live_in are self_clearance_posed_cpu's.  The trunk is
+    body_clearance_posed_cpu's cylinder (trunk_radius, plus_z, minus_z; body frame, axis z, about the body origin).  links: bit k
+    set = link k (0 coxa, 1 femur, 2 tibia) is tested; the coxa link starts at its mount on the trunk, hence 0b110.  Per
+    (leg, set): the bit mask of the links that hit the trunk, the link within margin that stands deepest (255 if none) and its
+    pen = radius - distance (-inf if none); per set whether it is live and no leg hits.  Serial host loop; want_* False pass NULL.
+    -> (links uint8, worst uint8, pen float32 or None, each [nlegs, nsets]; free uint8[nsets] or None; ms)"""
+    quats = _f32(quats, (-1, 4))
+    legs = _f32(legs, (-1, 14))
+    n, nl = len(quats), len(legs)
+    angles = _f32(angles)
+    if nl == 0 or angles.size % (3 * nl):
+        raise ValueError("angles: one (coxa, femur, tibia) triple per (leg, set), at [l*nsets + s]")
+    ns = angles.size // (3 * nl)
+    angles = angles.reshape(nl * ns, 3)
+    radius = _f32(radius, (3,))
+    if pose_idx is not None:
+        pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
+        if len(pose_idx) != ns:
+            raise ValueError("pose_idx: one pose per set")
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != ns:
+            raise ValueError("live_in: one byte per set")
+    hit, worst = (np.zeros((nl, ns), np.uint8) for _ in range(2))
+    pen = np.zeros((nl, ns), np.float32) if want_pen else None
+    free = np.zeros(ns, np.uint8) if want_free else None
+    ms = C.c_double(0)
+    check(load().lrm_trunk_clearance_posed_cpu(_ptr(quats), n, _ptr(legs), nl, _ptr(pose_idx), ns, _ptr(angles), _ptr(radius),
+                                               float(margin), float(tip_clear), float(trunk_radius), float(plus_z), float(minus_z),
+                                               _links_mask(links), _ptr(live_in), _ptr(hit), _ptr(worst), _ptr(pen), _ptr(free),
+                                               C.addressof(ms)))
+    return hit, worst, pen, free, ms.value
+
+
+def dbg_trunk_link_dist_host(segs, trunk_radius, plus_z, minus_z):
+    """lrm_dbg_trunk_link_dist_host: the link-to-cylinder distance of the trunk clearance calls on hand-made links in the body
+    frame, segs float32 [n, 6] = A, B -> float32[n]"""
+    segs = _f32(segs, (-1, 6))
+    out = np.zeros(len(segs), np.float32)
+    check(load().lrm_dbg_trunk_link_dist_host(_ptr(segs), len(segs), float(trunk_radius), float(plus_z), float(minus_z), _ptr(out)))
+    return out
 
 
 def dbg_link_pair_dist_host(segs):

@@ -24,6 +24,7 @@
 #include "lrm_leg_clearance.h"
 #include "lrm_stance.h"
 #include "lrm_self_clearance.h"
+#include "lrm_trunk_clearance.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -2220,6 +2221,95 @@ int lrm_self_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLeg
         }
         if (free_out) free_out[s] = set_free;
     }
+    return LRM_OK;
+}
+
+// ---- trunk-leg clearance per set: leg links against the body cylinder (lrm_trunk_clearance.hip) -----------
+namespace {
+// self_clearance_args' order and rules, then the cylinder and the link mask
+int trunk_clearance_args(size_t nposes, size_t nlegs, const int32_t* pose_idx, size_t nsets, const float* radius, float margin,
+                         float tip_clear, float trunk_radius, float plus_z, float minus_z, uint8_t links) {
+    const int rc = self_clearance_args(nposes, nlegs, pose_idx, nsets, radius, margin, tip_clear);
+    if (rc != LRM_OK) return rc;
+    if (!lrm_ik_finite(trunk_radius) || !lrm_ik_finite(plus_z) || !lrm_ik_finite(minus_z))
+        return fail(LRM_EINVAL, "trunk clearance: trunk_radius, plus_z and minus_z must be finite");
+    if (trunk_radius < 0.f) return fail(LRM_EINVAL, "trunk clearance: trunk_radius must be >= 0");
+    if (plus_z <= minus_z) return fail(LRM_EINVAL, "trunk clearance: plus_z must exceed minus_z");
+    if (links >> 3) return fail(LRM_EINVAL, "trunk clearance: links has bits 0..2 only (coxa, femur, tibia link)");
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_trunk_clearance_posed_dev(const void* workspace, const void* ik_workspace, size_t nposes, size_t nlegs, const int32_t* pose_idx,
+                                  size_t nsets, const float* coxa, const float* femur, const float* tibia, const float radius[3],
+                                  float margin, float tip_clear, float trunk_radius, float plus_z, float minus_z, uint8_t links,
+                                  const uint8_t* live_in, uint8_t* links_out, uint8_t* worst_out, float* pen_out, uint8_t* free_out,
+                                  void* stream) {
+    const int rc = trunk_clearance_args(nposes, nlegs, pose_idx, nsets, radius, margin, tip_clear, trunk_radius, plus_z, minus_z, links);
+    if (rc != LRM_OK) return rc;
+    if (nsets == 0) return LRM_OK;
+    if (!workspace || !ik_workspace || !coxa || !femur || !tibia || !links_out || !worst_out) return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
+    HIP_TRY(lrm_launch_trunk_clearance_posed(workspace, ik_workspace, nposes, nlegs, pose_idx, nsets, coxa, femur, tibia, radius, margin,
+                                             tip_clear, trunk_radius, plus_z, minus_z, links, live_in, links_out, worst_out, pen_out,
+                                             free_out, (hipStream_t)stream),
+            "posed trunk clearance launch");
+    return LRM_OK;
+}
+
+int lrm_trunk_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* pose_idx,
+                                  size_t nsets, const float* angles, const float radius[3], float margin, float tip_clear,
+                                  float trunk_radius, float plus_z, float minus_z, uint8_t links, const uint8_t* live_in,
+                                  uint8_t* links_out, uint8_t* worst_out, float* pen_out, uint8_t* free_out, double* ms) {
+    const int rc = trunk_clearance_args(nposes, nlegs, pose_idx, nsets, radius, margin, tip_clear, trunk_radius, plus_z, minus_z, links);
+    if (rc != LRM_OK) return rc;
+    if (nsets == 0) return LRM_OK;
+    if (!legs || (nposes && !quats) || !angles || !links_out || !worst_out) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, nullptr, nposes, legs, nlegs, recs.data()); // the body position is not read
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const LrmTrunkRadii R = lrm_trunk_radii(radius, margin, links);
+    const LrmTrunk C{trunk_radius, plus_z, minus_z};
+    const ScopeMs timer{ms};
+    for (size_t s = 0; s < nsets; s++) {
+        const int64_t p = pose_idx ? (int64_t)pose_idx[s] : (int64_t)s;
+        const bool live = !(live_in && !live_in[s]) && p >= 0 && (uint64_t)p < nposes;
+        bool set_free = live;
+        for (size_t l = 0; l < nlegs; l++) {
+            const size_t o = l * nsets + s;
+            LrmTrunkLeg A = lrm_trunk_leg_empty();
+            if (live) {
+                const LrmPoseRecord& rec = recs[p * nlegs + l];
+                LrmVec3 J[4];
+                lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(rec.head), iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
+                               angles[3 * o + 2], tip_clear, J);
+                if (lrm_leg_joints_finite(J)) A = lrm_trunk_leg(C, R, rec.head.inv_rot, J);
+            }
+            links_out[o] = (uint8_t)A.links;
+            worst_out[o] = (uint8_t)A.worst;
+            if (pen_out) pen_out[o] = A.pen;
+            set_free = set_free && A.links == 0u;
+        }
+        if (free_out) free_out[s] = set_free;
+    }
+    return LRM_OK;
+}
+
+// ---- diagnostics: lrm_trunk_clearance.h's link distance on arrays (host build / device build) -----------
+int lrm_dbg_trunk_link_dist_host(const float* segs, size_t n, float trunk_radius, float plus_z, float minus_z, float* out) {
+    if (n && (!segs || !out)) return fail(LRM_EINVAL, "null argument");
+    const LrmTrunk C{trunk_radius, plus_z, minus_z};
+    for (size_t i = 0; i < n; i++) {
+        const float* g = segs + 6 * i;
+        out[i] = lrm_trunk_link_dist(C, LrmVec3{g[0], g[1], g[2]}, LrmVec3{g[3], g[4], g[5]});
+    }
+    return LRM_OK;
+}
+int lrm_dbg_trunk_link_dist_dev(const float* segs, size_t n, float trunk_radius, float plus_z, float minus_z, float* out, void* stream) {
+    if (n && (!segs || !out)) return fail(LRM_EINVAL, "null argument");
+    if (n == 0) return LRM_OK;
+    HIP_TRY(lrm_launch_trunk_link_dist(segs, n, trunk_radius, plus_z, minus_z, out, (hipStream_t)stream), "trunk link distance launch");
     return LRM_OK;
 }
 

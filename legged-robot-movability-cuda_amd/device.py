@@ -416,6 +416,22 @@ def dbg_link_pair_dist(segs, out=None):
     return out
 
 
+def dbg_trunk_link_dist(segs, trunk_radius, plus_z, minus_z, out=None):
+    """lrm_dbg_trunk_link_dist_dev: the link-to-cylinder distance of trunk_clearance() on links in the body frame, segs float32
+    (n, 6) = A, B on the device -> float32 (n,); one link per lane."""
+    torch = _torch()
+    if not (segs.is_cuda and segs.dtype == torch.float32 and segs.dim() == 2 and segs.shape[1] == 6 and segs.is_contiguous()):
+        raise ValueError("segs: expected a contiguous float32 CUDA tensor of shape (n, 6)")
+    n = segs.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=segs.device)
+    _check_out(out, segs, torch.float32, n, "distances")
+    with torch.cuda.device(segs.device):
+        _capi.check(_capi.load().lrm_dbg_trunk_link_dist_dev(_dp(segs), n, float(trunk_radius), float(plus_z), float(minus_z), _dp(out),
+                                                             _stream(segs)))
+    return out
+
+
 class PoseSet:
     """A pose table for batched multi-pose queries (lrm_pose_compile_dev / lrm_reach_dist_posed_dev).
 
@@ -435,7 +451,8 @@ class PoseSet:
     leg_clearance() (with ik=True) asks the same of the legs under ik()'s angles: terrain inside the coxa, femur and tibia
     links, and leg_joints() returns the joints it tests; stance_stability() asks whether the chosen footholds carry the
     centre of mass, and which legs can be lifted; self_clearance() (with ik=True) asks whether the legs fit next to each
-    other under ik()'s angles: links of different legs against each other."""
+    other under ik()'s angles: links of different legs against each other; trunk_clearance() (with ik=True) whether they
+    stay out of the robot's own trunk: leg links against the body cylinder."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -893,6 +910,63 @@ class PoseSet:
                                                                   _dp(hits), _dp(with_), _dp(links), _dp(worst), _dp(pen), _dp(free),
                                                                   _stream(self.workspace)))
         return hits, with_, links, worst, pen, free
+
+    def trunk_clearance(self, angles, radius, trunk_radius, plus_z, minus_z, margin=0.0, tip_clear=0.0, links=0b110, pose_idx=None,
+                        live_in=None, hit=None, worst=None, pen=None, free=None):
+        """lrm_trunk_clearance_posed_dev: do the legs stay out of the robot's own trunk under the given joint angles.  Sets,
+        angles (ik()'s (3, nlegs*nsets) tensor, entry l*nsets + s), radius, margin, tip_clear, pose_idx and live_in are
+        self_clearance()'s.  The trunk is body_clearance()'s cylinder: trunk_radius, plus_z, minus_z in the body frame, axis z,
+        about the body origin.  links: bit k set = link k (0 coxa, 1 femur, 2 tibia) is tested; the coxa link starts at its
+        mount on the trunk, hence 0b110; a link with radius 0 is not tested either.  hit[l, s] = bit k set iff link k of leg l
+        hits the trunk; worst[l, s] = the link within margin that stands deepest (255 if none); pen[l, s] = its radius -
+        distance (-inf if none); free[s] = 1 iff the set is live and no leg hits.  A leg with nan angles gets the empty answer
+        and does not block free.  live_in: uint8[nsets] on the device, 0 = dead (0, 255, -inf, free 0), as is a pose index
+        outside the set's poses.
+        -> (hit uint8, worst uint8, pen float32, each [nlegs, nsets]; free uint8[nsets]); free is self_clearance()'s and
+        leg_clearance()'s live_in.  pose_idx, live_in and given outputs must be contiguous.  One launch, no allocation beyond
+        missing outputs, no shared buffer: update -> footholds -> ik -> trunk_clearance -> self_clearance -> leg_clearance can
+        be captured in a graph, and the call may run next to anything."""
+        torch = _torch()
+        if self.ik_workspace is None:
+            raise ValueError("PoseSet: built without ik=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
+                and angles.shape[0] == 3 and angles.shape[1] % self.nlegs == 0 and angles.is_contiguous()):
+            raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {self.nlegs} * nsets) tensor on {self.workspace.device}")
+        ns = angles.shape[1] // self.nlegs
+        n = self.nlegs * ns
+        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if len(radius) != 3:
+            raise ValueError("radius: three values (coxa, femur, tibia link)")
+        links = _capi._links_mask(links)
+        _check_out(pose_idx, self.workspace, torch.int32, ns, "pose_idx")
+        _check_out(live_in, self.workspace, torch.uint8, ns, "live_in")
+        if pose_idx is not None and pose_idx.numel() != ns or live_in is not None and live_in.numel() != ns:
+            raise ValueError("pose_idx / live_in: one entry per set")
+        if pose_idx is None and ns > self.nposes:
+            raise ValueError("without pose_idx set s takes pose s: nsets <= nposes")
+        shape = (self.nlegs, ns)
+        if hit is None:
+            hit = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if worst is None:
+            worst = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if pen is None:
+            pen = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if free is None:
+            free = torch.empty(ns, dtype=torch.uint8, device=self.device)
+        _check_out(hit, self.workspace, torch.uint8, n, "per-leg link masks")
+        _check_out(worst, self.workspace, torch.uint8, n, "per-leg worst links")
+        _check_out(pen, self.workspace, torch.float32, n, "per-leg penetrations")
+        _check_out(free, self.workspace, torch.uint8, ns, "per-set free bytes")
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().lrm_trunk_clearance_posed_dev(_dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
+                                                                   _dp(pose_idx), ns, _dp(angles[0]), _dp(angles[1]), _dp(angles[2]),
+                                                                   _capi._ptr(radius), float(margin), float(tip_clear),
+                                                                   float(trunk_radius), float(plus_z), float(minus_z), links,
+                                                                   _dp(live_in), _dp(hit), _dp(worst), _dp(pen), _dp(free),
+                                                                   _stream(self.workspace)))
+        return hit, worst, pen, free
 
     def leg_joints(self, angles, tip_clear=0.0, out=None):
         """lrm_leg_joints_posed_dev: the four joints of every (leg, pose) under angles (ik()'s (3, nlegs*nposes) tensor under
