@@ -475,7 +475,8 @@ int lrm_foothold_lists_posed_cpu(const float* targets_aos, size_t nt, const floa
  *                 d2 = d2_a + d2_b, ONE float32 add (no contraction) of the two d2 of lrm_footholds_posed_dev, i.e. of
  *                 (t - (body[a] + nominal_w[a,l]))^2 and (t - (body[b] + nominal_w[b,l]))^2: its minimum is the common
  *                 target nearest the midpoint of the leg's two nominal foot positions;
- *   all_legs_out  (may be NULL, nedges) 1 iff every leg has count > 0: the move is feasible with all feet planted.
+ *   all_legs_out  (may be NULL, nedges) 1 iff every leg has count > 0: the move is feasible with all feet planted AT ITS TWO ENDS;
+ *                 lrm_edge_transit_posed_dev tests the poses in between.
  * Consequences: for a == b count and best are lrm_footholds_posed_dev's of that pose and best_d2 is exactly twice its
  * value (x + x is exact); swapping edge_a and edge_b changes no output bit; best_out is a valid target_idx of
  * lrm_ik_posed_dev with pose_idx = either end of the edge.
@@ -933,6 +934,71 @@ int lrm_trunk_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLe
                                   float trunk_radius, float plus_z, float minus_z, uint8_t links,
                                   const uint8_t* live_in /* host, may be NULL */, uint8_t* links_out, uint8_t* worst_out,
                                   float* pen_out, uint8_t* free_out, double* ms);
+/* PLANTED-FOOT REACH ALONG A POSE TRANSITION: lrm_foothold_edges_posed_dev tests an edge (a, b) at its two ENDS only; a leg's
+ * workspace is not convex, so a foothold reachable under pose a and under pose b can be out of reach on the way.  This call
+ * samples the way: per (edge, leg) with a planted foot it evaluates nsamples = S poses between a and b (2 <= S <= 64, the ends
+ * included) and says at which of them the foot is reachable.  The reference has no such query.  It takes NO workspace and reads
+ * no table: the cloud, the quats (nposes x 4) and body (nposes x 3, NULL = 0) that lrm_pose_compile_dev reads (device for _dev),
+ * the legs (host, 1..LRM_MAX_LEGS), edge_a / edge_b (int32, nedges), foot (int32, [l*nedges + e]: lrm_foothold_edges_posed_dev's
+ * best_out as it stands, -1 = the leg is in the air) and live_in (uint8, nedges, may be NULL).
+ * Everything is float32 without contraction, only + - * /, comparisons and the correctly rounded square root on top of the head
+ * compiler and the strict evaluation: device and host give the same bits (csrc/lrm_edge_transit.h is the one source of both).
+ * Sample s of edge e, with a = edge_a[e], b = edge_b[e], qa = quats[a], qb = quats[b], ba = body[a], bb = body[b]:
+ *   u = (float)s / (float)(S - 1); w = 1 - u;
+ *   dot = ((qa0*qb0 + qa1*qb1) + qa2*qb2) + qa3*qb3; sg = dot < 0 ? -1 : +1 (a nan dot gives +1);
+ *   m_i = w*qa_i + u*(sg*qb_i); n2 = ((m0*m0 + m1*m1) + m2*m2) + m3*m3; q_i = m_i / sqrt(n2);
+ *   body_i = ba_i + u*(bb_i - ba_i).
+ *   Samples 0 and S-1 are NOT computed this way: they are quats[a], body[a] and quats[b], body[b] themselves, bit for bit and not
+ *   normalised, so they equal the posed calls on those poses.  The normalised blend traces the same great arc as slerp (it stays
+ *   in the plane of qa and sg*qb); only the speed along the arc differs: slower than slerp near the ends, faster in the middle.
+ *   A degenerate interior quaternion (n2 = 0, nan, inf) is evaluated as it comes out.
+ * PLANTED: (e, l) is planted iff the edge is live (live_in NULL or live_in[e] != 0), a and b lie in [0, nposes) and
+ *   0 <= foot[o] < nt, o = l*nedges + e.  An edge that is not live or has an end out of range is DEAD.
+ * Per sample of a planted leg: p_s = t[foot[o]] - body_s (one subtraction per component); r_s = reachability_global(p_s, legs[l],
+ *   q_s): the strict evaluation on lrm_compile_head(legs[l], q_s, 1) whatever lrm_set_mode says, exactly as
+ *   lrm_reach_dist_posed_* answers a pose with that quaternion and body.  Where r_s = 0, d2_s = (dx*dx + dy*dy) + dz*dz of
+ *   distance_global's vector (its validity byte is not consulted); a nan d2 is compared and stored as +inf.
+ * Outputs per (edge, leg) at [l*nedges + e], all written:
+ *   mask_out       (uint64, may be NULL) bit s = r_s; 0 when not planted;
+ *   reached_out    (int32) the number of set bits; -1 when not planted;
+ *   first_miss_out (int32) the smallest s with r_s = 0; -1 if none or not planted;
+ *   worst_out      (int32, may be NULL) the unreachable sample with the largest d2, ties to the smaller s; -1 if none;
+ *   worst_d2_out   (float, may be NULL) that d2; 0 if none;
+ * and per edge:
+ *   planted_out (uint8, may be NULL) bit l set iff leg l is planted;
+ *   clear_out   (uint8, may be NULL) 1 iff the edge is not dead and every planted leg has reached == S.  An edge without a planted
+ *               leg is clear: planted_out tells.  The byte is directly a live_in of the other posed calls;
+ *   advance_out (int32, may be NULL) the number of leading samples at which every planted leg reaches: the minimum over the
+ *               planted legs of first_miss, S where none misses -- how far the body gets before some foot must be lifted.
+ *               0 for a dead edge.
+ * Consequences: a == b makes every interior sample the pose's own quaternion, normalised (equal to the ends up to rounding), on
+ * the pose's own body: the mask is all ones or zero unless the target lies within rounding of the workspace boundary; with foot = lrm_foothold_edges_posed_dev's best, bits 0
+ * and S-1 of every planted entry are set; swapping the ends reverses the mask whenever (S-1-s)/(S-1) is the same float as
+ * 1 - s/(S-1) for every s (S = 2, 3, 5, 9, 17, 33: S-1 a power of two).
+ * Checked first, in this order (all LRM_EINVAL): nlegs outside 1..LRM_MAX_LEGS; nsamples outside 2..64; nt or nposes > INT32_MAX;
+ * nedges * nlegs past 2^32 - 1.  Then nedges == 0 is a no-op.  Then a NULL quats, legs, edge_a, edge_b, foot, reached_out or
+ * first_miss_out, or a NULL cloud with nt > 0, gives LRM_EINVAL.  nt == 0 plants nothing.  Any contents of edge_a, edge_b and foot
+ * are safe: an index is checked before an address is formed from it.
+ * lrm_edge_transit_posed_dev: ONE launch, a lane per (edge, sample): no allocation, no host synchronisation, no atomics, no shared
+ * buffer, no table -- it can be captured in a graph and may run concurrently with anything from any host thread.
+ * Bit-deterministic; the answer of an (edge, leg) depends on its own inputs only.
+ * lrm_edge_transit_posed_cpu: AoS targets, host arrays, a serial loop over every (edge, leg, sample) with the same functions: the
+ * reference the GPU tests compare with bit for bit; *ms = the loop's time.
+ * Chain: update -> footholds -> foothold_edges -> edge_transit -> ik / stance_stability(live_in = clear). */
+int lrm_edge_transit_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const float* quats /* device */,
+                               const float* body /* device, may be NULL */, size_t nposes, const LrmLegDimensions* legs /* host */,
+                               size_t nlegs, const int32_t* edge_a, const int32_t* edge_b /* device, nedges */, size_t nedges,
+                               const int32_t* foot /* device, nlegs*nedges at [l*nedges + e] */, size_t nsamples,
+                               const uint8_t* live_in /* device, nedges, may be NULL */, uint64_t* mask_out /* may be NULL */,
+                               int32_t* reached_out, int32_t* first_miss_out, int32_t* worst_out /* may be NULL */,
+                               float* worst_d2_out /* may be NULL */, uint8_t* planted_out /* nedges, may be NULL */,
+                               uint8_t* clear_out /* nedges, may be NULL */, int32_t* advance_out /* nedges, may be NULL */,
+                               void* stream);
+int lrm_edge_transit_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body /* may be NULL */,
+                               size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b,
+                               size_t nedges, const int32_t* foot, size_t nsamples, const uint8_t* live_in /* may be NULL */,
+                               uint64_t* mask_out, int32_t* reached_out, int32_t* first_miss_out, int32_t* worst_out,
+                               float* worst_d2_out, uint8_t* planted_out, uint8_t* clear_out, int32_t* advance_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a
@@ -1068,6 +1134,14 @@ int lrm_dbg_link_pair_dist_dev(const float* segs, size_t n, float* out, void* st
  * above on them and measure it against float64. */
 int lrm_dbg_trunk_link_dist_host(const float* segs, size_t n, float trunk_radius, float plus_z, float minus_z, float* out);
 int lrm_dbg_trunk_link_dist_dev(const float* segs, size_t n, float trunk_radius, float plus_z, float minus_z, float* out, void* stream);
+/* The sampled path of lrm_edge_transit_posed_dev (csrc/lrm_edge_transit.h) on its own: out holds 7 floats per (edge, sample) at
+ * [(e*nsamples + s)*7]: the quaternion q_s and the body position body_s the call evaluates; nan for an edge with an end outside
+ * [0, nposes).  body may be NULL (= 0).  Host build and device build (one sample per lane); the tests hold the path to the
+ * text above and measure it against a float64 model. */
+int lrm_dbg_edge_transit_samples_host(const float* quats, const float* body, size_t nposes, const int32_t* edge_a, const int32_t* edge_b,
+                                      size_t nedges, size_t nsamples, float* out);
+int lrm_dbg_edge_transit_samples_dev(const float* quats, const float* body, size_t nposes, const int32_t* edge_a, const int32_t* edge_b,
+                                     size_t nedges, size_t nsamples, float* out, void* stream);
 /* The device's correctly rounded square root (csrc/lrm_exact_math.h, lrm_sqrtf) against the
  * compiler's IEEE sqrtf on ALL 2^32 float bit patterns: writes the number of patterns whose results
  * differ bitwise (nan payloads included) and the first such pattern.  Synchronous. */

@@ -146,6 +146,10 @@ def load():
         "lrm_trunk_clearance_posed_dev": [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, fp, fp, fp, fp, fp, C.c_uint8, vp, vp, vp, vp, vp, vp],
         "lrm_trunk_clearance_posed_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, fp, fp, fp, fp, fp, C.c_uint8, vp, vp, vp, vp, vp, vp],
         "lrm_dbg_trunk_link_dist_host": [vp, sz, fp, fp, fp, vp],
+        "lrm_dbg_edge_transit_samples_host": [vp, vp, sz, vp, vp, sz, sz, vp],
+        "lrm_dbg_edge_transit_samples_dev": [vp, vp, sz, vp, vp, sz, sz, vp, vp],
+        "lrm_edge_transit_posed_dev": [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_edge_transit_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "lrm_dbg_trunk_link_dist_dev": [vp, sz, fp, fp, fp, vp, vp],
         "lrm_dbg_link_pair_dist_host": [vp, sz, vp],
         "lrm_dbg_link_pair_dist_dev": [vp, sz, vp, vp],
@@ -154,7 +158,7 @@ def load():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_", "lrm_edge_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes = argtypes
@@ -836,6 +840,72 @@ def trunk_clearance_posed_cpu(quats, legs, angles, radius, trunk_radius, plus_z,
                                                _links_mask(links), _ptr(live_in), _ptr(hit), _ptr(worst), _ptr(pen), _ptr(free),
                                                C.addressof(ms)))
     return hit, worst, pen, free, ms.value
+
+
+def _nsamples(nsamples):
+    nsamples = int(nsamples)
+    if nsamples < 0:
+        raise ValueError("nsamples: 2 to 64 poses per edge, the ends included")
+    return nsamples
+
+
+def edge_transit_posed_cpu(targets, quats, body, legs, edge_a, edge_b, foot, nsamples=9, live_in=None, want_mask=True,
+                           want_worst=True, want_edge=True):
+    """lrm_edge_transit_posed_cpu: does a planted foot stay reachable while the body moves from pose edge_a[e] to pose edge_b[e].
+    foot int32 [nlegs, nedges] = foothold_edges_posed_cpu's best as it stands (-1: the leg is in the air); nsamples poses per
+    edge, the ends included: the normalised linear blend of the two quaternions (the short way round; the great arc of slerp at
+    another speed) and the linear blend of the bodies; the ends are the poses themselves.  Per (leg, edge): mask (bit s = sample
+    s reaches), reached (the number of bits; -1 when not planted), first_miss (the first sample that does not reach; -1 if none),
+    worst (the unreachable sample with the largest squared distance_global vector; -1 if none) and that worst_d2 (0 if none);
+    per edge: planted (bit l = leg l is planted), clear (live, both ends in range and every planted leg reaches at every sample)
+    and advance (the number of leading samples at which every planted leg reaches; 0 for a dead edge).  Serial host loop;
+    want_* False pass NULL.
+    -> (mask uint64 or None, reached int32, first_miss int32, worst int32 or None, worst_d2 float32 or None, each [nlegs, nedges];
+    planted uint8, clear uint8, advance int32, each [nedges] or None; ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    nl = len(legs)
+    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    ne = len(edge_a)
+    if len(edge_b) != ne:
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    foot = np.ascontiguousarray(foot, np.int32)
+    if foot.size != nl * ne:
+        raise ValueError("foot: one target index per (leg, edge), at [l*nedges + e]")
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != ne:
+            raise ValueError("live_in: one byte per edge")
+    shape = (nl, ne)
+    mask = np.zeros(shape, np.uint64) if want_mask else None
+    reached, first_miss = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    worst = np.zeros(shape, np.int32) if want_worst else None
+    worst_d2 = np.zeros(shape, np.float32) if want_worst else None
+    planted = np.zeros(ne, np.uint8) if want_edge else None
+    clear = np.zeros(ne, np.uint8) if want_edge else None
+    advance = np.zeros(ne, np.int32) if want_edge else None
+    ms = C.c_double(0)
+    check(load().lrm_edge_transit_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), nl,
+                                            _ptr(edge_a), _ptr(edge_b), ne, _ptr(foot), _nsamples(nsamples), _ptr(live_in), _ptr(mask),
+                                            _ptr(reached), _ptr(first_miss), _ptr(worst), _ptr(worst_d2), _ptr(planted), _ptr(clear),
+                                            _ptr(advance), C.addressof(ms)))
+    return mask, reached, first_miss, worst, worst_d2, planted, clear, advance, ms.value
+
+
+def dbg_edge_transit_samples_host(quats, body, edge_a, edge_b, nsamples):
+    """lrm_dbg_edge_transit_samples_host: the sampled path of the edge transit calls -> float32 [nedges, nsamples, 7] = the
+    quaternion and the body position of every sample (nan for an edge with an end out of range)"""
+    quats = _f32(quats).reshape(-1, 4)
+    body = None if body is None else _f32(body).reshape(-1, 3)
+    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    if len(edge_a) != len(edge_b) or (body is not None and len(body) != len(quats)):
+        raise ValueError("edge_a / edge_b: one pose index each per edge; body: one position per pose")
+    out = np.zeros((len(edge_a), _nsamples(nsamples), 7), np.float32)
+    check(load().lrm_dbg_edge_transit_samples_host(_ptr(quats), _ptr(body), len(quats), _ptr(edge_a), _ptr(edge_b), len(edge_a),
+                                                   _nsamples(nsamples), _ptr(out)))
+    return out
 
 
 def dbg_trunk_link_dist_host(segs, trunk_radius, plus_z, minus_z):

@@ -25,6 +25,7 @@
 #include "lrm_stance.h"
 #include "lrm_self_clearance.h"
 #include "lrm_trunk_clearance.h"
+#include "lrm_edge_transit.h"
 #include "lrm_ik.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
@@ -2310,6 +2311,142 @@ int lrm_dbg_trunk_link_dist_dev(const float* segs, size_t n, float trunk_radius,
     if (n && (!segs || !out)) return fail(LRM_EINVAL, "null argument");
     if (n == 0) return LRM_OK;
     HIP_TRY(lrm_launch_trunk_link_dist(segs, n, trunk_radius, plus_z, minus_z, out, (hipStream_t)stream), "trunk link distance launch");
+    return LRM_OK;
+}
+
+// ---- planted-foot reach along pose transitions: sampled motion per edge (lrm_edge_transit.hip) -----------
+namespace {
+// the range checks of both forms, before any early return
+int edge_transit_args(size_t nt, size_t nposes, size_t nlegs, size_t nedges, size_t nsamples) {
+    if (nlegs < 1 || nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "edge transit: nlegs must be 1..LRM_MAX_LEGS");
+    if (nsamples < 2 || nsamples > LRM_TRANSIT_MAX_SAMPLES) return fail(LRM_EINVAL, "edge transit: nsamples must be 2..64");
+    if (nt > (size_t)INT32_MAX || nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "edge transit: nt and nposes must not exceed INT32_MAX");
+    if (nedges > (size_t)UINT32_MAX / nlegs) return fail(LRM_EINVAL, "edge transit: more than 2^32 - 1 (edge, leg) outputs");
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_edge_transit_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const float* quats, const float* body,
+                               size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b,
+                               size_t nedges, const int32_t* foot, size_t nsamples, const uint8_t* live_in, uint64_t* mask_out,
+                               int32_t* reached_out, int32_t* first_miss_out, int32_t* worst_out, float* worst_d2_out,
+                               uint8_t* planted_out, uint8_t* clear_out, int32_t* advance_out, void* stream) {
+    const int rc = edge_transit_args(nt, nposes, nlegs, nedges, nsamples);
+    if (rc != LRM_OK) return rc;
+    if (nedges == 0) return LRM_OK;
+    if (!quats || !legs || !edge_a || !edge_b || !foot || !reached_out || !first_miss_out || (nt && (!tx || !ty || !tz)))
+        return fail(LRM_EINVAL, "null argument");
+    HIP_TRY(lrm_launch_edge_transit_posed(tx, ty, tz, nt, quats, body, nposes, legs, nlegs, edge_a, edge_b, nedges, foot, nsamples, live_in,
+                                          mask_out, reached_out, first_miss_out, worst_out, worst_d2_out, planted_out, clear_out,
+                                          advance_out, (hipStream_t)stream),
+            "edge transit launch");
+    return LRM_OK;
+}
+
+int lrm_edge_transit_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                               const LrmLegDimensions* legs, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b, size_t nedges,
+                               const int32_t* foot, size_t nsamples, const uint8_t* live_in, uint64_t* mask_out, int32_t* reached_out,
+                               int32_t* first_miss_out, int32_t* worst_out, float* worst_d2_out, uint8_t* planted_out,
+                               uint8_t* clear_out, int32_t* advance_out, double* ms) {
+    const int rc = edge_transit_args(nt, nposes, nlegs, nedges, nsamples);
+    if (rc != LRM_OK) return rc;
+    if (nedges == 0) return LRM_OK;
+    if (!quats || !legs || !edge_a || !edge_b || !foot || !reached_out || !first_miss_out || (nt && !targets))
+        return fail(LRM_EINVAL, "null argument");
+    const uint32_t S = (uint32_t)nsamples;
+    LrmCompiledLeg H; // only its head is written and read
+    const ScopeMs timer{ms};
+    for (size_t e = 0; e < nedges; e++) {
+        const int64_t a = edge_a[e], b = edge_b[e];
+        const bool live = !(live_in && !live_in[e]) && a >= 0 && b >= 0 && (uint64_t)a < nposes && (uint64_t)b < nposes;
+        LrmVec3 ba{0.f, 0.f, 0.f}, bb{0.f, 0.f, 0.f};
+        if (live && body) {
+            ba = LrmVec3{body[3 * a], body[3 * a + 1], body[3 * a + 2]};
+            bb = LrmVec3{body[3 * b], body[3 * b + 1], body[3 * b + 2]};
+        }
+        uint32_t planted_bits = 0u;
+        bool all_reach = true;
+        int32_t advance = (int32_t)S;
+        for (size_t l = 0; l < nlegs; l++) {
+            const size_t o = l * nedges + e;
+            LrmTransitLeg A = lrm_transit_leg_unplanted();
+            if (live && lrm_transit_foot_in_cloud(foot[o], (uint32_t)nt)) {
+                const float* t = targets + 3 * (size_t)foot[o];
+                uint64_t mask = 0ull, key = 0ull;
+                for (uint32_t s = 0; s < S; s++) {
+                    const LrmTransitSample smp = lrm_transit_sample(quats + 4 * a, quats + 4 * b, ba, bb, s, S);
+                    const LrmVec3 p{t[0] - smp.body.x, t[1] - smp.body.y, t[2] - smp.body.z};
+                    float d2 = 0.f;
+                    if (lrm_transit_eval(legs[l], smp.q, p, &H, &d2)) {
+                        mask |= 1ull << s;
+                    } else {
+                        const uint64_t k = lrm_transit_key(d2, s);
+                        if (k > key) key = k;
+                    }
+                }
+                A = lrm_transit_leg(mask, key, S);
+                planted_bits |= 1u << l;
+                all_reach = all_reach && A.first_miss < 0;
+                if (A.first_miss >= 0 && A.first_miss < advance) advance = A.first_miss;
+            }
+            if (mask_out) mask_out[o] = A.mask;
+            reached_out[o] = A.reached;
+            first_miss_out[o] = A.first_miss;
+            if (worst_out) worst_out[o] = A.worst;
+            if (worst_d2_out) worst_d2_out[o] = A.worst_d2;
+        }
+        if (planted_out) planted_out[e] = (uint8_t)planted_bits;
+        if (clear_out) clear_out[e] = live && all_reach;
+        if (advance_out) advance_out[e] = live ? advance : 0;
+    }
+    return LRM_OK;
+}
+
+// ---- diagnostics: lrm_edge_transit.h's sampled path on arrays (host build / device build) -----------
+namespace {
+int edge_transit_samples_args(const float* quats, size_t nposes, const int32_t* edge_a, const int32_t* edge_b, size_t nedges,
+                              size_t nsamples, const float* out) {
+    if (nsamples < 2 || nsamples > LRM_TRANSIT_MAX_SAMPLES) return fail(LRM_EINVAL, "edge transit: nsamples must be 2..64");
+    if (nposes > (size_t)INT32_MAX || nedges > (size_t)UINT32_MAX / LRM_TRANSIT_MAX_SAMPLES)
+        return fail(LRM_EINVAL, "edge transit samples: too many poses or edges");
+    if (nedges && (!quats || !edge_a || !edge_b || !out)) return fail(LRM_EINVAL, "null argument");
+    return LRM_OK;
+}
+} // namespace
+int lrm_dbg_edge_transit_samples_host(const float* quats, const float* body, size_t nposes, const int32_t* edge_a, const int32_t* edge_b,
+                                      size_t nedges, size_t nsamples, float* out) {
+    const int rc = edge_transit_samples_args(quats, nposes, edge_a, edge_b, nedges, nsamples, out);
+    if (rc != LRM_OK) return rc;
+    for (size_t e = 0; e < nedges; e++) {
+        const int64_t a = edge_a[e], b = edge_b[e];
+        const bool ok = a >= 0 && b >= 0 && (uint64_t)a < nposes && (uint64_t)b < nposes;
+        for (uint32_t s = 0; s < (uint32_t)nsamples; s++) {
+            float* o = out + (e * nsamples + s) * 7;
+            if (!ok) {
+                for (int k = 0; k < 7; k++) o[k] = std::nanf("");
+                continue;
+            }
+            LrmVec3 ba{0.f, 0.f, 0.f}, bb{0.f, 0.f, 0.f};
+            if (body) {
+                ba = LrmVec3{body[3 * a], body[3 * a + 1], body[3 * a + 2]};
+                bb = LrmVec3{body[3 * b], body[3 * b + 1], body[3 * b + 2]};
+            }
+            const LrmTransitSample smp = lrm_transit_sample(quats + 4 * a, quats + 4 * b, ba, bb, s, (uint32_t)nsamples);
+            for (int k = 0; k < 4; k++) o[k] = smp.q[k];
+            o[4] = smp.body.x;
+            o[5] = smp.body.y;
+            o[6] = smp.body.z;
+        }
+    }
+    return LRM_OK;
+}
+int lrm_dbg_edge_transit_samples_dev(const float* quats, const float* body, size_t nposes, const int32_t* edge_a, const int32_t* edge_b,
+                                     size_t nedges, size_t nsamples, float* out, void* stream) {
+    const int rc = edge_transit_samples_args(quats, nposes, edge_a, edge_b, nedges, nsamples, out);
+    if (rc != LRM_OK) return rc;
+    if (nedges == 0) return LRM_OK;
+    HIP_TRY(lrm_launch_edge_transit_samples(quats, body, nposes, edge_a, edge_b, nedges, nsamples, out, (hipStream_t)stream),
+            "edge transit samples launch");
     return LRM_OK;
 }
 

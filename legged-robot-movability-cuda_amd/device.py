@@ -401,6 +401,104 @@ def stance_stability(tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None
     return margin, edge, stable, feet
 
 
+def edge_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot, nsamples=9, live_in=None, mask=None, reached=None,
+                 first_miss=None, worst=None, worst_d2=None, planted=None, clear=None, advance=None):
+    """lrm_edge_transit_posed_dev: does a planted foot stay reachable while the body moves from pose edge_a[e] to pose edge_b[e].
+    foothold_edges() looks at the two ends of an edge only; this call samples nsamples poses between them, the ends included:
+    the normalised linear blend of the two quaternions (the short way round: the great arc of slerp at another speed) and the
+    linear blend of the bodies.  quats float32 (nposes, 4) and body float32 (nposes, 3) or None are the tensors given to
+    update(); legs the host legs (1 to 8); edge_a / edge_b int32 device tensors; foot int32 [nlegs, nedges] on the device:
+    foothold_edges()'s best as it stands (-1 = the leg is in the air).  No table is read or written.
+    mask[l, e] (int64; bit s = sample s reaches), reached[l, e] (the number of bits; -1 when not planted), first_miss[l, e] (-1 if
+    none), worst[l, e] (the unreachable sample with the largest squared distance vector; -1 if none), worst_d2[l, e] (0 if none);
+    planted[e] (bit l = leg l is planted), clear[e] (1 iff live, both ends in range and every planted leg reaches at every
+    sample), advance[e] (the number of leading samples at which every planted leg reaches; 0 for a dead edge).
+    live_in: uint8 [nedges] on the device, 0 = dead.  Any index in edge_a, edge_b and foot is safe: one outside its range
+    makes the edge dead or the leg unplanted.  -> (mask, reached, first_miss, worst, worst_d2, planted, clear, advance); clear
+    is directly the live_in of the other posed calls.  Every tensor must be contiguous.  One launch, no allocation beyond
+    missing outputs, no shared buffer: it can be captured in a graph and may run next to anything."""
+    torch = _torch()
+    nt = _check_f32(tx, ty, tz)
+    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
+        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
+    nposes = quats.shape[0]
+    if nt and tx.device != quats.device:
+        raise ValueError("targets and poses must live on one device")
+    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
+                                 and tuple(body.shape) == (nposes, 3)):
+        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
+    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+    nl = len(legs)
+    if not 1 <= nl <= 8:
+        raise ValueError("legs: 1 to 8 legs")
+    ne = edge_a.numel()
+    _check_out(edge_a, quats, torch.int32, ne, "edge_a")
+    _check_out(edge_b, quats, torch.int32, ne, "edge_b")
+    if edge_b.numel() != ne:
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    if not (foot.is_cuda and foot.device == quats.device and foot.dtype == torch.int32 and foot.dim() == 2 and foot.is_contiguous()
+            and tuple(foot.shape) == (nl, ne)):
+        raise ValueError(f"foot: expected a contiguous int32 tensor of shape ({nl}, {ne}) on the poses' device")
+    _check_out(live_in, quats, torch.uint8, ne, "live_in")
+    if live_in is not None and live_in.numel() != ne:
+        raise ValueError("live_in: one byte per edge")
+    nsamples = _capi._nsamples(nsamples)
+    shape, n, dev = (nl, ne), nl * ne, quats.device
+    if mask is None:
+        mask = torch.empty(shape, dtype=torch.int64, device=dev)
+    if reached is None:
+        reached = torch.empty(shape, dtype=torch.int32, device=dev)
+    if first_miss is None:
+        first_miss = torch.empty(shape, dtype=torch.int32, device=dev)
+    if worst is None:
+        worst = torch.empty(shape, dtype=torch.int32, device=dev)
+    if worst_d2 is None:
+        worst_d2 = torch.empty(shape, dtype=torch.float32, device=dev)
+    if planted is None:
+        planted = torch.empty(ne, dtype=torch.uint8, device=dev)
+    if clear is None:
+        clear = torch.empty(ne, dtype=torch.uint8, device=dev)
+    if advance is None:
+        advance = torch.empty(ne, dtype=torch.int32, device=dev)
+    _check_out(mask, quats, torch.int64, n, "per-leg sample masks")
+    _check_out(reached, quats, torch.int32, n, "per-leg reached counts")
+    _check_out(first_miss, quats, torch.int32, n, "per-leg first misses")
+    _check_out(worst, quats, torch.int32, n, "per-leg worst samples")
+    _check_out(worst_d2, quats, torch.float32, n, "per-leg worst squared distances")
+    _check_out(planted, quats, torch.uint8, ne, "per-edge planted bits")
+    _check_out(clear, quats, torch.uint8, ne, "per-edge clear bytes")
+    _check_out(advance, quats, torch.int32, ne, "per-edge advances")
+    with torch.cuda.device(dev):
+        _capi.check(_capi.load().lrm_edge_transit_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _capi._ptr(legs),
+                                                            nl, _dp(edge_a), _dp(edge_b), ne, _dp(foot), nsamples, _dp(live_in), _dp(mask),
+                                                            _dp(reached), _dp(first_miss), _dp(worst), _dp(worst_d2), _dp(planted),
+                                                            _dp(clear), _dp(advance), _stream(quats)))
+    return mask, reached, first_miss, worst, worst_d2, planted, clear, advance
+
+
+def dbg_edge_transit_samples(quats, body, edge_a, edge_b, nsamples):
+    """lrm_dbg_edge_transit_samples_dev: the sampled path of edge_transit() -> float32 (nedges, nsamples, 7) on the device: the
+    quaternion and the body position of every sample (nan for an edge with an end out of range); one sample per lane."""
+    torch = _torch()
+    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
+        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
+    nposes = quats.shape[0]
+    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
+                                 and tuple(body.shape) == (nposes, 3)):
+        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
+    ne = edge_a.numel()
+    _check_out(edge_a, quats, torch.int32, ne, "edge_a")
+    _check_out(edge_b, quats, torch.int32, ne, "edge_b")
+    if edge_b.numel() != ne:
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    nsamples = _capi._nsamples(nsamples)
+    out = torch.empty((ne, nsamples, 7), dtype=torch.float32, device=quats.device)
+    with torch.cuda.device(quats.device):
+        _capi.check(_capi.load().lrm_dbg_edge_transit_samples_dev(_dp(quats), _dp(body), nposes, _dp(edge_a), _dp(edge_b), ne, nsamples,
+                                                                  _dp(out), _stream(quats)))
+    return out
+
+
 def dbg_link_pair_dist(segs, out=None):
     """lrm_dbg_link_pair_dist_dev: the link-pair distance of self_clearance() on segment pairs, segs float32 (n, 12) =
     A1, B1, A2, B2 on the device -> float32 (n,); one pair per lane."""
@@ -452,7 +550,8 @@ class PoseSet:
     links, and leg_joints() returns the joints it tests; stance_stability() asks whether the chosen footholds carry the
     centre of mass, and which legs can be lifted; self_clearance() (with ik=True) asks whether the legs fit next to each
     other under ik()'s angles: links of different legs against each other; trunk_clearance() (with ik=True) whether they
-    stay out of the robot's own trunk: leg links against the body cylinder."""
+    stay out of the robot's own trunk: leg links against the body cylinder; edge_transit() whether the feet that
+    foothold_edges() plants stay reachable at sampled poses between the two ends of a transition."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
         torch = _torch()
@@ -791,6 +890,29 @@ class PoseSet:
             raise ValueError(f"foot: expected an int32 tensor of shape ({self.nlegs}, nstances)")
         return stance_stability(tx, ty, tz, foot, quats, body, pose_idx, com, plane, lift, min_margin, live_in, margin, edge, stable,
                                 feet)
+
+    def edge_transit(self, tx, ty, tz, quats, body, edge_a, edge_b, foot, nsamples=9, live_in=None, mask=None, reached=None,
+                     first_miss=None, worst=None, worst_d2=None, planted=None, clear=None, advance=None, check=True):
+        """device.edge_transit() with this set's legs: quats (and body) are the tensors of the last update() -- the set keeps
+        compiled records, not the poses, and the call compiles the poses in between itself -- so their pose count must be the
+        set's; foot is foothold_edges()'s best [nlegs, nedges].  check=True validates edge_a / edge_b on the host (one
+        synchronisation), as foothold_edges() does; check=False leaves an index outside [0, nposes) to the kernel (a dead edge):
+        the form for graph capture.  -> (mask, reached, first_miss, worst, worst_d2 [nlegs, nedges]; planted, clear, advance
+        [nedges]); clear is the live_in of ik()'s callers and of stance_stability():
+        update -> footholds -> foothold_edges -> edge_transit -> ik / stance_stability(live_in = clear)."""
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if quats.dim() != 2 or quats.shape[0] != self.nposes:
+            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
+        if quats.device != self.workspace.device:
+            raise ValueError("quats and poses must live on one device")
+        if check and edge_a.numel() and edge_a.numel() == edge_b.numel():
+            lo = min(int(edge_a.min()), int(edge_b.min()))
+            hi = max(int(edge_a.max()), int(edge_b.max()))
+            if lo < 0 or hi >= self.nposes:
+                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
+        return edge_transit(tx, ty, tz, quats, body, self.legs, edge_a, edge_b, foot, nsamples, live_in, mask, reached, first_miss,
+                            worst, worst_d2, planted, clear, advance)
 
     def _check_angles(self, angles):
         torch = _torch()
