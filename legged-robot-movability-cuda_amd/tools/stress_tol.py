@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Randomised campaign for LRM_MODE_TOL on one GPU: random leg geometries and joint limits around the two reference
 robots, random body orientations, and clouds chosen to be hard -- uniform, far (beyond the inner grid of the plane table), near
-and far interleaved, the planar bench grid, a cluster around the coxa axis, and a cloud pushed ONTO the workspace boundary (every point moved along its own distance vector, then jittered
-by 1e-4 .. 1e-1 mm).  The bit-exact mode (LRM_MODE_FAST, itself checked bit for bit against the oracle by the test
+and far interleaved, the planar bench grid, a cluster around the coxa axis, a cloud pushed ONTO the workspace boundary (every point moved along its own distance vector, then jittered
+by 1e-4 .. 1e-1 mm), and two threshold shells (tests/shell_cases.py: the uniform and the planar cloud moved along their distance vectors to
+0.9 .. 1.6 times LRM_MODE_TOL_REL's replay threshold, where the relative error of the tolerance arithmetic is worst).  The bit-exact mode (LRM_MODE_FAST, itself checked bit for bit against the oracle by the test
 suite) is the reference, on the device: the reach mask and bit words must be identical, the distance field within the
 contract tolerance.  Prints one JSON line; exit code 1 on any violation.
 
@@ -15,7 +16,9 @@ import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))  # shell_cases.py: the shell generator the test suite uses
 
 
 def main():
@@ -33,7 +36,9 @@ def main():
     args = ap.parse_args()
     import torch
     import lrm_amd as lrm
+    import shell_cases
     rng = np.random.default_rng(args.seed)
+    shell_rng = np.random.default_rng([args.seed, 1])  # the shells draw from a generator of their own: the other clouds stay what they were
     n = args.points
     tol = 1e-5
     out = {"legs": 0, "tol_eligible": 0, "cases": 0, "evaluations": 0, "mask_mismatches": 0, "bit_word_mismatches": 0,
@@ -104,6 +109,12 @@ def main():
             _, d0, _ = run(lrm.MODE_FAST, t[0], t[1], t[2], leg, q)
             jitter = (10.0 ** rng.uniform(-4, -1, (n, 1))) * rng.normal(size=(n, 3))
             clouds["boundary"] = (u - d0.cpu().numpy().T + jitter).astype(np.float32)
+            # threshold shells of the uniform and the planar cloud (reachable seeds, whose vector is zero, give no shell point)
+            terms = shell_cases.band_terms(lrm, leg, q)
+            clouds["uni_shell"] = shell_cases.shell(u, d0.cpu().numpy().T, terms, *shell_cases.F_RANGE["uni_shell"], shell_rng)
+            t = torch.from_numpy(np.ascontiguousarray(clouds["grid"].T)).cuda()
+            _, d0, _ = run(lrm.MODE_FAST, t[0], t[1], t[2], leg, q)
+            clouds["grid_shell"] = shell_cases.shell(clouds["grid"], d0.cpu().numpy().T, terms, *shell_cases.F_RANGE["grid_shell"], shell_rng)
             for name, pts in clouds.items():
                 t = torch.from_numpy(np.ascontiguousarray(pts.T)).cuda()
                 m1, d1, b1 = run(lrm.MODE_STRICT if args.exact else lrm.MODE_FAST, t[0], t[1], t[2], leg, q)
