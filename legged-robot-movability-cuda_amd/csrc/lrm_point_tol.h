@@ -92,9 +92,6 @@
 #endif
 #define LRM_TD_SECOND 0x10000u // statistic only: the second candidate could not be pruned by its lower bound
 
-#ifndef LRM_TOL_DIET
-#define LRM_TOL_DIET 1
-#endif
 // -DLRM_PHASE_MARKS (tools/valu_phases.py only, never shipped): an s_nop at every phase boundary of the table evaluation, named in
 // the assembly by a comment; "rare" marks open the blocks that are not on the common path.
 #if defined(LRM_PHASE_MARKS) && defined(__HIP_DEVICE_COMPILE__)
@@ -105,7 +102,7 @@
 // min(|a|, |b|, c) and max(a, |b|) as ONE instruction each: fminf(fabsf(a), fabsf(b)) compiles to a canonicalising
 // v_max_f32 per operand in front of the v_min_f32 (IEEE mode), six instructions for a four-way minimum instead of two.
 // NaN operands are ignored, exactly as fminf / fmaxf ignore them.
-#if defined(__HIP_DEVICE_COMPILE__) && LRM_TOL_DIET
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ float lrm_min3_aa(float a, float b, float c) {
     float r;
     asm("v_min3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -121,7 +118,7 @@ LRM_HD float lrm_min3_aa(float a, float b, float c) { return fminf(fminf(fabsf(a
 LRM_HD float lrm_max_a(float a, float b) { return fmaxf(a, fabsf(b)); }
 #endif
 // min(|a|, |b|) as one instruction (the same value as fminf(fabsf(a), fabsf(b)), nan only when both are)
-#if defined(__HIP_DEVICE_COMPILE__) && LRM_TOL_DIET
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ float lrm_min_aa(float a, float b) {
     float r;
     asm("v_min_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
@@ -165,11 +162,7 @@ LRM_HD void lrm_tol_plane(const LrmTolLeg& L, const LrmTolTables T, float u, flo
     const float t_s0 = __builtin_fmaf(L.dir_cos[1], z, -(L.dir_sin[1] * x));
     const float t_s1 = __builtin_fmaf(L.dir_cos[2], z, -(L.dir_sin[2] * x));
     const uint32_t reg = lrm_region_from_signs(L.region_lut, t_mid, t_s0, t_s1, z) * LRM_N_CIRCLES;
-#if LRM_TOL_DIET
     const float macc = lrm_min3_aa(t_s1, t_s1, lrm_min3_aa(t_mid, t_s0, lrm_max_a(x, z)));
-#else
-    const float macc = fminf(fminf(fabsf(t_mid), fabsf(t_s0)), fminf(fabsf(t_s1), fmaxf(x, fabsf(z))));
-#endif
     float vacc = -3.0e38f, cacc = 3.0e38f;
     uint32_t lo = 0x7f80000fu, hi = 0x7f80000fu; // the two smallest keys: squared distance bits | candidate number
     const LrmTolLeg::Circle* ct = T.circ + reg;
@@ -197,11 +190,7 @@ LRM_HD void lrm_tol_plane(const LrmTolLeg& L, const LrmTolTables T, float u, flo
     }
     valid = vacc < 0.f;
     // corner points only matter when the point itself is invalid (one_leg.cu:109-116)
-#if LRM_TOL_DIET
     const uint32_t lo_circ = lo, hi_circ = hi; // ranking without the corner points: selected again after the loop
-#else
-    const uint32_t keep = valid ? 0u : 0xffffffffu;
-#endif
 #if defined(__HIP_DEVICE_COMPILE__)
     const int n_corners = __builtin_amdgcn_readfirstlane(L.n_corners); // a scalar also when the leg block lives in LDS
 #else
@@ -213,18 +202,13 @@ LRM_HD void lrm_tol_plane(const LrmTolLeg& L, const LrmTolTables T, float u, flo
             const LrmCircle c = T.feat[4 * LRM_N_CIRCLES + i];
             const float vx = x - c.x, vy = z - c.y;
             const float m = __builtin_fmaf(vy, vy, vx * vx);
-            uint32_t k = (lrm_f2u(m) & ~15u) | (uint32_t)(LRM_N_CIRCLES + i);
-#if !LRM_TOL_DIET
-            k = (k & keep) | (0x7f80000fu & ~keep);
-#endif
+            const uint32_t k = (lrm_f2u(m) & ~15u) | (uint32_t)(LRM_N_CIRCLES + i);
             hi = lrm_umed3(lo, hi, k);
             lo = lo < k ? lo : k;
         }
     }
-#if LRM_TOL_DIET
     lo = valid ? lo_circ : lo;
     hi = valid ? hi_circ : hi;
-#endif
     const float lo2 = lrm_u2f(lo & ~15u), hi2 = lrm_u2f(hi & ~15u);
     // |b - a| < tau  <=>  b^2 < a^2 + tau (2a + tau); the keys dropped 4 mantissa bits (< 2e-6 relative)
     const float a = LRM_FAST_SQRT(lo2);
@@ -290,9 +274,6 @@ inline const uint32_t* lrm_toltab_bound_inner(const uint8_t* tab) {
 #if defined(__HIP_DEVICE_COMPILE__)
 LRM_HD uint32_t lrm_tt_cell(const uint16_t* cells, uint32_t i) {
     typedef const __attribute__((address_space(1))) char* GP;
-#if defined(LRM_TAB_EXP_ONE_LINE) // timing experiment (wrong results): every look-up reads the same cache line
-    asm volatile("v_and_b32 %0, 31, %0" : "+v"(i));
-#endif
     return *(const __attribute__((address_space(1))) uint16_t*)((GP)cells + (i << 1));
 }
 LRM_HD float lrm_half_bits_to_float(uint32_t h) { // the low 16 bits (v_cvt_f32_f16 reads nothing else)
@@ -409,14 +390,8 @@ LRM_HD uint32_t lrm_toltab_resolve(const LrmTolTabView& G, uint32_t c, uint32_t 
 template <bool kInfo = false>
 LRM_HD void lrm_tol_plane_tab(const LrmTolTabView& G, uint32_t code, float x, float z, float band, float tau,
                               float& du, float& dz, bool& valid, uint32_t& doubt, uint32_t* row = nullptr) {
-#if defined(LRM_TAB_EXP_ONE_ROW) && defined(__HIP_DEVICE_COMPILE__) // timing experiment (wrong results): every lane reads the same rows -- no LDS bank conflicts
-    uint32_t code_rows = code;
-    asm volatile("v_and_b32 %0, 0x421, %0" : "+v"(code_rows));
-#else
-    const uint32_t code_rows = code;
-#endif
-    const LrmTabVRow vr = G.vrows[(code_rows >> 10) & 31u];
-    const LrmTabRow ra = G.rows[code_rows & 31u], rb = G.rows[(code_rows >> 5) & 31u];
+    const LrmTabVRow vr = G.vrows[(code >> 10) & 31u];
+    const LrmTabRow ra = G.rows[code & 31u], rb = G.rows[(code >> 5) & 31u];
     float vacc;
     {
         const float vx = x - vr.x, vy = z - vr.y;
@@ -582,11 +557,7 @@ LRM_HD bool lrm_tab_point(const LrmTolLeg& L, const LrmTolTabView& G, LrmVec3& p
     const bool need = two & !flag & !(n0 < b1 - tau * __builtin_fmaf(2.0f, LRM_FAST_SQRT(n0), tau));
     uint32_t codeC = code0; // kInfo: the winning candidate's own kind (codeW names the limit plane when the alternative won)
     bool flipC = !firstD;   //        and whether it is the flipped one
-#if defined(LRM_TAB_EXP_NO_SECOND) // timing experiment (wrong results): the second candidate is never evaluated
-    if (false) {
-#else
     if (LRM_TOL_ANY(need)) { // device: when a lane of the wave needs it (3 % of the waves of a random cloud); host: when this point does
-#endif
 #if !defined(__HIP_DEVICE_COMPILE__)
         lrm_tab_host_seconds++;
 #endif
@@ -829,11 +800,7 @@ LRM_HD LrmTolPoint lrm_tol_prologue(const LrmTolLeg& L, LrmVec3 p) {
     constexpr uint32_t kLutD = lrm_tol_lut(false), kLutF = lrm_tol_lut(true);
     const uint32_t codeD = (kLutD >> (pat << 1)) & 3u, codeF = (kLutF >> (pat << 1)) & 3u;
     const bool inD = (pat & 5u) == 1u, inF = (pat & 5u) == 4u;
-#if LRM_TOL_DIET
     const float ymin = lrm_min3_aa(wm, um, lrm_min3_aa(wM, uM, 3.0e38f));
-#else
-    const float ymin = fminf(fminf(fabsf(wM), fabsf(uM)), fminf(fabsf(wm), fabsf(um)));
-#endif
     S.lu = (!(ymin > S.band) || !(r > LRM_TOL_RMIN)) ? LRM_TD_YAW : 0u;
     S.two = codeD != codeF;
     // offsets of the two candidates' planes: 0 for a meridian plane, w of the limit for a limit plane

@@ -38,20 +38,11 @@
 #ifndef LRM_TOL_MIN_WAVES
 #define LRM_TOL_MIN_WAVES 8 // the staged kernel needs 59 VGPRs; its barriers like occupancy: 6 / 7 / 8 waves -> 123.0 / 122.3 / 119.9 us per step
 #endif
-#ifndef LRM_TOL_LEG_IN_LDS
-#define LRM_TOL_LEG_IN_LDS 0 // 1: the scalars too go through LDS (full-rate VGPR-only operands by the issue-class table, but measured 148 us against 114: the extra lgkmcnt waits cost more than the half-rate operands)
-#endif
 #ifndef LRM_TOL_BLOCK
 #define LRM_TOL_BLOCK 256
 #endif
-#ifndef LRM_TOL_STAGED
-#define LRM_TOL_STAGED 1
-#endif
 #ifndef LRM_TOL_SEG_PER_WAVE
 #define LRM_TOL_SEG_PER_WAVE 8 // segments one fix-up workgroup compacts: ~20 queued points at the usual 0.4 % of doubt, one pass of its first wave
-#endif
-#ifndef LRM_TOL_PREFETCH
-#define LRM_TOL_PREFETCH 1
 #endif
 #ifndef LRM_TOL_GRID_MULT
 #define LRM_TOL_GRID_MULT 8
@@ -140,8 +131,39 @@ struct QueueRec {
 };
 static_assert(sizeof(QueueRec) == 16, "one 16-byte store / load per queued point");
 
+// The point at byte offset `toff` (4 * its thread) of the round whose first point is `rbase`: wave-uniform base + 32-bit vector
+// offset (lrm_at).  kAoS: x is the float3 array of the apply_kernel boundary, y and z are unused.
+template <bool kAoS>
+__device__ __forceinline__ LrmVec3 load_point(const float* x, const float* y, const float* z, size_t rbase, uint32_t toff) {
+    return kAoS ? LrmVec3{lrm_at(x + 3 * rbase, 3u * toff), lrm_at(x + 3 * rbase, 3u * toff + 4u), lrm_at(x + 3 * rbase, 3u * toff + 8u)}
+                : LrmVec3{lrm_at(x + rbase, toff), lrm_at(y + rbase, toff), lrm_at(z + rbase, toff)};
+}
+// (A kernel's first load, in front of its table staging, stays written out: through this helper the compiler orders the scalar
+// address arithmetic of that one site differently.  The table staging and the doubt-queue push stay written out for the same
+// reason: as helpers they compile to other instructions.)
+
+// The vector p to the same place of the field (kAoS: dx is the float3 output, dy and dz are unused).  kNonTemporal: the table
+// kernels' SoA field is written once and never read by the kernels, and ordinary stores evict the inputs the next step re-reads
+// (the 1.25e7-point share of a 1e8 cloud cycles 312 MB through the 256 MiB Infinity Cache).
+template <bool kAoS, bool kNonTemporal>
+__device__ __forceinline__ void store_field(float* dx, float* dy, float* dz, size_t rbase, uint32_t toff, const LrmVec3& p) {
+    if (kAoS) {
+        lrm_at(dx + 3 * rbase, 3u * toff) = p.x;
+        lrm_at(dx + 3 * rbase, 3u * toff + 4u) = p.y;
+        lrm_at(dx + 3 * rbase, 3u * toff + 8u) = p.z;
+    } else if (kNonTemporal) {
+        __builtin_nontemporal_store(p.x, &lrm_at(dx + rbase, toff));
+        __builtin_nontemporal_store(p.y, &lrm_at(dy + rbase, toff));
+        __builtin_nontemporal_store(p.z, &lrm_at(dz + rbase, toff));
+    } else {
+        lrm_at(dx + rbase, toff) = p.x;
+        lrm_at(dy + rbase, toff) = p.y;
+        lrm_at(dz + rbase, toff) = p.z;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------
-// Staged variant (LRM_TOL_STAGED): every lane evaluates the more promising yaw candidate of its point; the lanes
+// Staged variant: every lane evaluates the more promising yaw candidate of its point; the lanes
 // whose second candidate can still win (lower bound on its norm, lrm_tol_need_second: ~25 % of a random cloud)
 // hand its PLANE evaluation -- four floats -- to the workgroup through LDS, where it runs compacted (one wave's
 // worth per 256 points instead of all four waves), and take (du, dz, valid, doubt) back.  Everything else, and every
@@ -158,8 +180,7 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
     __shared__ uint32_t s_cnt[2];
     __shared__ float4 s_task[kBlock]; // {u, z, band, tau} of a pending second plane evaluation
     __shared__ float4 s_res[kBlock];  // {du, dz, valid, doubt bits}
-    const LrmTolLeg& L = lrm_kernarg<LrmTolLeg>(kTolLegArg);
-#if LRM_TOL_PREFETCH
+    const LrmTolLeg& L = lrm_kernarg<LrmTolLeg>(kTolLegArg); // (its scalars stay in SGPRs: through LDS the extra lgkmcnt waits cost more than half-rate operands)
     // The point of the NEXT round is loaded while this round's second-candidate stage runs, the first one in front of the
     // table staging: the load latency leaves the critical path of the workgroup (three more VGPRs: 64, the limit of 8 waves).
     LrmVec3 p_next{0.f, 0.f, 0.f};
@@ -170,7 +191,6 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
         if (i0 < n) p_next = kAoS ? LrmVec3{lrm_at(x + 3 * rb0, 3u * to), lrm_at(x + 3 * rb0, 3u * to + 4u), lrm_at(x + 3 * rb0, 3u * to + 8u)}
                                   : LrmVec3{lrm_at(x + rb0, to), lrm_at(y + rb0, to), lrm_at(z + rb0, to)};
     }
-#endif
     {
         const float* csrc = reinterpret_cast<const float*>(&L.circ[0][0]);
         const float* fsrc = reinterpret_cast<const float*>(&L.feat[0]);
@@ -195,13 +215,7 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
         // scalar unit, the vector offset is a loop invariant -- no 64-bit address arithmetic on the vector unit
         const size_t rbase = (size_t)blockIdx.x * kBlock + (size_t)round * stride;
         const uint32_t toff = lrm_opaque(toff0), tid_o = lrm_opaque(threadIdx.x);
-#if LRM_TOL_PREFETCH
         LrmVec3 p = p_next;
-#else
-        LrmVec3 p{0.f, 0.f, 0.f};
-        if (live) p = kAoS ? LrmVec3{lrm_at(x + 3 * rbase, 3u * toff), lrm_at(x + 3 * rbase, 3u * toff + 4u), lrm_at(x + 3 * rbase, 3u * toff + 8u)}
-                           : LrmVec3{lrm_at(x + rbase, toff), lrm_at(y + rbase, toff), lrm_at(z + rbase, toff)};
-#endif
         // ---- A: first candidate ----
         const LrmTolPoint S = lrm_tol_prologue(L, p);
         const float short_mm = fmaxf(LRM_TOL_REL_MM, LRM_TOL_REL_BANDS * S.band); // LRM_MODE_TOL_REL's threshold (lrm_tol_rel_threshold)
@@ -220,23 +234,14 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
         const uint32_t slot = base + (uint32_t)__popcll(nm & ((1ull << lane) - 1ull));
         if (need) s_task[slot] = make_float4(S.u1, S.z, S.band, S.tau);
         if (threadIdx.x == 0) s_cnt[(round + 1u) & 1u] = 0; // nobody touches the other counter during this round
-#if !defined(LRM_TOL_EXP_NOBARRIER) // timing experiments only (wrong results)
         __syncthreads();
-#endif
-#if LRM_TOL_PREFETCH
         {
             const uint32_t i_next = i + stride;
             const size_t rb_next = rbase + stride;
             p_next = LrmVec3{0.f, 0.f, 0.f};
-            if (i_next < n) p_next = kAoS ? LrmVec3{lrm_at(x + 3 * rb_next, 3u * toff), lrm_at(x + 3 * rb_next, 3u * toff + 4u), lrm_at(x + 3 * rb_next, 3u * toff + 8u)}
-                                          : LrmVec3{lrm_at(x + rb_next, toff), lrm_at(y + rb_next, toff), lrm_at(z + rb_next, toff)};
+            if (i_next < n) p_next = load_point<kAoS>(x, y, z, rb_next, toff);
         }
-#endif
-#if defined(LRM_TOL_EXP_NOB)
-        const uint32_t total = 0;
-#else
         const uint32_t total = s_cnt[round & 1u];
-#endif
         // ---- B: the compacted second plane evaluations; the lanes that take them rotate from round to round ----
         {
             uint32_t t = threadIdx.x + (round % (uint32_t)(kBlock / 64)) * 64u; // (threadIdx.x + round * 64) mod kBlock
@@ -250,9 +255,7 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
                 s_res[t] = make_float4(bu, bz, bvalid ? 1.f : 0.f, lrm_u2f(bd));
             }
         }
-#if !defined(LRM_TOL_EXP_NOBARRIER)
         __syncthreads();
-#endif
         // ---- C: back with the owner ----
         LrmTolCand B = A;
         if (need) {
@@ -269,15 +272,7 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
             doubt |= (live && !(nn >= short_mm * short_mm)) ? 1u : 0u;
         }
         if (live) {
-            if (kAoS) {
-                lrm_at(dx + 3 * rbase, 3u * toff) = p.x;
-                lrm_at(dx + 3 * rbase, 3u * toff + 4u) = p.y;
-                lrm_at(dx + 3 * rbase, 3u * toff + 8u) = p.z;
-            } else {
-                lrm_at(dx + rbase, toff) = p.x;
-                lrm_at(dy + rbase, toff) = p.y;
-                lrm_at(dz + rbase, toff) = p.z;
-            }
+            store_field<kAoS, false>(dx, dy, dz, rbase, toff, p);
             if (mask) lrm_at(mask + rbase, tid_o) = m;
         }
         if (bits && i < (uint32_t)((n + 63) & ~(size_t)63)) { // wave-uniform
@@ -292,8 +287,7 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
             if (doubt) {
                 const uint32_t qs = qb + (uint32_t)__popcll(dm & ((1ull << lane) - 1ull));
                 if (qs < (uint32_t)kSegCap) { // beyond: the count tells the fix-up to redo the workgroup.  The point comes back from the L2 (loaded a round ago)
-                    const LrmVec3 q = kAoS ? LrmVec3{lrm_at(x + 3 * rbase, 3u * toff), lrm_at(x + 3 * rbase, 3u * toff + 4u), lrm_at(x + 3 * rbase, 3u * toff + 8u)}
-                                           : LrmVec3{lrm_at(x + rbase, toff), lrm_at(y + rbase, toff), lrm_at(z + rbase, toff)};
+                    const LrmVec3 q = load_point<kAoS>(x, y, z, rbase, toff);
                     seg[qs] = QueueRec{i, q.x, q.y, q.z};
                 }
             }
@@ -331,17 +325,6 @@ __global__ __launch_bounds__(kBlock, LRM_TOL_MIN_WAVES) void dist_tol_staged_ker
 #ifndef LRM_SHORT_MIN_WAVES
 #define LRM_SHORT_MIN_WAVES 6 // LRM_MODE_TOL_REL's variant carries the info word, the in-loop flush and the replay tail: 80 VGPRs + 12 bytes of scratch per lane (the flush) at 6 waves: 92.2 us; 96 VGPRs at 5 waves: 96.2
 #endif
-#ifndef LRM_TAB_PREFETCH2
-#define LRM_TAB_PREFETCH2 0 // two rounds of loads in flight per wave (6 waves/SIMD): 80 / 123 / 933 us at 1e7 / 1.25e7 / 1e8 points against 75 / 119 / 891 (profiles/r04_ab_prefetch_nt.txt)
-#endif
-#ifndef LRM_TAB_NT_STORE
-#define LRM_TAB_NT_STORE 1 // the distance field is written once and never read by the kernels: non-temporal stores.  Nothing at 1e7 points (71.7 -> 70.8 us:
-                           // inputs and outputs fit the 256 MiB Infinity Cache together) or 1e8 (822 -> 827), but the 1.25e7-point share of the 1e8 cloud --
-                           // 312 MB cycling through a 256 MiB cache -- 117.7 -> 85.9 us: ordinary stores evict the inputs the next step re-reads
-#endif
-#ifndef LRM_TAB_NT_LOAD
-#define LRM_TAB_NT_LOAD 0 // non-temporal loads of the points as well: 72 -> 89 / 91 -> 109 / 800 -> 809 us at 1e7 / 1.25e7 / 1e8 points: no
-#endif
 struct TabLds {
     LrmTabRow rows[32];
     LrmTabVRow vrows[32];
@@ -349,15 +332,6 @@ struct TabLds {
 constexpr int kTabSegCap = LRM_TOL_TAB_SEG_CAP; // doubt slots per workgroup of dist_tab_kernel
 #ifndef LRM_SHORT_CAP
 #define LRM_SHORT_CAP 64 // LDS slots per wave for the short vectors of LRM_MODE_TOL_REL (~15 expected over a wave's five rounds; a segment without room for a round's records is replayed on the spot)
-#endif
-// The replayed vectors leave with non-temporal stores as well: ordinary ones make the L2 fetch the rest of each line (the tolerance
-// vectors of the neighbours, streamed out moments before) from memory: 92.97 -> 88.34 us per 1e7 points, 128.2 -> 108.1 us per 1.25e7
-// (profiles/r04_ab_rel_fixup.txt; the fix-up's few stores gain nothing from it: 14.2 -> 14.3 us, 14.6 -> 16.5 at 1.25e7)
-#ifndef LRM_REPLAY_NT_STORE
-#define LRM_REPLAY_NT_STORE 1
-#endif
-#ifndef LRM_SHORT_TAIL_WAIT
-#define LRM_SHORT_TAIL_WAIT 1
 #endif
 constexpr int kShortCap = LRM_SHORT_CAP;
 static_assert(kShortCap == 64, "an emptied segment holds exactly one round of a wave, and the in-loop flush replays one record per lane: a larger cap would drop records");
@@ -381,20 +355,12 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
     const LrmTolLeg& L = lrm_kernarg<LrmTolLeg>(kTolLegArg);
     const LrmTolTabHeader* hd = reinterpret_cast<const LrmTolTabHeader*>(tab);
     LrmVec3 p_next{0.f, 0.f, 0.f}; // the first point in front of the table staging
-#if LRM_TAB_PREFETCH2
-    LrmVec3 p_next2{0.f, 0.f, 0.f}; // and the second round's: two rounds of loads in flight per wave (clouds beyond the Infinity Cache wait for HBM)
-#endif
     {
         const uint32_t i0 = blockIdx.x * kBlock + threadIdx.x;
         const size_t rb0 = (size_t)blockIdx.x * kBlock;
         const uint32_t to = lrm_opaque(threadIdx.x * 4u);
         if (i0 < n) p_next = kAoS ? LrmVec3{lrm_at(x + 3 * rb0, 3u * to), lrm_at(x + 3 * rb0, 3u * to + 4u), lrm_at(x + 3 * rb0, 3u * to + 8u)}
                                   : LrmVec3{lrm_at(x + rb0, to), lrm_at(y + rb0, to), lrm_at(z + rb0, to)};
-#if LRM_TAB_PREFETCH2
-        const size_t rb1 = rb0 + (size_t)gridDim.x * kBlock;
-        if (i0 + gridDim.x * kBlock < n) p_next2 = kAoS ? LrmVec3{lrm_at(x + 3 * rb1, 3u * to), lrm_at(x + 3 * rb1, 3u * to + 4u), lrm_at(x + 3 * rb1, 3u * to + 8u)}
-                                                       : LrmVec3{lrm_at(x + rb1, to), lrm_at(y + rb1, to), lrm_at(z + rb1, to)};
-#endif
     }
     {
         static_assert(sizeof(TabLds) == sizeof(hd->rows) + sizeof(hd->vrows) && sizeof(TabLds) % 16 == 0, "rows | vrows");
@@ -424,23 +390,14 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
             const size_t i = r[0];
             LrmVec3 q{lrm_u2f(r[1]), lrm_u2f(r[2]), lrm_u2f(r[3])};
             lrm_xtab_replay(lrm_fresh(X), s_tab.rows, q, r[4]);
-#if defined(LRM_EXP_NOSCATTER) // timing experiment (wrong results): the replayed vectors are computed but (practically) never stored
-            if (!(q.x != q.x)) return;
-#endif
             if (kAoS) {
                 dx[3 * i] = q.x;
                 dx[3 * i + 1] = q.y;
                 dx[3 * i + 2] = q.z;
-            } else {
-#if LRM_REPLAY_NT_STORE
+            } else { // non-temporal: an ordinary store makes the L2 fetch the rest of the line, the neighbours' vectors streamed out moments before
                 __builtin_nontemporal_store(q.x, dx + i);
                 __builtin_nontemporal_store(q.y, dy + i);
                 __builtin_nontemporal_store(q.z, dz + i);
-#else
-                dx[i] = q.x;
-                dy[i] = q.y;
-                dz[i] = q.z;
-#endif
             }
         }
     };
@@ -459,39 +416,17 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
         const uint32_t toff = lrm_opaque(toff0), tid_o = lrm_opaque(threadIdx.x);
         LRM_PHASE("0_loop_head_prefetch");
         LrmVec3 p = p_next;
-#if LRM_TAB_PREFETCH2
-        {   // the points of the next two rounds are in flight while this one is evaluated
-            const uint32_t i_next = i + 2u * stride;
-            const size_t rb_next = rbase + 2 * (size_t)stride;
-            p_next = p_next2;
-            p_next2 = LrmVec3{0.f, 0.f, 0.f};
-            if (i_next < n32 && i_next > i) p_next2 = kAoS ? LrmVec3{lrm_at(x + 3 * rb_next, 3u * toff), lrm_at(x + 3 * rb_next, 3u * toff + 4u), lrm_at(x + 3 * rb_next, 3u * toff + 8u)}
-                                                          : LrmVec3{lrm_at(x + rb_next, toff), lrm_at(y + rb_next, toff), lrm_at(z + rb_next, toff)};
-        }
-#else
         {   // the next round's point is in flight while this one is evaluated
             const uint32_t i_next = i + stride;
             const size_t rb_next = rbase + stride;
             p_next = LrmVec3{0.f, 0.f, 0.f};
-#if LRM_TAB_NT_LOAD
-            if (i_next < n32) p_next = kAoS ? LrmVec3{lrm_at(x + 3 * rb_next, 3u * toff), lrm_at(x + 3 * rb_next, 3u * toff + 4u), lrm_at(x + 3 * rb_next, 3u * toff + 8u)}
-                                          : LrmVec3{__builtin_nontemporal_load(&lrm_at(x + rb_next, toff)), __builtin_nontemporal_load(&lrm_at(y + rb_next, toff)), __builtin_nontemporal_load(&lrm_at(z + rb_next, toff))};
-#else
-            if (i_next < n32) p_next = kAoS ? LrmVec3{lrm_at(x + 3 * rb_next, 3u * toff), lrm_at(x + 3 * rb_next, 3u * toff + 4u), lrm_at(x + 3 * rb_next, 3u * toff + 8u)}
-                                          : LrmVec3{lrm_at(x + rb_next, toff), lrm_at(y + rb_next, toff), lrm_at(z + rb_next, toff)};
-#endif
+            if (i_next < n32) p_next = load_point<kAoS>(x, y, z, rb_next, toff);
         }
-#endif
         uint32_t doubt = 0;
         const LrmVec3 p_in = p; // kept for the queue record (three registers; re-loading it cost a pushing wave an L2 round trip)
         uint32_t info = 0; // kShort: what the evaluation decided (the tail replays the winner's value chain from it)
-#if defined(LRM_EXP_NOINFO) // timing experiment (wrong results): the decisions are not packed
-        float band = 0.f;
-        const bool m = lrm_tab_point<false>(L, G, p, doubt, &info, &band) && live;
-#else
         float band = 0.f; // the point's decision band (mm)
         const bool m = lrm_tab_point<kShort>(L, G, p, doubt, &info, &band) && live;
-#endif
         LRM_PHASE("6_short_test_stores_queues");
         doubt = live ? ((doubt & 0xffffu) | (selftest & 1u)) : 0u; // selftest: every point goes to the fix-up
         bool is_short = false;
@@ -501,21 +436,7 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
             is_short = live & (doubt == 0u) & !(nn >= short_mm * short_mm);
         }
         if (live) {
-            if (kAoS) {
-                lrm_at(dx + 3 * rbase, 3u * toff) = p.x;
-                lrm_at(dx + 3 * rbase, 3u * toff + 4u) = p.y;
-                lrm_at(dx + 3 * rbase, 3u * toff + 8u) = p.z;
-            } else {
-#if LRM_TAB_NT_STORE // streaming stores of the field: see LRM_TAB_NT_STORE above
-                __builtin_nontemporal_store(p.x, &lrm_at(dx + rbase, toff));
-                __builtin_nontemporal_store(p.y, &lrm_at(dy + rbase, toff));
-                __builtin_nontemporal_store(p.z, &lrm_at(dz + rbase, toff));
-#else
-                lrm_at(dx + rbase, toff) = p.x;
-                lrm_at(dy + rbase, toff) = p.y;
-                lrm_at(dz + rbase, toff) = p.z;
-#endif
-            }
+            store_field<kAoS, true>(dx, dy, dz, rbase, toff, p);
             if (mask) lrm_at(mask + rbase, tid_o) = m;
         }
         if (bits) {
@@ -524,11 +445,7 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
         }
         if (kShort) { // the wave's LDS segment; a record that finds no room goes to the doubt queue instead (the filtered code takes it)
             const uint64_t sm = __ballot(is_short);
-#if defined(LRM_EXP_NOPUSH) // timing experiment (wrong results): the short vectors are never recorded
-            if (false) {
-#else
             if (sm) {
-#endif
                 // A segment without room for this round's records is replayed on the spot by its own wave (a cloud of reachable
                 // points only has 35 % short vectors: sending what does not fit to the doubt queue made its workgroups overflow and
                 // the filtered code redo them whole, 0.71 ms per 1e7 points; profiles/r04_bench_a.json).  The earlier stores of the
@@ -568,19 +485,13 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
     }
     LRM_PHASE("end_of_loop");
     if (kShort && lane == 0) s_wcnt[wave_s] = wq;
-#if LRM_SHORT_TAIL_WAIT
     // The replayed vectors below overwrite tolerance vectors stored by OTHER waves of this workgroup: every wave first waits until
     // its own stores have been acknowledged by the L2 (the workgroup-scope fence of __syncthreads does not: one CU, one L1 -- it
     // relies on the CU's stores to one address reaching the L2 in issue order).
     if (kShort) __builtin_amdgcn_s_waitcnt(0);
-#endif
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = s_qn;
-#if defined(LRM_EXP_NOTAIL) // timing experiment (wrong results): the short vectors are recorded but never replayed
-    if (false) {
-#else
     if (kShort) {
-#endif
         // ---- the tail: what is left in the four segments, compacted over the workgroup's waves (usually its first wave alone) ----
         static_assert(kBlock / 64 == 4, "four wave segments");
         const uint32_t c0 = s_wcnt[0], c1 = c0 + s_wcnt[1], c2 = c1 + s_wcnt[2], total = c2 + s_wcnt[3];
@@ -661,28 +572,13 @@ __global__ __launch_bounds__(kBlock, LRM_XTAB_MIN_WAVES) void dist_xtab_kernel(
             const uint32_t i_next = i + stride;
             const size_t rb_next = rbase + stride;
             p_next = LrmVec3{0.f, 0.f, 0.f};
-            if (i_next < n32) p_next = kAoS ? LrmVec3{lrm_at(x + 3 * rb_next, 3u * toff), lrm_at(x + 3 * rb_next, 3u * toff + 4u), lrm_at(x + 3 * rb_next, 3u * toff + 8u)}
-                                          : LrmVec3{lrm_at(x + rb_next, toff), lrm_at(y + rb_next, toff), lrm_at(z + rb_next, toff)};
+            if (i_next < n32) p_next = load_point<kAoS>(x, y, z, rb_next, toff);
         }
         uint32_t doubt = 0;
         const bool m = lrm_xtab_point(lrm_fresh(X), G, p, doubt) && live;
         doubt = live ? ((doubt & 0xffffu) | (selftest & 1u)) : 0u;
         if (live) {
-            if (kAoS) {
-                lrm_at(dx + 3 * rbase, 3u * toff) = p.x;
-                lrm_at(dx + 3 * rbase, 3u * toff + 4u) = p.y;
-                lrm_at(dx + 3 * rbase, 3u * toff + 8u) = p.z;
-            } else {
-#if LRM_TAB_NT_STORE
-                __builtin_nontemporal_store(p.x, &lrm_at(dx + rbase, toff));
-                __builtin_nontemporal_store(p.y, &lrm_at(dy + rbase, toff));
-                __builtin_nontemporal_store(p.z, &lrm_at(dz + rbase, toff));
-#else
-                lrm_at(dx + rbase, toff) = p.x;
-                lrm_at(dy + rbase, toff) = p.y;
-                lrm_at(dz + rbase, toff) = p.z;
-#endif
-            }
+            store_field<kAoS, true>(dx, dy, dz, rbase, toff, p);
             if (mask) lrm_at(mask + rbase, tid_o) = m;
         }
         if (bits) {
@@ -697,8 +593,7 @@ __global__ __launch_bounds__(kBlock, LRM_XTAB_MIN_WAVES) void dist_xtab_kernel(
             if (doubt) {
                 const uint32_t qs = qb + (uint32_t)__popcll(dm & ((1ull << lane) - 1ull));
                 if (qs < (uint32_t)kTabSegCap) {
-                    const LrmVec3 q = kAoS ? LrmVec3{lrm_at(x + 3 * rbase, 3u * toff), lrm_at(x + 3 * rbase, 3u * toff + 4u), lrm_at(x + 3 * rbase, 3u * toff + 8u)}
-                                           : LrmVec3{lrm_at(x + rbase, toff), lrm_at(y + rbase, toff), lrm_at(z + rbase, toff)};
+                    const LrmVec3 q = load_point<kAoS>(x, y, z, rbase, toff);
                     seg[qs] = QueueRec{i, q.x, q.y, q.z};
                 }
             }
