@@ -3,7 +3,8 @@
 robots, random body orientations, and clouds chosen to be hard -- uniform, far (beyond the inner grid of the plane table), near
 and far interleaved, the planar bench grid, a cluster around the coxa axis, a cloud pushed ONTO the workspace boundary (every point moved along its own distance vector, then jittered
 by 1e-4 .. 1e-1 mm), and two threshold shells (tests/shell_cases.py: the uniform and the planar cloud moved along their distance vectors to
-0.9 .. 1.6 times LRM_MODE_TOL_REL's replay threshold, where the relative error of the tolerance arithmetic is worst).  The bit-exact mode (LRM_MODE_FAST, itself checked bit for bit against the oracle by the test
+0.9 .. 1.6 times LRM_MODE_TOL_REL's replay threshold, where the relative error of the tolerance arithmetic is worst), and the eight families of
+tests/lattice_cases.py: points within 1e-4 mm of the plane table's own cell lines, on the seam between its two grids, at the end of the outer grid and beyond it.  The bit-exact mode (LRM_MODE_FAST, itself checked bit for bit against the oracle by the test
 suite) is the reference, on the device: the reach mask and bit words must be identical, the distance field within the
 contract tolerance.  Prints one JSON line; exit code 1 on any violation.
 
@@ -18,7 +19,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-sys.path.insert(1, os.path.join(ROOT, "tests"))  # shell_cases.py: the shell generator the test suite uses
+sys.path.insert(1, os.path.join(ROOT, "tests"))  # shell_cases.py, lattice_cases.py: the generators the test suite uses
 
 
 def main():
@@ -37,13 +38,19 @@ def main():
     import torch
     import lrm_amd as lrm
     import shell_cases
+    try:  # the lattice families come with the test suite's generator; a tree whose tests/ has none runs the other clouds, and says so
+        import lattice_cases
+    except ImportError:
+        lattice_cases = None
+        print("tests/lattice_cases.py not found: the campaign runs without the plane table's lattice families", file=sys.stderr, flush=True)
     rng = np.random.default_rng(args.seed)
     shell_rng = np.random.default_rng([args.seed, 1])  # the shells draw from a generator of their own: the other clouds stay what they were
+    lattice_seed = 0  # and so do the lattice families: one seed per (leg, orientation)
     n = args.points
     tol = 1e-5
     out = {"legs": 0, "tol_eligible": 0, "cases": 0, "evaluations": 0, "mask_mismatches": 0, "bit_word_mismatches": 0,
            "nonfinite": 0, "max_err": 0.0, "worst": None, "max_queued_fraction": 0.0, "mean_queued_fraction": 0.0,
-           "overflowed_segments": 0}
+           "overflowed_segments": 0, "lattice_families": len(lattice_cases.FAMILIES) if lattice_cases else 0}
     queued = []
 
     def run(mode, x, y, z, leg, q):
@@ -115,6 +122,10 @@ def main():
             t = torch.from_numpy(np.ascontiguousarray(clouds["grid"].T)).cuda()
             _, d0, _ = run(lrm.MODE_FAST, t[0], t[1], t[2], leg, q)
             clouds["grid_shell"] = shell_cases.shell(clouds["grid"], d0.cpu().numpy().T, terms, *shell_cases.F_RANGE["grid_shell"], shell_rng)
+            # the plane table's own lattice and seams (the yaw limits are fields 9 and 8 of the leg: no orientation changes them)
+            lattice_seed += 1
+            for family in (lattice_cases.FAMILIES if lattice_cases else ()):
+                clouds[family] = lattice_cases.make(family, n, leg, q, (float(leg[9]), float(leg[8])), 1000 * args.seed + lattice_seed)
             for name, pts in clouds.items():
                 t = torch.from_numpy(np.ascontiguousarray(pts.T)).cuda()
                 m1, d1, b1 = run(lrm.MODE_STRICT if args.exact else lrm.MODE_FAST, t[0], t[1], t[2], leg, q)

@@ -11,20 +11,17 @@ LRM_MODE_TOL).  The kernel's threshold appears in one assertion only, the margin
 replayed) must meet 1e-5 on every vector at least as long as the threshold at its point -- the contract restated; threshold /
 crossover is the margin.  The bound remains empirical: no forward-error derivation stands behind it."""
 import functools
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import shell_cases as sc
-from conftest import bits_equal
-from tolcheck import TOL, field_error
+from tolcheck import TOL, check_rel, field_error, oracle_parallel, packed, run_reach_dist, soa
 
 pytestmark = pytest.mark.gpu
 
 N = 200_000   # per case: the table kernel is the default from this size on
 SEED = 1
-WORKERS = 16
 OVERFLOW_KEY = ("uni_shell", "m2_a", "tilt_y")
 OVERFLOW_N = 400_000
 
@@ -40,24 +37,6 @@ def torch_cuda():
 def back_to_fast(lrm):
     yield
     lrm.set_mode(lrm.MODE_FAST)
-
-
-def soa(torch, pts):
-    return tuple(torch.from_numpy(np.ascontiguousarray(pts[:, k])).cuda() for k in range(3))
-
-
-def packed(mask):
-    n = len(mask)
-    return np.packbits(np.pad(mask, (0, (-n) % 64)), bitorder="little").view(np.uint64)
-
-
-def oracle_parallel(oracle, pts, leg, q):
-    """(reach mask, vectors, validity) of the oracle, the cloud split over WORKERS threads (the library calls release the GIL)"""
-    parts = np.array_split(np.arange(len(pts)), WORKERS)
-    parts = [p for p in parts if len(p)]
-    with ThreadPoolExecutor(WORKERS) as ex:
-        res = list(ex.map(lambda idx: (oracle.reach(pts[idx[0]:idx[-1] + 1], leg, q), oracle.dist(pts[idx[0]:idx[-1] + 1], leg, q)), parts))
-    return np.concatenate([r[0] for r in res]), np.concatenate([r[1][0] for r in res]), np.concatenate([r[1][1] for r in res])
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,39 +62,6 @@ def check_case_conditions(key, c):
     assert c["in_band"] >= sc.MIN_IN_BAND, (key, c["in_band"])
     if key[0] == "mix_shell":
         assert c["short"] >= sc.MIN_SHORT_MIX, (key, c["short"])
-
-
-def check_rel(name, c, d, flags=None, want_flags=None, bits=None):
-    """the literal contract on EVERY point: flags bit for bit, |d - d_ref| <= 1e-5 |d_ref|, vectors below 16 mm bit-identical
-    -> (worst literal error, |d_ref| there, thr there)"""
-    d = np.ascontiguousarray(d, np.float32)
-    if flags is not None:
-        assert np.array_equal(np.asarray(flags).astype(bool), np.asarray(want_flags).astype(bool)), f"{name}: flags differ from the oracle"
-    if bits is not None:
-        assert np.array_equal(np.asarray(bits).view(np.uint64), packed(c["m"])), f"{name}: ballot words differ from the oracle"
-    nref = c["nref"]
-    err = np.linalg.norm(d.astype(np.float64) - c["d"].astype(np.float64), axis=1)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        lit = np.where(nref > 0, err / nref, np.where(err > 0, np.inf, 0.0))
-    i = int(np.argmax(lit))
-    print(f"{name}: worst literal error {lit[i]:.3e} at |d_ref| = {nref[i]:.3f} mm (thr {c['thr'][i]:.3f} mm, point {c['pts'][i].tolist()}); "
-          f"worst absolute error {err.max():.3e} mm")
-    assert (err <= TOL * nref).all(), f"{name}: literal error {lit[i]:.3e} at |d_ref| = {nref[i]:.3f} mm, thr {c['thr'][i]:.3f} mm, point {c['pts'][i].tolist()}"
-    short = nref < 16.0
-    assert bits_equal(d[short], c["d"][short]).all(), f"{name}: a vector below 16 mm is not bit-identical"
-    return float(lit[i]), float(nref[i]), float(c["thr"][i])
-
-
-def run_reach_dist(lrm, torch, c, mode):
-    x, y, z = soa(torch, c["pts"])
-    n = len(c["pts"])
-    lrm.set_mode(mode)
-    bits = torch.empty((n + 63) // 64, dtype=torch.int64, device="cuda")
-    m, d, bits = lrm.device.reach_dist(x, y, z, c["leg"], c["q"], mask=torch.empty(n, dtype=torch.uint8, device="cuda"), bits=bits)
-    torch.cuda.synchronize()
-    counts = lrm.dbg_tol_queue_counts() if mode != lrm.MODE_FAST else None
-    lrm.set_mode(lrm.MODE_FAST)
-    return m.cpu().numpy(), d.cpu().numpy().T, bits.cpu().numpy(), counts
 
 
 @pytest.mark.parametrize("key", sc.case_keys(), ids=sc.case_id)
