@@ -1119,10 +1119,19 @@ void lrm_multi_release(void);
 /* ---- diagnostics -------------------------------------------------------------------------
  * The glibc-exact atan2f / sincosf of the strict kernels (csrc/lrm_exact_math.h) applied to
  * arrays: at2[i] = atan2f(a[i], b[i]); (sn[i], cs[i]) = sincosf(a[i]).  Host build and device
- * build; tests compare both with the platform libm. */
+ * build; tests compare the host build with the platform libm and the device build with the host build. */
 int lrm_dbg_exact_math_host(const float* a, const float* b, size_t n, float* at2, float* sn, float* cs);
 int lrm_dbg_exact_math_dev(const float* a, const float* b, size_t n, float* at2, float* sn, float* cs,
                            void* stream);
+/* Block checksums of the same header's one-argument functions over float bit patterns (csrc/lrm_dbg_math.h), for comparing
+ * the device build with the host build on EVERY float.  The 2^32 patterns u form 65536 blocks of 65536: block b holds
+ * u = b * 65536 + j.  fn: 0 lrm_atanf(x), 1 the sine, 2 the cosine of lrm_sincosf(x).  With r(u) the result's bits, every nan
+ * replaced by 0x7fc00000, sums_out[k] = sum_j r(u) * (2 j + 1) mod 2^64 of block first_block + k, k < nblocks: the weights are
+ * odd, so one wrong result in a block changes its sum.  first_block + nblocks <= 65536; nblocks == 0 writes nothing.  Host:
+ * at most 16 threads (LRM_DBG_MATH_THREADS sets fewer).  Device: sums_out is device memory, one workgroup per block, one
+ * launch on `stream`. */
+int lrm_dbg_exact_math_sums_host(int fn, uint32_t first_block, uint32_t nblocks, uint64_t* sums_out);
+int lrm_dbg_exact_math_sums_dev(int fn, uint32_t first_block, uint32_t nblocks, uint64_t* sums_out, void* stream);
 /* The link-pair distance of lrm_self_clearance_posed_dev (csrc/lrm_self_clearance.h) on n hand-made segment pairs: segs holds
  * 12 floats per pair, A1, B1, A2, B2 as x, y, z; out[i] = d of pair i.  Host build and device build (one pair per lane); the
  * tests hold the branchy distance to the text above on them. */

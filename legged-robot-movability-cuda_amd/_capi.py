@@ -101,6 +101,8 @@ def load():
         "lrm_dbg_pair_sphere": [vp, vp, vp],
         "lrm_dbg_exact_math_host": [vp, vp, sz, vp, vp, vp],
         "lrm_dbg_exact_math_dev": [vp, vp, sz, vp, vp, vp, vp],
+        "lrm_dbg_exact_math_sums_host": [C.c_int, C.c_uint32, C.c_uint32, vp],
+        "lrm_dbg_exact_math_sums_dev": [C.c_int, C.c_uint32, C.c_uint32, vp, vp],
         "lrm_dbg_sqrt_check_dev": [vp, vp],
         "lrm_any_in_sphere_dev": [vp, vp, vp, sz, vp, vp, vp, sz, fp, vp, vp],
         "lrm_any_in_cylinder_dev": [vp, vp, vp, sz, vp, vp, vp, sz, fp, fp, fp, vp, vp],

@@ -27,6 +27,7 @@
 #include "lrm_trunk_clearance.h"
 #include "lrm_edge_transit.h"
 #include "lrm_ik.h"
+#include "lrm_dbg_math.h"
 #include "lrm_launch.h"
 #include "lrm_point.h"
 #include "lrm_point_fast.h"
@@ -2516,6 +2517,46 @@ int lrm_dbg_exact_math_dev(const float* a, const float* b, size_t n, float* at2,
     if (n && (!a || !b || !at2 || !sn || !cs)) return fail(LRM_EINVAL, "null argument");
     if (n == 0) return LRM_OK;
     HIP_TRY(lrm_launch_exact_math(a, b, n, at2, sn, cs, (hipStream_t)stream), "exact_math launch");
+    return LRM_OK;
+}
+
+// ---- diagnostics: block checksums of lrm_atanf / lrm_sincosf over float bit patterns (lrm_dbg_math.h) --------
+namespace {
+int sums_args_ok(int fn, uint32_t first_block, uint32_t nblocks, const uint64_t* sums_out) {
+    if (fn < 0 || fn >= LRM_DBG_MATH_FNS) return fail(LRM_EINVAL, "fn must be 0 (atanf), 1 (sin) or 2 (cos)");
+    if (first_block > LRM_DBG_MATH_BLOCKS || nblocks > LRM_DBG_MATH_BLOCKS - first_block)
+        return fail(LRM_EINVAL, "first_block + nblocks exceeds the 65536 blocks of the domain");
+    if (nblocks && !sums_out) return fail(LRM_EINVAL, "null argument");
+    return LRM_OK;
+}
+void sums_host_blocks(int fn, uint32_t first_block, uint32_t nblocks, int t, int threads, uint64_t* sums_out) {
+    for (uint32_t b = (uint32_t)t; b < nblocks; b += (uint32_t)threads)
+        sums_out[b] = fn == 0   ? lrm_dbg_math_block_sum<0>(first_block + b)
+                      : fn == 1 ? lrm_dbg_math_block_sum<1>(first_block + b)
+                                : lrm_dbg_math_block_sum<2>(first_block + b);
+}
+} // namespace
+
+int lrm_dbg_exact_math_sums_host(int fn, uint32_t first_block, uint32_t nblocks, uint64_t* sums_out) {
+    if (int rc = sums_args_ok(fn, first_block, nblocks, sums_out)) return rc;
+    // the pool is sized as the table builder's (lrm_toltab.cpp), to 16 threads at the most; blocks are independent
+    int threads = (int)std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : (threads > 16 ? 16 : threads);
+    if (const char* e = std::getenv("LRM_DBG_MATH_THREADS")) threads = std::min(16, std::max(1, std::atoi(e)));
+    if ((uint32_t)threads > nblocks) threads = nblocks ? (int)nblocks : 1;
+    auto work = [&](int t) { sums_host_blocks(fn, first_block, nblocks, t, threads, sums_out); };
+    if (threads <= 1) work(0);
+    else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; t++) pool.emplace_back(work, t);
+        for (auto& th : pool) th.join();
+    }
+    return LRM_OK;
+}
+int lrm_dbg_exact_math_sums_dev(int fn, uint32_t first_block, uint32_t nblocks, uint64_t* sums_out, void* stream) {
+    if (int rc = sums_args_ok(fn, first_block, nblocks, sums_out)) return rc;
+    if (nblocks == 0) return LRM_OK;
+    HIP_TRY(lrm_launch_exact_math_sums(fn, first_block, nblocks, sums_out, (hipStream_t)stream), "exact_math_sums launch");
     return LRM_OK;
 }
 

@@ -14,10 +14,18 @@
 //    Nagy, 2018; glibc sysdeps/ieee754/flt-32/s_sincosf.h): reduction by pi/2 with a scaled
 //    float->int conversion, degree-9/8 polynomials in double.  glibc's x86-64 build selects
 //    its FMA variant on AVX2 hosts; with fused multiply-adds this restatement matches that
-//    variant on all 2.2e9 floats with |x| < 120, and with or without FMA on |x| < 7 (the
-//    only range the path produces: angles in [-2pi, 2pi]).  tests/test_capi_cpu.py (host build against this
-//    machine's glibc) and tests/test_gpu_parity.py (device build against the host build) check it.
-//    |x| >= 120 (never produced by the path) is answered with nan, like inf and nan.
+//    variant on all 2.2e9 floats with |x| < 120, and with or without FMA on |x| < 7.
+//
+// The contract of lrm_sincosf, stated here once: bit-exact for every |x| < 120, nan for every other
+// argument (|x| >= 120, inf, nan), so that a misuse is loud instead of silently inexact.  The strict
+// path itself stays inside [-2pi, 2pi] and the IK inside [-3pi, 3pi]; the clearance and transit calls
+// pass their callers' angles, whatever those are.  lrm_atanf and lrm_atan2f are exact on every
+// argument, specials included.
+//
+// What holds the contract: tests/test_exact_math_cpu.py runs tools/check_exact_math.cpp, the host
+// build against this machine's glibc on every float (sincosf: all |x| < 120; atanf: every
+// non-negative pattern) and on a lattice of atan2f pairs; tests/test_gpu_exact_math.py compares the
+// device build with the host build on all 2^32 patterns of atanf, sin and cos and on the same lattice.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -176,9 +184,8 @@ LRM_HD void lrm_sincosf(float y, float* sinp, float* cosp) {
         const double s = ((n + 1) & 2) ? -1.0 : 1.0; // sign[] = {1,-1,-1,1}
         x = x * s;
     } else {
-        // |y| >= 120, inf, nan: outside the emulated range (the path only produces angles in
-        // [-2pi, 2pi]).  inf/nan give nan as in glibc; a finite argument this large gives nan as
-        // well, so that a misuse is loud instead of silently inexact.
+        // |y| >= 120, inf, nan: outside the exact range (see the contract at the top).  inf/nan give
+        // nan as in glibc; a finite argument this large gives nan as well.
         *sinp = *cosp = y - y + __builtin_nanf("");
         return;
     }

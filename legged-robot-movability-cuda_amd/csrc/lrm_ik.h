@@ -3,7 +3,7 @@
 // One source for the device kernels (lrm_ik.hip) and the CPU entry points (lrm_capi.cpp), compiled with
 // -ffp-contract=off like lrm_point.h.  Only lrm_atan2f, lrm_sincosf, lrm_sqrtf (lrm_exact_math.h) and + - * /
 // appear, so the host loop and the kernel agree bit for bit.  Every sincos argument is an angle in [-3 pi, 3 pi],
-// inside lrm_sincosf's exact range.
+// inside lrm_sincosf's exact range (|x| < 120: the contract at the top of lrm_exact_math.h).
 //
 // Frames: p (caller's frame) -> qrot(inv_rot) -> rotate by -body_angle -> x -= body -> rotate by -coxa_pitch: the coxa
 // frame of lrm_reach_global / lrm_dist_global.  There the tip of (yaw c, femur f, tibia t) is

@@ -873,7 +873,8 @@ __global__ __launch_bounds__(kBlock) void any_in_shape_kernel(
     if (live) out[c] = found ? 1 : 0;
 }
 
-// diagnostic: the device build of lrm_exact_math.h on arrays (tests compare it with glibc)
+// diagnostic: the device build of lrm_exact_math.h on arrays (tests compare it with the host build,
+// which the CPU suite compares with glibc)
 __global__ __launch_bounds__(kBlock) void exact_math_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             size_t n, float* __restrict__ at2,
                                                             float* __restrict__ sn, float* __restrict__ cs) {

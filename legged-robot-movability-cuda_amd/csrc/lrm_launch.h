@@ -144,6 +144,8 @@ hipError_t lrm_launch_sqrt_check(unsigned long long* counters_dev /* [2]: mismat
                                  hipStream_t st);
 hipError_t lrm_launch_exact_math(const float* a, const float* b, size_t n, float* at2, float* sn, float* cs,
                                  hipStream_t st);
+// lrm_dbg_math.hip: sums_dev[k] = the checksum (lrm_dbg_math.h) of block first_block + k, k < nblocks; one workgroup per block
+hipError_t lrm_launch_exact_math_sums(int fn, uint32_t first_block, uint32_t nblocks, uint64_t* sums_dev, hipStream_t st);
 hipError_t lrm_launch_rotate_soa(const float* sx, const float* sy, const float* sz, size_t n, const LrmCompiledLeg* rot_dev,
                                  float* dx, float* dy, float* dz, hipStream_t st);
 hipError_t lrm_launch_sweep_update(const uint8_t* all_legs, const uint8_t* cyl_validate, const uint8_t* cyl_eliminate,

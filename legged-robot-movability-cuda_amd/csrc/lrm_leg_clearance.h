@@ -26,7 +26,7 @@ LRM_HD void lrm_leg_joints(const LrmCompiledLeg& L, const LrmIkLeg& K, float c, 
 }
 
 // A leg is tested iff all twelve coordinates are finite: nan angles (IK status 0) and angles outside lrm_sincosf's range
-// give nan joints.
+// (|x| < 120, lrm_exact_math.h) give nan joints.
 LRM_HD bool lrm_leg_joints_finite(const LrmVec3 J[4]) {
     bool ok = true;
     for (int k = 0; k < 4; k++) ok = ok && lrm_ik_finite(J[k].x) && lrm_ik_finite(J[k].y) && lrm_ik_finite(J[k].z);

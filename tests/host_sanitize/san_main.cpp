@@ -258,6 +258,22 @@ void posed(const Scene& s, bool null_optionals) {
                                 margin_out.data(), null_optionals ? nullptr : edge.data(), stable.data(), null_optionals ? nullptr : feet.data(), ms));
 }
 
+// block checksums of the exact-math layer: the call's worker threads write disjoint sums, between sentinels
+void checksums() {
+    const uint64_t guard = 0x5a5a5a5a5a5a5a5aull;
+    for (int fn = 0; fn < 3; ++fn) {
+        std::vector<uint64_t> sums(5, guard);
+        OK(lrm_dbg_exact_math_sums_host(fn, 0x3f7f, 3, sums.data() + 1));
+        OK(lrm_dbg_exact_math_sums_host(fn, 65535, 1, sums.data() + 1));
+        OK(lrm_dbg_exact_math_sums_host(fn, 7, 0, sums.data() + 1));
+        if (sums[0] != guard || sums[4] != guard) { std::fprintf(stderr, "san_main: a checksum outside its range\n"); ++g_failures; }
+    }
+    OK(lrm_dbg_exact_math_sums_host(0, 0, 0, nullptr));
+    REFUSED(lrm_dbg_exact_math_sums_host(3, 0, 1, nullptr));
+    REFUSED(lrm_dbg_exact_math_sums_host(0, 65535, 2, nullptr));
+    REFUSED(lrm_dbg_exact_math_sums_host(0, 0, 1, nullptr));
+}
+
 void pairs_and_bodies(const F3& good, const F3& hostile) {
     // link pairs read from the clouds, four points a pair
     for (const F3* c : {&good, &hostile}) {
@@ -318,6 +334,7 @@ int main(int argc, char** argv) {
         single_leg(hostile, m2, nullptr, true); // quat NULL: the identity
         table_build(moon, nullptr);
         pairs_and_bodies(good, hostile);
+        checksums();
         const F3 few(good.begin(), good.begin() + 3 * 900);
         for (int hostile_poses = 0; hostile_poses < 2; ++hostile_poses)
             for (const F3* cloud : {&few, &hostile}) {
@@ -335,6 +352,7 @@ int main(int argc, char** argv) {
         for (int k = 0; k < 8; ++k) pool.emplace_back(thread_body, k, &small, &s);
         for (auto& t : pool) t.join();
         lrm_set_mode(LRM_MODE_FAST);
+        checksums(); // its own pool of workers, under the thread sanitizer too
     }
     if (g_failures) { std::fprintf(stderr, "san_main: %d unexpected return codes\n", g_failures.load()); return 1; }
     std::puts("san_main: every call returned as documented");
