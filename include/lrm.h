@@ -18,7 +18,7 @@
  * host buffers (host-buffer calls through LRM_HOST_PIPELINE=1 run one at a time), lrm_tol_prepare, lrm_apply_oct* and
  * lrm_dbg_toltab_build (the caches of compiled tables are locked; one device table build runs at a time).  lrm_set_mode
  * is process-wide: a switch in one thread changes the next call of every thread.  The pair kernels (lrm_reach_any_dev,
- * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_foothold_misses_posed_dev, lrm_body_clearance_posed_dev, lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
+ * lrm_footholds_dev, lrm_footholds_posed_dev, lrm_foothold_lists_posed_dev, lrm_foothold_edges_posed_dev, lrm_foothold_misses_posed_dev, lrm_body_clearance_posed_dev, lrm_swing_transit_posed_dev (with a foot radius), lrm_positionability*, lrm_any_in_sphere_dev, lrm_any_in_cylinder_dev) share unlocked per-device pools, and
  * lrm_reach_dist_multi its unlocked communicators: call them from one host thread at a time.  lrm_release_workspaces
  * must not overlap any other call.
  * A captured graph that uses a plane table stays valid only while that (leg, orientation) is in the 64-entry table cache
@@ -999,6 +999,82 @@ int lrm_edge_transit_posed_cpu(const float* targets_aos, size_t nt, const float*
                                size_t nedges, const int32_t* foot, size_t nsamples, const uint8_t* live_in /* may be NULL */,
                                uint64_t* mask_out, int32_t* reached_out, int32_t* first_miss_out, int32_t* worst_out,
                                float* worst_d2_out, uint8_t* planted_out, uint8_t* clear_out, int32_t* advance_out, double* ms);
+/* SWING-FOOT TRANSIT: REACH AND TERRAIN CLEARANCE OF A LIFTED FOOT.  lrm_edge_transit_posed_dev samples a pose transition for the feet
+ * that stay planted; this call does it for the leg that is LIFTED: during the step from pose a to pose b the swinging foot leaves
+ * target foot_from and lands on target foot_to, along a straight line with a parabolic bump of height `lift` along `up`.  Per
+ * (edge, leg) it says at which of the S sampled poses the moving foot is reachable, and which terrain targets stand within
+ * foot_radius of the polyline the foot travels along.  The reference has no such query.  No workspace and no table.
+ * The cloud, quats, body, legs, edge_a, edge_b, nsamples = S (2..64) and live_in are exactly lrm_edge_transit_posed_dev's.  Further:
+ *   foot_from, foot_to (int32, [l*nedges + e], device for _dev): the target on which leg l stands under pose a and the one on which
+ *     it lands under pose b.  (e, l) is SWINGING iff the edge is live, a and b lie in [0, nposes) and both indices lie in [0, nt).
+ *     from == to is allowed (lift and put down).  A leg with either index outside the cloud (-1, say) is not swinging: callers pass
+ *     -1 for the planted legs, which stay lrm_edge_transit_posed_dev's business.
+ *   lift (finite, any sign); up (host float[3], NULL = (0, 0, 1), finite, used as given and NOT normalised);
+ *   foot_radius (>= 0, finite; 0 = no terrain test at all); margin (>= 0, finite); skip (0..63).
+ * Everything is float32 without contraction, only + - * /, comparisons and the correctly rounded square root on top of the head
+ * compiler and the strict evaluation: device and host give the same bits (csrc/lrm_swing.h is the one source of both).
+ *   A = t[from], B = t[to], D = B - A (one subtraction per component).
+ *   Path point of sample s RELATIVE TO A: P_0 = 0, P_{S-1} = D; for an interior sample u = (float)s / (float)(S - 1), w = 1 - u,
+ *     h = lift * ((4*u) * w), P_s.c = u*D.c + h*up.c (two multiplications, one addition).
+ *   Pose of sample s: lrm_edge_transit_posed_dev's q_s, body_s (the ends are the table's own rows, bit for bit).
+ *   Foot of sample s: F_0 = A and F_{S-1} = B themselves, an interior F_s = A + P_s (one addition per component).
+ *   p_s = F_s - body_s; r_s and, where it is 0, d2_s as lrm_edge_transit_posed_dev forms them (a nan d2 as +inf).
+ * Terrain test, only when foot_radius > 0: segment k runs from P_k to P_{k+1} and is tested for skip <= k < S-1-skip (skip keeps the
+ *   take-off and the landing, where the foot is at the ground by definition, out of the test; with 2*skip >= S-1 nothing is tested).
+ *   Target i, except i == from and i == to, is tested with q = t_i - A (one subtraction per component) and d_k = the distance of q to
+ *   segment k: lrm_leg_clearance_posed_dev's function and clamping rule with a = P_k, ab = P_{k+1} - P_k, den = |ab|^2.
+ *   hit = d_k < foot_radius; near = d_k < foot_radius + margin (the sum formed once); pen = foot_radius - d_k (-0 as +0); a nan d is
+ *   neither.  If any tested path point P_skip .. P_{S-1-skip} is not finite the leg's terrain part is skipped with the empty answer;
+ *   its reach part still decides clear.
+ * Outputs per (edge, leg) at [l*nedges + e], all written:
+ *   mask_out (uint64, may be NULL), reached_out, first_miss_out, worst_out (may be NULL), worst_d2_out (may be NULL): exactly
+ *     lrm_edge_transit_posed_dev's meaning and encodings with "swinging" in place of "planted" (0 / -1 / -1 / -1 / 0 when not);
+ *   hits_out    (int32) the number of targets with a hit on some tested segment;
+ *   hit_seg_out (int32) the smallest tested k with a hit, -1 if none;
+ *   near_out    (int32) the near target with the largest pen (over targets, then over its segments), ties to the smaller index,
+ *               -1 if none;
+ *   pen_out     (float, may be NULL) that pen, -inf if none;
+ *   a leg that is not swinging gets 0 / -1 / -1 / -inf for these four;
+ * and per edge:
+ *   swinging_out (uint8, may be NULL) bit l set iff leg l is swinging;
+ *   clear_out    (uint8, may be NULL) 1 iff the edge is not dead and every swinging leg has reached == S and hits == 0.  The byte is
+ *                directly a live_in of the other posed calls.
+ * Consequences: with lift = 0, from == to (a finite target) and foot_radius = 0 every reach output equals lrm_edge_transit_posed_*
+ * with foot = from, bit for bit (swinging_out = its planted_out, clear_out = its clear_out); hits > 0 iff hit_seg >= 0 iff pen > 0.
+ * Checked first, in this order (all LRM_EINVAL): lrm_edge_transit_posed_dev's range checks; a nan or infinite lift, foot_radius or
+ * margin; a negative foot_radius or margin; skip > 63; a non-finite up.  Then nedges == 0 is a no-op.  Then a NULL quats, legs, edge_a,
+ * edge_b, foot_from, foot_to, reached_out, first_miss_out, hits_out, hit_seg_out or near_out, or a NULL cloud with nt > 0, gives
+ * LRM_EINVAL.  nt == 0 lets nothing swing.  Any contents of the index arrays are safe: an index is checked before an address is
+ * formed from it.
+ * lrm_swing_transit_posed_dev: the reach kernel (a lane per (edge, sample)) and, when something is tested, the terrain kernel (a
+ * wave per edge walks the cloud's boxes and culls against the path's box about A; the cull never changes an answer): at most two
+ * launches behind the boxes' own, no atomics, bit-deterministic, no host synchronisation.  With foot_radius = 0 no box buffer is
+ * read: the call only launches and may run concurrently with anything from any host thread.  With foot_radius > 0 and nt >= 4096 it
+ * fills and reads the per-device tile-box buffer and so is one of the PAIR KERNELS, with lrm_footholds_posed_dev's rules: one host
+ * thread at a time, no two pair launches on different clouds concurrently on one device, and an allocation only when the cloud is
+ * larger than the buffer holds -- after one call on a cloud of the largest size it only launches and can be captured in a graph and
+ * replayed with new feet.  It does not use the compiled-leg slots.
+ * lrm_swing_transit_posed_cpu: AoS targets, host arrays, a serial loop with the same functions over every (edge, leg, sample) and
+ * every (target, segment) WITHOUT any cull: the reference the GPU tests compare with bit for bit; *ms = the loop's time.
+ * Chain: update -> footholds -> foothold_edges -> edge_transit -> swing_transit(live_in = clear) -> ik / stance_stability. */
+int lrm_swing_transit_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const float* quats /* device */,
+                                const float* body /* device, may be NULL */, size_t nposes, const LrmLegDimensions* legs /* host */,
+                                size_t nlegs, const int32_t* edge_a, const int32_t* edge_b /* device, nedges */, size_t nedges,
+                                const int32_t* foot_from, const int32_t* foot_to /* device, nlegs*nedges at [l*nedges + e] */,
+                                size_t nsamples, float lift, const float* up /* host float[3], may be NULL */, float foot_radius,
+                                float margin, uint32_t skip, const uint8_t* live_in /* device, nedges, may be NULL */,
+                                uint64_t* mask_out /* may be NULL */, int32_t* reached_out, int32_t* first_miss_out,
+                                int32_t* worst_out /* may be NULL */, float* worst_d2_out /* may be NULL */, int32_t* hits_out,
+                                int32_t* hit_seg_out, int32_t* near_out, float* pen_out /* may be NULL */,
+                                uint8_t* swinging_out /* nedges, may be NULL */, uint8_t* clear_out /* nedges, may be NULL */,
+                                void* stream);
+int lrm_swing_transit_posed_cpu(const float* targets_aos, size_t nt, const float* quats, const float* body /* may be NULL */,
+                                size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b,
+                                size_t nedges, const int32_t* foot_from, const int32_t* foot_to, size_t nsamples, float lift,
+                                const float* up /* may be NULL */, float foot_radius, float margin, uint32_t skip,
+                                const uint8_t* live_in /* may be NULL */, uint64_t* mask_out, int32_t* reached_out,
+                                int32_t* first_miss_out, int32_t* worst_out, float* worst_d2_out, int32_t* hits_out, int32_t* hit_seg_out,
+                                int32_t* near_out, float* pen_out, uint8_t* swinging_out, uint8_t* clear_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

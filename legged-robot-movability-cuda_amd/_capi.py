@@ -152,6 +152,8 @@ def load():
         "lrm_dbg_edge_transit_samples_dev": [vp, vp, sz, vp, vp, sz, sz, vp, vp],
         "lrm_edge_transit_posed_dev": [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "lrm_edge_transit_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "lrm_swing_transit_posed_dev": [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, fp, vp, fp, fp, C.c_uint32] + [vp] * 13,
+        "lrm_swing_transit_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, fp, vp, fp, fp, C.c_uint32] + [vp] * 13,
         "lrm_dbg_trunk_link_dist_dev": [vp, sz, fp, fp, fp, vp, vp],
         "lrm_dbg_link_pair_dist_host": [vp, sz, vp],
         "lrm_dbg_link_pair_dist_dev": [vp, sz, vp, vp],
@@ -893,6 +895,67 @@ def edge_transit_posed_cpu(targets, quats, body, legs, edge_a, edge_b, foot, nsa
                                             _ptr(reached), _ptr(first_miss), _ptr(worst), _ptr(worst_d2), _ptr(planted), _ptr(clear),
                                             _ptr(advance), C.addressof(ms)))
     return mask, reached, first_miss, worst, worst_d2, planted, clear, advance, ms.value
+
+
+def _swing_scalars(lift, up, foot_radius, margin, skip):
+    """the host scalars of the swing transit calls: (lift, up float32[3] or None, foot_radius, margin, skip); the library
+    checks their values"""
+    if up is not None:
+        up = np.ascontiguousarray(up, np.float32).reshape(-1)
+        if len(up) != 3:
+            raise ValueError("up: three floats, or None for (0, 0, 1)")
+    skip = int(skip)
+    if not 0 <= skip <= 63:
+        raise ValueError("skip: 0 to 63 segments at either end of the path")
+    return float(lift), up, float(foot_radius), float(margin), skip
+
+
+def swing_transit_posed_cpu(targets, quats, body, legs, edge_a, edge_b, foot_from, foot_to, nsamples=9, lift=0.0, up=None,
+                            foot_radius=0.0, margin=0.0, skip=0, live_in=None, want_mask=True, want_worst=True, want_pen=True,
+                            want_edge=True):
+    """lrm_swing_transit_posed_cpu: can a LIFTED foot get from target foot_from[l, e] (under pose edge_a[e]) to target
+    foot_to[l, e] (under pose edge_b[e]): along a straight line with a parabolic bump of height lift along up, at nsamples
+    sampled poses (edge_transit_posed_cpu's), is the moving foot reachable, and do terrain targets stand within foot_radius of
+    the polyline (segments skip .. nsamples-2-skip; the two footholds themselves are never tested; foot_radius 0: no terrain
+    test).  A leg with either index outside the cloud (-1) is not swinging.  Per (leg, edge): mask, reached, first_miss, worst,
+    worst_d2 as edge_transit_posed_cpu's; hits (targets hit), hit_seg (the first segment hit, -1), near (the deepest target
+    within foot_radius + margin, -1) and its pen (-inf); per edge: swinging (bit l) and clear (live, every swinging leg reaches at
+    every sample and hits nothing).  Serial host loop without any cull; want_* False pass NULL.
+    -> (mask uint64 or None, reached, first_miss int32, worst int32 or None, worst_d2 float32 or None, hits, hit_seg, near int32,
+    pen float32 or None, each [nlegs, nedges]; swinging, clear uint8 [nedges] or None; ms)"""
+    targets = _f32(targets, (-1, 3))
+    quats, body, legs = _posed_tables(quats, body, legs)
+    nl = len(legs)
+    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    ne = len(edge_a)
+    if len(edge_b) != ne:
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    foot_from = np.ascontiguousarray(foot_from, np.int32)
+    foot_to = np.ascontiguousarray(foot_to, np.int32)
+    if foot_from.size != nl * ne or foot_to.size != nl * ne:
+        raise ValueError("foot_from / foot_to: one target index per (leg, edge), at [l*nedges + e]")
+    if live_in is not None:
+        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
+        if len(live_in) != ne:
+            raise ValueError("live_in: one byte per edge")
+    lift, up, foot_radius, margin, skip = _swing_scalars(lift, up, foot_radius, margin, skip)
+    shape = (nl, ne)
+    mask = np.zeros(shape, np.uint64) if want_mask else None
+    reached, first_miss = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    worst = np.zeros(shape, np.int32) if want_worst else None
+    worst_d2 = np.zeros(shape, np.float32) if want_worst else None
+    hits, hit_seg, near = np.zeros(shape, np.int32), np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    pen = np.zeros(shape, np.float32) if want_pen else None
+    swinging = np.zeros(ne, np.uint8) if want_edge else None
+    clear = np.zeros(ne, np.uint8) if want_edge else None
+    ms = C.c_double(0)
+    check(load().lrm_swing_transit_posed_cpu(_ptr(targets), len(targets), _ptr(quats), _ptr(body), len(quats), _ptr(legs), nl,
+                                             _ptr(edge_a), _ptr(edge_b), ne, _ptr(foot_from), _ptr(foot_to), _nsamples(nsamples), lift,
+                                             _ptr(up), foot_radius, margin, skip, _ptr(live_in), _ptr(mask), _ptr(reached),
+                                             _ptr(first_miss), _ptr(worst), _ptr(worst_d2), _ptr(hits), _ptr(hit_seg), _ptr(near),
+                                             _ptr(pen), _ptr(swinging), _ptr(clear), C.addressof(ms)))
+    return mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging, clear, ms.value
 
 
 def dbg_edge_transit_samples_host(quats, body, edge_a, edge_b, nsamples):

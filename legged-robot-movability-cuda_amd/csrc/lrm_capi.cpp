@@ -26,6 +26,7 @@
 #include "lrm_self_clearance.h"
 #include "lrm_trunk_clearance.h"
 #include "lrm_edge_transit.h"
+#include "lrm_swing.h"
 #include "lrm_ik.h"
 #include "lrm_dbg_math.h"
 #include "lrm_launch.h"
@@ -2399,6 +2400,152 @@ int lrm_edge_transit_posed_cpu(const float* targets, size_t nt, const float* qua
         if (planted_out) planted_out[e] = (uint8_t)planted_bits;
         if (clear_out) clear_out[e] = live && all_reach;
         if (advance_out) advance_out[e] = live ? advance : 0;
+    }
+    return LRM_OK;
+}
+
+// ---- swing-foot transit: reach and terrain clearance of a lifted foot per (edge, leg) (lrm_swing.hip) -----------
+namespace {
+// edge_transit's range checks, then the scalars', before any early return; *upv receives up or its default (0, 0, 1)
+int swing_transit_args(size_t nt, size_t nposes, size_t nlegs, size_t nedges, size_t nsamples, float lift, const float* up,
+                       float foot_radius, float margin, uint32_t skip, float upv[3]) {
+    const int rc = edge_transit_args(nt, nposes, nlegs, nedges, nsamples);
+    if (rc != LRM_OK) return rc;
+    if (!std::isfinite(lift) || !std::isfinite(foot_radius) || !std::isfinite(margin))
+        return fail(LRM_EINVAL, "swing transit: lift, foot_radius and margin must be finite");
+    if (foot_radius < 0.f || margin < 0.f) return fail(LRM_EINVAL, "swing transit: foot_radius and margin must be >= 0");
+    if (skip > LRM_SWING_MAX_SKIP) return fail(LRM_EINVAL, "swing transit: skip must be 0..63");
+    upv[0] = upv[1] = 0.f;
+    upv[2] = 1.f;
+    if (up) {
+        for (int k = 0; k < 3; k++) upv[k] = up[k];
+        if (!std::isfinite(up[0]) || !std::isfinite(up[1]) || !std::isfinite(up[2])) return fail(LRM_EINVAL, "swing transit: up must be finite");
+    }
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_swing_transit_posed_dev(const float* tx, const float* ty, const float* tz, size_t nt, const float* quats, const float* body,
+                                size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b,
+                                size_t nedges, const int32_t* foot_from, const int32_t* foot_to, size_t nsamples, float lift,
+                                const float* up, float foot_radius, float margin, uint32_t skip, const uint8_t* live_in,
+                                uint64_t* mask_out, int32_t* reached_out, int32_t* first_miss_out, int32_t* worst_out,
+                                float* worst_d2_out, int32_t* hits_out, int32_t* hit_seg_out, int32_t* near_out, float* pen_out,
+                                uint8_t* swinging_out, uint8_t* clear_out, void* stream) {
+    float upv[3];
+    int rc = swing_transit_args(nt, nposes, nlegs, nedges, nsamples, lift, up, foot_radius, margin, skip, upv);
+    if (rc != LRM_OK) return rc;
+    if (nedges == 0) return LRM_OK;
+    if (!quats || !legs || !edge_a || !edge_b || !foot_from || !foot_to || !reached_out || !first_miss_out || !hits_out || !hit_seg_out ||
+        !near_out || (nt && (!tx || !ty || !tz)))
+        return fail(LRM_EINVAL, "null argument");
+    float* boxes = nullptr; // foot_radius == 0: no terrain test, no box buffer, the call only launches
+    if (foot_radius > 0.f) {
+        rc = cull_boxes(nt, &boxes);
+        if (rc != LRM_OK) return rc;
+    }
+    HIP_TRY(lrm_launch_swing_transit_posed(tx, ty, tz, nt, quats, body, nposes, legs, nlegs, edge_a, edge_b, nedges, foot_from, foot_to,
+                                           nsamples, lift, upv, foot_radius, margin, skip, boxes, live_in, mask_out, reached_out,
+                                           first_miss_out, worst_out, worst_d2_out, hits_out, hit_seg_out, near_out, pen_out, swinging_out,
+                                           clear_out, (hipStream_t)stream),
+            "swing transit launch");
+    return LRM_OK;
+}
+
+int lrm_swing_transit_posed_cpu(const float* targets, size_t nt, const float* quats, const float* body, size_t nposes,
+                                const LrmLegDimensions* legs, size_t nlegs, const int32_t* edge_a, const int32_t* edge_b, size_t nedges,
+                                const int32_t* foot_from, const int32_t* foot_to, size_t nsamples, float lift, const float* up,
+                                float foot_radius, float margin, uint32_t skip, const uint8_t* live_in, uint64_t* mask_out,
+                                int32_t* reached_out, int32_t* first_miss_out, int32_t* worst_out, float* worst_d2_out, int32_t* hits_out,
+                                int32_t* hit_seg_out, int32_t* near_out, float* pen_out, uint8_t* swinging_out, uint8_t* clear_out,
+                                double* ms) {
+    float upv[3];
+    const int rc = swing_transit_args(nt, nposes, nlegs, nedges, nsamples, lift, up, foot_radius, margin, skip, upv);
+    if (rc != LRM_OK) return rc;
+    if (nedges == 0) return LRM_OK;
+    if (!quats || !legs || !edge_a || !edge_b || !foot_from || !foot_to || !reached_out || !first_miss_out || !hits_out || !hit_seg_out ||
+        !near_out || (nt && !targets))
+        return fail(LRM_EINVAL, "null argument");
+    const uint32_t S = (uint32_t)nsamples;
+    const LrmVec3 U{upv[0], upv[1], upv[2]};
+    const LrmSwingRange range = lrm_swing_range(S, skip);
+    const bool terrain = foot_radius > 0.f && range.k0 < range.k1;
+    const float reach = foot_radius + margin;
+    LrmCompiledLeg H; // only its head is written and read
+    LrmVec3 P[LRM_TRANSIT_MAX_SAMPLES];
+    LrmSwingSeg seg[LRM_TRANSIT_MAX_SAMPLES];
+    const ScopeMs timer{ms};
+    for (size_t e = 0; e < nedges; e++) {
+        const int64_t a = edge_a[e], b = edge_b[e];
+        const bool live = !(live_in && !live_in[e]) && a >= 0 && b >= 0 && (uint64_t)a < nposes && (uint64_t)b < nposes;
+        LrmVec3 ba{0.f, 0.f, 0.f}, bb{0.f, 0.f, 0.f};
+        if (live && body) {
+            ba = LrmVec3{body[3 * a], body[3 * a + 1], body[3 * a + 2]};
+            bb = LrmVec3{body[3 * b], body[3 * b + 1], body[3 * b + 2]};
+        }
+        uint32_t swing_bits = 0u;
+        bool clear = live;
+        for (size_t l = 0; l < nlegs; l++) {
+            const size_t o = l * nedges + e;
+            LrmTransitLeg T = lrm_transit_leg_unplanted();
+            LrmSwingTerrain N = lrm_swing_terrain_empty();
+            if (live && lrm_transit_foot_in_cloud(foot_from[o], (uint32_t)nt) && lrm_transit_foot_in_cloud(foot_to[o], (uint32_t)nt)) {
+                const uint32_t ifrom = (uint32_t)foot_from[o], ito = (uint32_t)foot_to[o];
+                const float* ta = targets + 3 * (size_t)ifrom;
+                const float* tb = targets + 3 * (size_t)ito;
+                const LrmVec3 A{ta[0], ta[1], ta[2]}, B{tb[0], tb[1], tb[2]};
+                const LrmVec3 D{B.x - A.x, B.y - A.y, B.z - A.z};
+                uint64_t mask = 0ull, key = 0ull;
+                for (uint32_t s = 0; s < S; s++) {
+                    P[s] = lrm_swing_path_point(D, lift, U, s, S);
+                    const LrmTransitSample smp = lrm_transit_sample(quats + 4 * a, quats + 4 * b, ba, bb, s, S);
+                    const LrmVec3 F = lrm_swing_foot(A, B, P[s], s, S);
+                    const LrmVec3 p{F.x - smp.body.x, F.y - smp.body.y, F.z - smp.body.z};
+                    float d2 = 0.f;
+                    if (lrm_transit_eval(legs[l], smp.q, p, &H, &d2)) {
+                        mask |= 1ull << s;
+                    } else {
+                        const uint64_t k = lrm_transit_key(d2, s);
+                        if (k > key) key = k;
+                    }
+                }
+                T = lrm_transit_leg(mask, key, S);
+                swing_bits |= 1u << l;
+                bool tested = terrain;
+                for (uint32_t k = range.k0; tested && k <= range.k1; k++) tested = lrm_swing_point_finite(P[k]);
+                if (tested) { // every target: no box is consulted
+                    for (uint32_t k = range.k0; k < range.k1; k++) seg[k] = lrm_swing_seg(P[k], P[k + 1]);
+                    uint32_t hits = 0u, first_hit = kLrmSwingNoSeg;
+                    uint64_t best = kLrmLegClearanceNone;
+                    for (size_t t = 0; t < nt; t++) {
+                        if (t == ifrom || t == ito) continue; // the two footholds themselves are never tested
+                        const LrmVec3 q{targets[3 * t] - A.x, targets[3 * t + 1] - A.y, targets[3 * t + 2] - A.z};
+                        float pen = 0.f;
+                        uint32_t fh = kLrmSwingNoSeg;
+                        const unsigned in = lrm_swing_test(seg, range, foot_radius, reach, q, &pen, &fh);
+                        if (in & LRM_SWING_HIT) hits++;
+                        if (fh < first_hit) first_hit = fh;
+                        if (in & LRM_SWING_NEAR) {
+                            const uint64_t k = lrm_leg_clearance_key(pen, (uint32_t)t);
+                            if (k < best) best = k;
+                        }
+                    }
+                    N = lrm_swing_terrain(hits, first_hit, best);
+                }
+                clear = clear && T.first_miss < 0 && N.hits == 0;
+            }
+            if (mask_out) mask_out[o] = T.mask;
+            reached_out[o] = T.reached;
+            first_miss_out[o] = T.first_miss;
+            if (worst_out) worst_out[o] = T.worst;
+            if (worst_d2_out) worst_d2_out[o] = T.worst_d2;
+            hits_out[o] = N.hits;
+            hit_seg_out[o] = N.hit_seg;
+            near_out[o] = N.near;
+            if (pen_out) pen_out[o] = N.pen;
+        }
+        if (swinging_out) swinging_out[e] = (uint8_t)swing_bits;
+        if (clear_out) clear_out[e] = clear;
     }
     return LRM_OK;
 }

@@ -476,6 +476,119 @@ def edge_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot, nsamples=9
     return mask, reached, first_miss, worst, worst_d2, planted, clear, advance
 
 
+def swing_layout(best, edge_a, edge_b, lift_mask):
+    """(foot_from, foot_to) int32 [nlegs, nedges] for swing_transit() from PoseSet.footholds()'s best [nlegs, nposes]: leg l of
+    edge e leaves best[l, edge_a[e]] and lands on best[l, edge_b[e]] where bit l of lift_mask[e] (uint8 device tensor, nedges)
+    is set, and gets -1 / -1 (not swinging: a planted leg, edge_transit()'s business) where it is clear or where an end lies
+    outside [0, nposes) (a dead edge).  edge_a / edge_b: int32 device tensors.  Only tensor operations: no host
+    synchronisation."""
+    torch = _torch()
+    if not (best.dtype == torch.int32 and best.dim() == 2 and 1 <= best.shape[0] <= 8):
+        raise ValueError("best: the int32 (nlegs, nposes) tensor of footholds()")
+    nl, ne = best.shape[0], edge_a.numel()
+    if not (edge_a.dtype == torch.int32 and edge_b.dtype == torch.int32 and edge_b.numel() == ne):
+        raise ValueError("edge_a / edge_b: int32 tensors of nedges pose indices")
+    if not (lift_mask.dtype == torch.uint8 and lift_mask.numel() == ne):
+        raise ValueError("lift_mask: a uint8 tensor of nedges leg bit masks")
+    dev = best.device
+    lifted = (lift_mask.reshape(1, ne).to(dev).to(torch.int32) >> torch.arange(nl, dtype=torch.int32, device=dev).reshape(nl, 1)) & 1
+    none = torch.full((nl, ne), -1, dtype=torch.int32, device=dev)
+    a, b = edge_a.reshape(-1).to(dev).long(), edge_b.reshape(-1).to(dev).long()
+    nposes = best.shape[1]
+    take = (lifted != 0) & ((a >= 0) & (a < nposes) & (b >= 0) & (b < nposes)).reshape(1, ne)  # a bad end is a dead edge: nothing swings
+    foot_from = torch.where(take, best[:, a.clamp(0, max(nposes - 1, 0))], none)
+    foot_to = torch.where(take, best[:, b.clamp(0, max(nposes - 1, 0))], none)
+    return foot_from.contiguous(), foot_to.contiguous()
+
+
+def swing_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot_from, foot_to, nsamples=9, lift=0.0, up=None,
+                  foot_radius=0.0, margin=0.0, skip=0, live_in=None, mask=None, reached=None, first_miss=None, worst=None,
+                  worst_d2=None, hits=None, hit_seg=None, near=None, pen=None, swinging=None, clear=None):
+    """lrm_swing_transit_posed_dev: can a LIFTED foot get from its foothold under pose edge_a[e] to its foothold under pose
+    edge_b[e].  edge_transit() samples the move for the feet that stay planted; this call does it for the swinging foot, which
+    travels from target foot_from[l, e] to target foot_to[l, e] along a straight line with a parabolic bump of height lift along
+    up (3 host floats, None = (0, 0, 1), not normalised), at the same nsamples sampled poses.  foot_from / foot_to: int32
+    [nlegs, nedges] on the device (swing_layout() builds them); a leg with either index outside the cloud (-1) is not swinging.
+    Reach part: mask, reached, first_miss, worst, worst_d2 [l, e] as edge_transit()'s, for the moving foot.  Terrain part, only
+    with foot_radius > 0: the path's segments skip .. nsamples-2-skip against every target but the two footholds: hits[l, e]
+    (targets within foot_radius), hit_seg[l, e] (the first segment hit, -1), near[l, e] (the deepest target within foot_radius +
+    margin, -1) and its pen[l, e] (foot_radius - distance; -inf).  swinging[e] (bit l), clear[e] (1 iff live, both ends in range,
+    every swinging leg reaches at every sample and hits nothing): directly the live_in of the other posed calls.
+    Any index is safe.  -> (mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging, clear).  Every tensor
+    must be contiguous.  No table.  With foot_radius == 0 one launch and no shared buffer; with foot_radius > 0 and 4096 targets
+    or more it uses the pair kernels' box buffer (their threading rules; graph capture after one call on the largest cloud)."""
+    torch = _torch()
+    nt = _check_f32(tx, ty, tz)
+    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
+        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
+    nposes = quats.shape[0]
+    if nt and tx.device != quats.device:
+        raise ValueError("targets and poses must live on one device")
+    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
+                                 and tuple(body.shape) == (nposes, 3)):
+        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
+    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+    nl = len(legs)
+    if not 1 <= nl <= 8:
+        raise ValueError("legs: 1 to 8 legs")
+    ne = edge_a.numel()
+    _check_out(edge_a, quats, torch.int32, ne, "edge_a")
+    _check_out(edge_b, quats, torch.int32, ne, "edge_b")
+    if edge_b.numel() != ne:
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    for foot, what in ((foot_from, "foot_from"), (foot_to, "foot_to")):
+        if not (foot.is_cuda and foot.device == quats.device and foot.dtype == torch.int32 and foot.dim() == 2 and foot.is_contiguous()
+                and tuple(foot.shape) == (nl, ne)):
+            raise ValueError(f"{what}: expected a contiguous int32 tensor of shape ({nl}, {ne}) on the poses' device")
+    _check_out(live_in, quats, torch.uint8, ne, "live_in")
+    if live_in is not None and live_in.numel() != ne:
+        raise ValueError("live_in: one byte per edge")
+    nsamples = _capi._nsamples(nsamples)
+    lift, up, foot_radius, margin, skip = _capi._swing_scalars(lift, up, foot_radius, margin, skip)
+    shape, n, dev = (nl, ne), nl * ne, quats.device
+    if mask is None:
+        mask = torch.empty(shape, dtype=torch.int64, device=dev)
+    if reached is None:
+        reached = torch.empty(shape, dtype=torch.int32, device=dev)
+    if first_miss is None:
+        first_miss = torch.empty(shape, dtype=torch.int32, device=dev)
+    if worst is None:
+        worst = torch.empty(shape, dtype=torch.int32, device=dev)
+    if worst_d2 is None:
+        worst_d2 = torch.empty(shape, dtype=torch.float32, device=dev)
+    if hits is None:
+        hits = torch.empty(shape, dtype=torch.int32, device=dev)
+    if hit_seg is None:
+        hit_seg = torch.empty(shape, dtype=torch.int32, device=dev)
+    if near is None:
+        near = torch.empty(shape, dtype=torch.int32, device=dev)
+    if pen is None:
+        pen = torch.empty(shape, dtype=torch.float32, device=dev)
+    if swinging is None:
+        swinging = torch.empty(ne, dtype=torch.uint8, device=dev)
+    if clear is None:
+        clear = torch.empty(ne, dtype=torch.uint8, device=dev)
+    _check_out(mask, quats, torch.int64, n, "per-leg sample masks")
+    _check_out(reached, quats, torch.int32, n, "per-leg reached counts")
+    _check_out(first_miss, quats, torch.int32, n, "per-leg first misses")
+    _check_out(worst, quats, torch.int32, n, "per-leg worst samples")
+    _check_out(worst_d2, quats, torch.float32, n, "per-leg worst squared distances")
+    _check_out(hits, quats, torch.int32, n, "per-leg hit counts")
+    _check_out(hit_seg, quats, torch.int32, n, "per-leg first hit segments")
+    _check_out(near, quats, torch.int32, n, "per-leg deepest near targets")
+    _check_out(pen, quats, torch.float32, n, "per-leg penetrations")
+    _check_out(swinging, quats, torch.uint8, ne, "per-edge swinging bits")
+    _check_out(clear, quats, torch.uint8, ne, "per-edge clear bytes")
+    with torch.cuda.device(dev):
+        _capi.check(_capi.load().lrm_swing_transit_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _capi._ptr(legs),
+                                                             nl, _dp(edge_a), _dp(edge_b), ne, _dp(foot_from), _dp(foot_to), nsamples, lift,
+                                                             _capi._ptr(up), foot_radius, margin, skip, _dp(live_in), _dp(mask),
+                                                             _dp(reached), _dp(first_miss), _dp(worst), _dp(worst_d2), _dp(hits),
+                                                             _dp(hit_seg), _dp(near), _dp(pen), _dp(swinging), _dp(clear),
+                                                             _stream(quats)))
+    return mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging, clear
+
+
 def dbg_edge_transit_samples(quats, body, edge_a, edge_b, nsamples):
     """lrm_dbg_edge_transit_samples_dev: the sampled path of edge_transit() -> float32 (nedges, nsamples, 7) on the device: the
     quaternion and the body position of every sample (nan for an edge with an end out of range); one sample per lane."""
@@ -550,7 +663,8 @@ class PoseSet:
     links, and leg_joints() returns the joints it tests; stance_stability() asks whether the chosen footholds carry the
     centre of mass, and which legs can be lifted; self_clearance() (with ik=True) asks whether the legs fit next to each
     other under ik()'s angles: links of different legs against each other; trunk_clearance() (with ik=True) whether they
-    stay out of the robot's own trunk: leg links against the body cylinder; edge_transit() whether the feet that
+    stay out of the robot's own trunk: leg links against the body cylinder; swing_transit() whether a lifted foot gets from
+    its old foothold to its new one; edge_transit() whether the feet that
     foothold_edges() plants stay reachable at sampled poses between the two ends of a transition."""
 
     def __init__(self, legs, nposes_max, device=None, ik=False, footholds=False, nominal=None):
@@ -913,6 +1027,31 @@ class PoseSet:
                 raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
         return edge_transit(tx, ty, tz, quats, body, self.legs, edge_a, edge_b, foot, nsamples, live_in, mask, reached, first_miss,
                             worst, worst_d2, planted, clear, advance)
+
+    def swing_transit(self, tx, ty, tz, quats, body, edge_a, edge_b, foot_from, foot_to, nsamples=9, lift=0.0, up=None,
+                      foot_radius=0.0, margin=0.0, skip=0, live_in=None, mask=None, reached=None, first_miss=None, worst=None,
+                      worst_d2=None, hits=None, hit_seg=None, near=None, pen=None, swinging=None, clear=None, check=True):
+        """device.swing_transit() with this set's legs: quats (and body) are the tensors of the last update(), so their pose
+        count must be the set's; foot_from / foot_to [nlegs, nedges] come from swing_layout(footholds()'s best, edge_a, edge_b,
+        lift_mask).  check=True validates edge_a / edge_b on the host (one synchronisation), as edge_transit() does; check=False
+        leaves an index outside [0, nposes) to the kernel (a dead edge): the form for graph capture.  -> (mask, reached,
+        first_miss, worst, worst_d2, hits, hit_seg, near, pen [nlegs, nedges]; swinging, clear [nedges]); give edge_transit()'s
+        clear as live_in, and this clear to what follows:
+        update -> footholds -> foothold_edges -> edge_transit -> swing_transit(live_in = clear) -> ik / stance_stability."""
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+        if quats.dim() != 2 or quats.shape[0] != self.nposes:
+            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
+        if quats.device != self.workspace.device:
+            raise ValueError("quats and poses must live on one device")
+        if check and edge_a.numel() and edge_a.numel() == edge_b.numel():
+            lo = min(int(edge_a.min()), int(edge_b.min()))
+            hi = max(int(edge_a.max()), int(edge_b.max()))
+            if lo < 0 or hi >= self.nposes:
+                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
+        return swing_transit(tx, ty, tz, quats, body, self.legs, edge_a, edge_b, foot_from, foot_to, nsamples, lift, up, foot_radius,
+                             margin, skip, live_in, mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging,
+                             clear)
 
     def _check_angles(self, angles):
         torch = _torch()
