@@ -26,11 +26,51 @@ def build(verbose=False):
     return LIB_PATH
 
 
+_C_SCALARS = {"size_t": C.c_size_t, "float": C.c_float, "double": C.c_double, "int": C.c_int, "int32_t": C.c_int32,
+              "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+_C_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "void": None, "const char*": C.c_char_p}
+_signatures = None  # parse_header(include/lrm.h), read once
+
+
+def parse_header(text):
+    """{name: (restype, [argtypes])} of every lrm_* prototype in header text: the only source of the ctypes signatures.
+    A pointer, an array or the LrmOctExchange callback is a c_void_p, a scalar by value its own ctypes type; a type that is
+    not listed above raises LrmError (never a guess)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", "", text, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([^;{}()]*?)\b(lrm_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _C_RETURNS:
+            raise LrmError(f"{name}: unknown return type '{ret}'")
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            if "*" in p or "[" in p or words[:1] == ["LrmOctExchange"]:
+                argtypes.append(C.c_void_p)
+            elif len(words) in (1, 2) and words[0] in _C_SCALARS:
+                argtypes.append(_C_SCALARS[words[0]])
+            else:
+                raise LrmError(f"{name}: unknown parameter type '{' '.join(p.split())}'")
+        out[name] = (_C_RETURNS[ret], argtypes)
+    return out
+
+
+def signatures():
+    """parse_header() of include/lrm.h"""
+    global _signatures
+    if _signatures is None:
+        try:
+            text = open(HEADER_PATH).read()
+        except OSError as e:
+            raise LrmError(f"{HEADER_PATH} is missing: the ctypes signatures come from it ({e})")
+        _signatures = parse_header(text)
+    return _signatures
+
+
 def declared_symbols():
     """Every function name declared in include/lrm.h."""
-    text = open(HEADER_PATH).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(lrm_[a-z0-9_]+)\s*\(", text)))
+    return sorted(signatures())
 
 
 def exported_symbols():
@@ -54,152 +94,14 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    vp, sz, fp = C.c_void_p, C.c_size_t, C.c_float
-    L.lrm_version.restype = C.c_char_p
-    L.lrm_last_error.restype = C.c_char_p
-    sig = {
-        "lrm_device_count": [], "lrm_set_device": [C.c_int], "lrm_set_mode": [C.c_int], "lrm_get_mode": [],
-        "lrm_reach": [vp, sz, vp, vp, vp, vp],
-        "lrm_dist": [vp, sz, vp, vp, vp, vp, vp],
-        "lrm_reach_dist": [vp, sz, vp, vp, vp, vp, vp],
-        "lrm_reach_soa": [vp, vp, vp, sz, vp, vp, vp, vp],
-        "lrm_dist_soa": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_reach_cpu": [vp, sz, vp, vp, vp, vp],
-        "lrm_dist_cpu": [vp, sz, vp, vp, vp, vp, vp],
-        "lrm_rbdl_equiv_cpu": [vp, sz, vp, vp, vp],
-        "lrm_reach_dev": [vp, vp, vp, sz, vp, vp, vp, vp],
-        "lrm_reach_bits_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp],
-        "lrm_dist_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_reach_dist_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_reach_dist_bits_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_reach_aos_dev": [vp, sz, vp, vp, vp, vp],
-        "lrm_dist_aos_dev": [vp, sz, vp, vp, vp, vp, vp],
-        "lrm_reach_any_dev": [vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
-        "lrm_footholds_dev": [vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_footholds_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_positionability": [vp, sz, vp, sz, vp, sz, vp, sz, C.c_int, vp, vp],
-        "lrm_morton_order": [vp, sz, vp],
-        "lrm_dbg_fast_host": [vp, sz, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_dbg_fused_reach_host": [vp, sz, vp, vp, vp, vp],
-        "lrm_dbg_tol_host": [vp, sz, vp, vp, vp, vp, vp],
-        "lrm_dbg_tol_ok": [vp, vp],
-        "lrm_dbg_tol_queue_counts": [vp, vp, vp],
-        "lrm_dbg_tol_grid": [sz, vp],
-        "lrm_dbg_toltab_host": [vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_dbg_toltab_bounds": [vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_dbg_xtab_host": [vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_dbg_replay_host": [vp, sz, vp, vp, vp, vp, vp],
-        "lrm_dbg_toltab_build": [vp, vp, C.c_int, vp, sz, vp, vp],
-        "lrm_shard_bounds": [sz, C.c_int, C.c_int, sz, vp, vp],
-        "lrm_dbg_pair_counts": [vp],
-        "lrm_tol_prepare": [vp, vp, sz, vp],
-        "lrm_tol_table_build_ms": [vp],
-        "lrm_positionability_dev": [vp, vp, vp, sz, vp, vp, vp, sz, vp, sz, vp, sz, C.c_int, vp, vp, vp],
-        "lrm_dbg_oct_trace": [C.c_int],
-        "lrm_dbg_oct_trace_read": [vp, sz, vp],
-        "lrm_reach_dist_multi": [vp, sz, vp, vp, C.c_int, vp, vp, vp, vp, vp],
-        "lrm_dbg_pair_sphere": [vp, vp, vp],
-        "lrm_dbg_exact_math_host": [vp, vp, sz, vp, vp, vp],
-        "lrm_dbg_exact_math_dev": [vp, vp, sz, vp, vp, vp, vp],
-        "lrm_dbg_exact_math_sums_host": [C.c_int, C.c_uint32, C.c_uint32, vp],
-        "lrm_dbg_exact_math_sums_dev": [C.c_int, C.c_uint32, C.c_uint32, vp, vp],
-        "lrm_dbg_sqrt_check_dev": [vp, vp],
-        "lrm_any_in_sphere_dev": [vp, vp, vp, sz, vp, vp, vp, sz, fp, vp, vp],
-        "lrm_any_in_cylinder_dev": [vp, vp, vp, sz, vp, vp, vp, sz, fp, fp, fp, vp, vp],
-        "lrm_pose_compile_dev": [vp, vp, sz, vp, sz, vp, vp],
-        "lrm_reach_dist_posed_dev": [vp, vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_reach_dist_posed_cpu": [vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
-        "lrm_dbg_pose_compile_host": [vp, vp, sz, vp, sz, vp],
-        "lrm_dbg_compile_leg_head": [vp, vp, vp],
-        "lrm_ik_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_fk_dev": [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_ik_cpu": [vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_fk_cpu": [vp, sz, vp, vp, vp, vp],
-        "lrm_pose_ik_compile_dev": [vp, sz, vp, sz, vp, vp],
-        "lrm_dbg_pose_ik_compile_host": [vp, sz, vp, sz, vp],
-        "lrm_ik_posed_dev": [vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_fk_posed_dev": [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp],
-        "lrm_ik_posed_cpu": [vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp],
-        "lrm_fk_posed_cpu": [vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp],
-        "lrm_pose_footholds_compile_dev": [vp, sz, vp, sz, vp, vp, vp],
-        "lrm_dbg_pose_footholds_compile_host": [vp, sz, vp, sz, vp, vp],
-        "lrm_footholds_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp],
-        "lrm_footholds_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
-        "lrm_foothold_offsets_dev": [vp, sz, vp, vp],
-        "lrm_foothold_lists_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp],
-        "lrm_foothold_lists_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp],
-        "lrm_foothold_edges_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp],
-        "lrm_foothold_edges_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp],
-        "lrm_foothold_misses_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, fp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_foothold_misses_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, fp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_foothold_support_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_foothold_support_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_dbg_foothold_support_grid": [sz, sz, vp],
-        "lrm_body_clearance_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp],
-        "lrm_body_clearance_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, fp, fp, fp, fp, vp, vp, vp, vp, vp, vp],
-        "lrm_leg_clearance_posed_dev": [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_leg_clearance_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_leg_joints_posed_dev": [vp, vp, vp, sz, sz, vp, vp, fp, vp, vp],
-        "lrm_leg_joints_posed_cpu": [vp, vp, vp, sz, vp, sz, fp, vp, vp],
-        "lrm_stance_stability_dev": [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
-        "lrm_stance_stability_cpu": [vp, sz, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, sz, fp, vp, vp, vp, vp, vp, vp],
-        "lrm_self_clearance_posed_dev": [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_self_clearance_posed_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, fp, fp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_trunk_clearance_posed_dev": [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, fp, fp, fp, fp, fp, C.c_uint8, vp, vp, vp, vp, vp, vp],
-        "lrm_trunk_clearance_posed_cpu": [vp, sz, vp, sz, vp, sz, vp, vp, fp, fp, fp, fp, fp, C.c_uint8, vp, vp, vp, vp, vp, vp],
-        "lrm_dbg_trunk_link_dist_host": [vp, sz, fp, fp, fp, vp],
-        "lrm_dbg_edge_transit_samples_host": [vp, vp, sz, vp, vp, sz, sz, vp],
-        "lrm_dbg_edge_transit_samples_dev": [vp, vp, sz, vp, vp, sz, sz, vp, vp],
-        "lrm_edge_transit_posed_dev": [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_edge_transit_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "lrm_swing_transit_posed_dev": [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, fp, vp, fp, fp, C.c_uint32] + [vp] * 13,
-        "lrm_swing_transit_posed_cpu": [vp, sz, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, fp, vp, fp, fp, C.c_uint32] + [vp] * 13,
-        "lrm_dbg_trunk_link_dist_dev": [vp, sz, fp, fp, fp, vp, vp],
-        "lrm_dbg_link_pair_dist_host": [vp, sz, vp],
-        "lrm_dbg_link_pair_dist_dev": [vp, sz, vp, vp],
-    }
-    for name, argtypes in sig.items():
+    for name, (restype, argtypes) in signatures().items():
         try:
             fn = getattr(L, name)
         except AttributeError:
             if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_", "lrm_edge_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
-        fn.argtypes = argtypes
-        fn.restype = C.c_int
-    L.lrm_leg_factory.argtypes = [fp] * 11 + [vp]
-    L.lrm_leg_factory.restype = None
-    for name in ("lrm_get_M2_leg", "lrm_get_moonbot_leg"):
-        getattr(L, name).argtypes = [fp, vp]
-        getattr(L, name).restype = None
-    L.lrm_octree_default_settings.argtypes = [vp]
-    L.lrm_octree_default_settings.restype = None
-    L.lrm_apply_oct.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp]
-    L.lrm_apply_oct.restype = C.c_int
-    L.lrm_octree_last_error.restype = C.c_char_p
-    L.lrm_apply_oct_sharded.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, C.c_int, C.c_int, vp, vp]
-    L.lrm_apply_oct_sharded.restype = C.c_int
-    L.lrm_apply_oct_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, C.c_int, C.c_int, vp, vp]
-    L.lrm_apply_oct_dev.restype = C.c_int
-    L.lrm_apply_oct_partitioned.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
-    L.lrm_apply_oct_partitioned.restype = C.c_int
-    L.lrm_apply_oct_partitioned_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
-    L.lrm_apply_oct_partitioned_dev.restype = C.c_int
-    L.lrm_rotate_leg_data.argtypes = [vp, vp, vp]
-    L.lrm_rotate_leg_data.restype = None
-    L.lrm_multi_release.argtypes = []
-    L.lrm_multi_release.restype = None
-    L.lrm_release_workspaces.argtypes = []
-    L.lrm_release_workspaces.restype = None
-    L.lrm_posed_workspace_bytes.argtypes = [sz, sz]
-    L.lrm_posed_workspace_bytes.restype = sz
-    L.lrm_posed_ik_workspace_bytes.argtypes = [sz, sz]
-    L.lrm_posed_ik_workspace_bytes.restype = sz
-    L.lrm_posed_footholds_workspace_bytes.argtypes = [sz, sz]
-    L.lrm_posed_footholds_workspace_bytes.restype = sz
-    if hasattr(L, "lrm_foothold_support_workspace_bytes"):  # missing in an older library variant of an A/B run
-        L.lrm_foothold_support_workspace_bytes.argtypes = [sz, sz, sz]
-        L.lrm_foothold_support_workspace_bytes.restype = sz
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = L
     return L
 
@@ -224,6 +126,34 @@ def _f32(a, shape=None):
 
 def _quat(q):
     return None if q is None else _f32(q, (4,))
+
+
+def _nominal(nominal, nlegs):
+    return None if nominal is None else _f32(nominal, (nlegs, 3))
+
+
+def _u8_per(a, n, what):
+    """an optional byte per pose, stance, set or edge (live_in, pose_live); what: the complaint about another length"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, np.uint8).reshape(-1)
+    if len(a) != n:
+        raise ValueError(what)
+    return a
+
+
+def _edges(edge_a, edge_b):
+    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
+    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    if len(edge_a) != len(edge_b):
+        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    return edge_a, edge_b
+
+
+def _posed_indices(n, pose_idx, leg_idx):
+    pi = None if pose_idx is None else np.ascontiguousarray(pose_idx, np.int32).reshape(n)
+    li = None if leg_idx is None else np.ascontiguousarray(leg_idx, np.uint8).reshape(n)
+    return pi, li
 
 
 def device_count():
@@ -374,8 +304,7 @@ def apply_reach_dist_posed_cpu(xyz, pose_idx, leg_idx, quats, body, legs):
     xyz = _f32(xyz, (-1, 3))
     n = len(xyz)
     quats, body, legs = _posed_tables(quats, body, legs)
-    pi = None if pose_idx is None else np.ascontiguousarray(pose_idx, np.int32).reshape(n)
-    li = None if leg_idx is None else np.ascontiguousarray(leg_idx, np.uint8).reshape(n)
+    pi, li = _posed_indices(n, pose_idx, leg_idx)
     m, v, d = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros_like(xyz)
     ms = C.c_double(0)
     check(load().lrm_reach_dist_posed_cpu(_ptr(xyz), n, _ptr(pi), _ptr(li), _ptr(quats), _ptr(body), len(quats), _ptr(legs),
@@ -431,12 +360,6 @@ def apply_fk_cpu(angles, leg, quat=None):
 POSE_IK_RECORD_BYTES = 128  # lrm_posed_ik_workspace_bytes(1, 1)
 
 
-def _posed_indices(n, pose_idx, leg_idx):
-    pi = None if pose_idx is None else np.ascontiguousarray(pose_idx, np.int32).reshape(n)
-    li = None if leg_idx is None else np.ascontiguousarray(leg_idx, np.uint8).reshape(n)
-    return pi, li
-
-
 def apply_ik_posed_cpu(xyz, pose_idx, leg_idx, quats, body, legs, target_idx=None, seed=None):
     """lrm_ik_posed_cpu: query i = (target target_idx[i] of xyz, or target i; pose pose_idx[i]; leg leg_idx[i]) on the
     host, p = target - body[pose]; indices None = target i / pose 0 / leg 0; seed None or float32[n, 3] per query
@@ -484,7 +407,7 @@ POSE_FOOTHOLD_BYTES = 32  # lrm_posed_footholds_workspace_bytes(1, 1)
 def dbg_pose_footholds_compile_host(quats, legs, nominal=None):
     """the foothold table the host makes -> float32[nposes, nlegs, 8]: {cull_center[3], cull_r2, nominal_w[3], pad}"""
     quats, _, legs = _posed_tables(quats, None, legs)
-    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    nom = _nominal(nominal, len(legs))
     out = np.zeros((len(quats), len(legs), POSE_FOOTHOLD_BYTES // 4), np.float32)
     check(load().lrm_dbg_pose_footholds_compile_host(_ptr(quats), len(quats), _ptr(legs), len(legs), _ptr(nom), _ptr(out)))
     return out
@@ -498,7 +421,7 @@ def footholds_posed_cpu(targets, quats, body, legs, nominal=None):
     all_legs uint8[nposes], ms)"""
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
-    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    nom = _nominal(nominal, len(legs))
     shape = (len(legs), len(quats))
     count, best, best_d2 = np.zeros(shape, np.int32), np.zeros(shape, np.int32), np.zeros(shape, np.float32)
     all_legs = np.zeros(len(quats), np.uint8)
@@ -517,7 +440,7 @@ def foothold_lists_posed_cpu(targets, quats, body, legs, offsets, capacity=None,
     -> (idx int32[capacity], d2 float32[capacity] or None, written int32[nlegs, nposes] or None, ms)"""
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
-    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    nom = _nominal(nominal, len(legs))
     offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
     if len(offsets) != len(legs) * len(quats) + 1:
         raise ValueError("offsets: nlegs * nposes + 1 entries")
@@ -550,11 +473,8 @@ def foothold_edges_posed_cpu(targets, quats, body, legs, edge_a, edge_b, nominal
     all_legs uint8[nedges] or None, ms)"""
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
-    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
-    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
-    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
-    if len(edge_a) != len(edge_b):
-        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    nom = _nominal(nominal, len(legs))
+    edge_a, edge_b = _edges(edge_a, edge_b)
     shape = (len(legs), len(edge_a))
     count, best = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
     best_d2 = np.zeros(shape, np.float32) if want_d2 else None
@@ -602,11 +522,8 @@ def foothold_support_posed_cpu(targets, quats, body, legs, nominal=None, pose_li
     None, ms)"""
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
-    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
-    if pose_live is not None:
-        pose_live = np.ascontiguousarray(pose_live, np.uint8).reshape(-1)
-        if len(pose_live) != len(quats):
-            raise ValueError("pose_live: one byte per pose")
+    nom = _nominal(nominal, len(legs))
+    pose_live = _u8_per(pose_live, len(quats), "pose_live: one byte per pose")
     shape = (len(legs), len(targets))
     count, best = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
     best_d2 = np.zeros(shape, np.float32) if want_d2 else None
@@ -636,10 +553,7 @@ def body_clearance_posed_cpu(targets, quats, body, legs, radius, plus_z, minus_z
     pass NULL.  -> (hits int32[nposes], top int32[nposes], height float32[nposes] or None, free uint8[nposes] or None, ms)"""
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != len(quats):
-            raise ValueError("live_in: one byte per pose")
+    live_in = _u8_per(live_in, len(quats), "live_in: one byte per pose")
     n = len(quats)
     hits, top = np.zeros(n, np.int32), np.zeros(n, np.int32)
     height = np.zeros(n, np.float32) if want_height else None
@@ -674,10 +588,7 @@ def leg_clearance_posed_cpu(targets, quats, body, legs, angles, radius, margin=0
     n, nl = len(quats), len(legs)
     angles = _leg_angles(angles, nl, n)
     radius = _f32(radius, (3,))
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != n:
-            raise ValueError("live_in: one byte per pose")
+    live_in = _u8_per(live_in, n, "live_in: one byte per pose")
     hits, links, worst = np.zeros((nl, n), np.int32), np.zeros((nl, n), np.uint8), np.zeros((nl, n), np.int32)
     pen = np.zeros((nl, n), np.float32) if want_pen else None
     free = np.zeros(n, np.uint8) if want_free else None
@@ -745,10 +656,7 @@ def stance_stability_cpu(targets, foot, quats, body=None, pose_idx=None, com=Non
         pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
         if len(pose_idx) != ns:
             raise ValueError("pose_idx: one pose per stance")
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != ns:
-            raise ValueError("live_in: one byte per stance")
+    live_in = _u8_per(live_in, ns, "live_in: one byte per stance")
     com, plane = _stance_host(com, plane)
     lift = stance_lift(lift, nl)
     nm = len(lift)
@@ -787,10 +695,7 @@ def self_clearance_posed_cpu(quats, legs, angles, radius, margin=0.0, tip_clear=
         pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
         if len(pose_idx) != ns:
             raise ValueError("pose_idx: one pose per set")
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != ns:
-            raise ValueError("live_in: one byte per set")
+    live_in = _u8_per(live_in, ns, "live_in: one byte per set")
     hits = np.zeros((nl, ns), np.int32)
     with_, links, worst = (np.zeros((nl, ns), np.uint8) for _ in range(3))
     pen = np.zeros((nl, ns), np.float32) if want_pen else None
@@ -831,10 +736,7 @@ def trunk_clearance_posed_cpu(quats, legs, angles, radius, trunk_radius, plus_z,
         pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
         if len(pose_idx) != ns:
             raise ValueError("pose_idx: one pose per set")
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != ns:
-            raise ValueError("live_in: one byte per set")
+    live_in = _u8_per(live_in, ns, "live_in: one byte per set")
     hit, worst = (np.zeros((nl, ns), np.uint8) for _ in range(2))
     pen = np.zeros((nl, ns), np.float32) if want_pen else None
     free = np.zeros(ns, np.uint8) if want_free else None
@@ -869,18 +771,12 @@ def edge_transit_posed_cpu(targets, quats, body, legs, edge_a, edge_b, foot, nsa
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
     nl = len(legs)
-    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
-    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    edge_a, edge_b = _edges(edge_a, edge_b)
     ne = len(edge_a)
-    if len(edge_b) != ne:
-        raise ValueError("edge_a / edge_b: one pose index each per edge")
     foot = np.ascontiguousarray(foot, np.int32)
     if foot.size != nl * ne:
         raise ValueError("foot: one target index per (leg, edge), at [l*nedges + e]")
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != ne:
-            raise ValueError("live_in: one byte per edge")
+    live_in = _u8_per(live_in, ne, "live_in: one byte per edge")
     shape = (nl, ne)
     mask = np.zeros(shape, np.uint64) if want_mask else None
     reached, first_miss = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
@@ -926,19 +822,13 @@ def swing_transit_posed_cpu(targets, quats, body, legs, edge_a, edge_b, foot_fro
     targets = _f32(targets, (-1, 3))
     quats, body, legs = _posed_tables(quats, body, legs)
     nl = len(legs)
-    edge_a = np.ascontiguousarray(edge_a, np.int32).reshape(-1)
-    edge_b = np.ascontiguousarray(edge_b, np.int32).reshape(-1)
+    edge_a, edge_b = _edges(edge_a, edge_b)
     ne = len(edge_a)
-    if len(edge_b) != ne:
-        raise ValueError("edge_a / edge_b: one pose index each per edge")
     foot_from = np.ascontiguousarray(foot_from, np.int32)
     foot_to = np.ascontiguousarray(foot_to, np.int32)
     if foot_from.size != nl * ne or foot_to.size != nl * ne:
         raise ValueError("foot_from / foot_to: one target index per (leg, edge), at [l*nedges + e]")
-    if live_in is not None:
-        live_in = np.ascontiguousarray(live_in, np.uint8).reshape(-1)
-        if len(live_in) != ne:
-            raise ValueError("live_in: one byte per edge")
+    live_in = _u8_per(live_in, ne, "live_in: one byte per edge")
     lift, up, foot_radius, margin, skip = _swing_scalars(lift, up, foot_radius, margin, skip)
     shape = (nl, ne)
     mask = np.zeros(shape, np.uint64) if want_mask else None
@@ -1265,7 +1155,7 @@ def footholds_cpu(bodies, targets, legs, quat=None, nominal=None):
     bodies = _f32(bodies, (-1, 3))
     targets = _f32(targets, (-1, 3))
     legs = _f32(legs).reshape(-1, 14)
-    nom = None if nominal is None else _f32(nominal, (len(legs), 3))
+    nom = _nominal(nominal, len(legs))
     count = np.zeros((len(legs), len(bodies)), np.int32)
     best = np.zeros((len(legs), len(bodies)), np.int32)
     best_d2 = np.zeros((len(legs), len(bodies)), np.float32)

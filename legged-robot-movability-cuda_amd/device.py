@@ -1,5 +1,7 @@
 """Device-resident entry points on torch CUDA(ROCm) tensors.  torch only owns the memory and
 the stream; every computation is a liblrm.so kernel launched on torch's current stream."""
+import math
+
 import numpy as np
 
 from . import _capi
@@ -47,12 +49,101 @@ def _check_field(out, ref, n):
         raise ValueError(f"distance field: expected a float32 (3, >= {n}) tensor with contiguous rows on {ref.device}")
 
 
+def _out(t, ref, shape, dtype, what, want=True):
+    """An output: allocated next to ref when the caller gives none (left None with want=False: the kernel gets NULL),
+    else checked as _check_out does -- at least prod(shape) elements, not that shape: callers pass longer buffers"""
+    if t is None:
+        return _torch().empty(shape, dtype=dtype, device=ref.device) if want else None
+    _check_out(t, ref, dtype, shape if isinstance(shape, int) else math.prod(shape), what)
+    return t
+
+
+def _out_field(t, ref, n):
+    """_out for a (3, n) float32 field"""
+    if t is None:
+        return _torch().empty((3, n), dtype=_torch().float32, device=ref.device)
+    _check_field(t, ref, n)
+    return t
+
+
+def _check_in(t, ref, dtype, numel, what):
+    """Optional device inputs (live_in, pose_live, pose_idx, leg_idx, edge_a, edge_b, count, target_idx) go to the kernels
+    as raw pointers too: None, or on ref's device, of that dtype, contiguous, at least numel entries"""
+    _check_out(t, ref, dtype, numel, what)
+
+
+def _one_per(n, what, *ts):
+    if any(t is not None and t.numel() != n for t in ts):
+        raise ValueError(what)
+
+
+def _launch(name, ref, *args):
+    """One stream-ordered call of liblrm.so on ref's device: torch's current stream there is the last argument"""
+    with _torch().cuda.device(ref.device):
+        _capi.check(getattr(_capi.load(), name)(*args, _stream(ref)))
+
+
 def _leg(leg):
     return np.ascontiguousarray(leg, dtype=np.float32).reshape(-1)
 
 
+def _legs(legs):
+    return np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+
+
 def _q(quat):
     return None if quat is None else np.ascontiguousarray(quat, dtype=np.float32).reshape(4)
+
+
+def _radius3(radius):
+    radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+    if len(radius) != 3:
+        raise ValueError("radius: three values (coxa, femur, tibia link)")
+    return radius
+
+
+def _check_poses(quats, body):
+    """the tensors given to PoseSet.update(), as the calls without a table take them -> nposes"""
+    torch = _torch()
+    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
+        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
+    nposes = quats.shape[0]
+    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
+                                 and tuple(body.shape) == (nposes, 3)):
+        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
+    return nposes
+
+
+def _check_targets(nt, tx, ref):
+    if nt and tx.device != ref.device:
+        raise ValueError("targets and poses must live on one device")
+
+
+def _check_edges(ref, edge_a, edge_b):
+    """-> nedges"""
+    ne = edge_a.numel()
+    _check_in(edge_a, ref, _torch().int32, ne, "edge_a")
+    _check_in(edge_b, ref, _torch().int32, ne, "edge_b")
+    _one_per(ne, "edge_a / edge_b: one pose index each per edge", edge_b)
+    return ne
+
+
+def _check_feet(foot, ref, shape, what):
+    """the int32 (nlegs, nedges) target indices of the transit calls"""
+    if not (foot.is_cuda and foot.device == ref.device and foot.dtype == _torch().int32 and foot.dim() == 2 and foot.is_contiguous()
+            and tuple(foot.shape) == shape):
+        raise ValueError(f"{what}: expected a contiguous int32 tensor of shape ({shape[0]}, {shape[1]}) on the poses' device")
+
+
+def _check_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b):
+    """what edge_transit() and swing_transit() take alike -> (nt, nposes, legs float32 (nlegs, 14), nedges)"""
+    nt = _check_f32(tx, ty, tz)
+    nposes = _check_poses(quats, body)
+    _check_targets(nt, tx, quats)
+    legs = _legs(legs)
+    if not 1 <= len(legs) <= 8:
+        raise ValueError("legs: 1 to 8 legs")
+    return nt, nposes, legs, _check_edges(quats, edge_a, edge_b)
 
 
 def reach(x, y, z, leg, quat=None, out=None, bits=None, want_bits=False):
@@ -60,38 +151,23 @@ def reach(x, y, z, leg, quat=None, out=None, bits=None, want_bits=False):
     ballot bit mask (int64 words, bit i&63 of word i>>6)."""
     torch = _torch()
     n = _check_f32(x, y, z)
-    if out is None:
-        out = torch.empty(n, dtype=torch.uint8, device=x.device)
-    if want_bits and bits is None:
-        bits = torch.empty((n + 63) // 64, dtype=torch.int64, device=x.device)
-    _check_out(out, x, torch.uint8, n, "mask")
-    _check_out(bits, x, torch.int64, (n + 63) // 64, "bit words")
-    leg = _leg(leg)
-    q = _q(quat)
-    L = _capi.load()
-    with torch.cuda.device(x.device):
-        if bits is not None:
-            _capi.check(L.lrm_reach_bits_dev(_dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(out),
-                                             _dp(bits), _stream(x)))
-            return out, bits
-        _capi.check(L.lrm_reach_dev(_dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(out), _stream(x)))
+    out = _out(out, x, n, torch.uint8, "mask")
+    bits = _out(bits, x, (n + 63) // 64, torch.int64, "bit words", want_bits)
+    leg, q = _leg(leg), _q(quat)
+    if bits is not None:
+        _launch("lrm_reach_bits_dev", x, _dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(out), _dp(bits))
+        return out, bits
+    _launch("lrm_reach_dev", x, _dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(out))
     return out
 
 
 def dist(x, y, z, leg, quat=None, out=None, valid=None, want_valid=True):
-    torch = _torch()
     n = _check_f32(x, y, z)
-    if out is None:
-        out = torch.empty((3, n), dtype=torch.float32, device=x.device)
-    if valid is None and want_valid:
-        valid = torch.empty(n, dtype=torch.uint8, device=x.device)
-    _check_field(out, x, n)
-    _check_out(valid, x, torch.uint8, n, "validity bytes")
-    leg = _leg(leg)
-    q = _q(quat)
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.load().lrm_dist_dev(_dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(out[0]),
-                                              _dp(out[1]), _dp(out[2]), _dp(valid), _stream(x)))
+    out = _out_field(out, x, n)
+    valid = _out(valid, x, n, _torch().uint8, "validity bytes", want_valid)
+    leg, q = _leg(leg), _q(quat)
+    _launch("lrm_dist_dev", x, _dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(out[0]), _dp(out[1]), _dp(out[2]),
+            _dp(valid))
     return out, valid
 
 
@@ -99,19 +175,12 @@ def reach_dist(x, y, z, leg, quat=None, mask=None, out=None, bits=None):
     """One launch: reach mask (bytes and/or ballot bit words) + distance field (3, n)."""
     torch = _torch()
     n = _check_f32(x, y, z)
-    if out is None:
-        out = torch.empty((3, n), dtype=torch.float32, device=x.device)
-    if mask is None and bits is None:
-        mask = torch.empty(n, dtype=torch.uint8, device=x.device)
-    _check_field(out, x, n)
-    _check_out(mask, x, torch.uint8, n, "mask")
-    _check_out(bits, x, torch.int64, (n + 63) // 64, "bit words")
-    leg = _leg(leg)
-    q = _q(quat)
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.load().lrm_reach_dist_bits_dev(_dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q),
-                                                         _dp(mask), _dp(bits), _dp(out[0]), _dp(out[1]), _dp(out[2]),
-                                                         _stream(x)))
+    out = _out_field(out, x, n)
+    mask = _out(mask, x, n, torch.uint8, "mask", want=bits is None)
+    bits = _out(bits, x, (n + 63) // 64, torch.int64, "bit words", want=False)
+    leg, q = _leg(leg), _q(quat)
+    _launch("lrm_reach_dist_bits_dev", x, _dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(mask), _dp(bits),
+            _dp(out[0]), _dp(out[1]), _dp(out[2]))
     if bits is not None:
         return mask, out, bits
     return mask, out
@@ -121,40 +190,28 @@ def ik(x, y, z, leg, quat=None, seed=None, out=None, status=None):
     """Joint angles (coxa, femur, tibia) that put the tip on each point, or as near as the joint limits allow, and the
     LRM_IK_* status byte of each (include/lrm.h).  seed: None (mid-range of the limits) or three float32 tensors
     (coxa, femur, tibia) of the points' length.  -> (angles (3, n) float32, status uint8[n]); one launch."""
-    torch = _torch()
     n = _check_f32(x, y, z)
     if seed is not None:
         if len(seed) != 3:
             raise ValueError("seed: three tensors (coxa, femur, tibia) or None")
         if _check_f32(x, *seed) != n:
             raise ValueError("seed: one angle per point")
-    if out is None:
-        out = torch.empty((3, n), dtype=torch.float32, device=x.device)
-    if status is None:
-        status = torch.empty(n, dtype=torch.uint8, device=x.device)
-    _check_field(out, x, n)
-    _check_out(status, x, torch.uint8, n, "status")
-    leg = _leg(leg)
-    q = _q(quat)
+    out = _out_field(out, x, n)
+    status = _out(status, x, n, _torch().uint8, "status")
+    leg, q = _leg(leg), _q(quat)
     sc, sf, st = (None, None, None) if seed is None else seed
-    with torch.cuda.device(x.device):
-        _capi.check(_capi.load().lrm_ik_dev(_dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(sc), _dp(sf),
-                                            _dp(st), _dp(out[0]), _dp(out[1]), _dp(out[2]), _dp(status), _stream(x)))
+    _launch("lrm_ik_dev", x, _dp(x), _dp(y), _dp(z), n, _capi._ptr(leg), _capi._ptr(q), _dp(sc), _dp(sf), _dp(st), _dp(out[0]),
+            _dp(out[1]), _dp(out[2]), _dp(status))
     return out, status
 
 
 def fk(coxa, femur, tibia, leg, quat=None, out=None):
     """Tip positions (3, n) of joint angles, the inverse of the frame chain ik() solves in; one launch."""
-    torch = _torch()
     n = _check_f32(coxa, femur, tibia)
-    if out is None:
-        out = torch.empty((3, n), dtype=torch.float32, device=coxa.device)
-    _check_field(out, coxa, n)
-    leg = _leg(leg)
-    q = _q(quat)
-    with torch.cuda.device(coxa.device):
-        _capi.check(_capi.load().lrm_fk_dev(_dp(coxa), _dp(femur), _dp(tibia), n, _capi._ptr(leg), _capi._ptr(q),
-                                            _dp(out[0]), _dp(out[1]), _dp(out[2]), _stream(coxa)))
+    out = _out_field(out, coxa, n)
+    leg, q = _leg(leg), _q(quat)
+    _launch("lrm_fk_dev", coxa, _dp(coxa), _dp(femur), _dp(tibia), n, _capi._ptr(leg), _capi._ptr(q), _dp(out[0]), _dp(out[1]),
+            _dp(out[2]))
     return out
 
 
@@ -164,20 +221,13 @@ def reach_any(bx, by, bz, tx, ty, tz, legs, quat=None, out=None, all_legs=None):
     torch = _torch()
     nb = _check_f32(bx, by, bz)
     nt = _check_f32(tx, ty, tz)
-    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
-    if out is None:
-        out = torch.empty((len(legs), nb), dtype=torch.uint8, device=bx.device)
-    if all_legs is None:
-        all_legs = torch.empty(nb, dtype=torch.uint8, device=bx.device)
-    q = _q(quat)
-    _check_out(out, bx, torch.uint8, len(legs) * nb, "per-leg results")
-    _check_out(all_legs, bx, torch.uint8, nb, "per-body results")
+    legs, q = _legs(legs), _q(quat)
+    out = _out(out, bx, (len(legs), nb), torch.uint8, "per-leg results")
+    all_legs = _out(all_legs, bx, nb, torch.uint8, "per-body results")
     if nt and tx.device != bx.device:
         raise ValueError("bodies and targets must live on one device")
-    with torch.cuda.device(bx.device):
-        _capi.check(_capi.load().lrm_reach_any_dev(_dp(bx), _dp(by), _dp(bz), nb, _dp(tx), _dp(ty), _dp(tz), nt,
-                                                   _capi._ptr(legs), len(legs), _capi._ptr(q), _dp(out),
-                                                   _dp(all_legs), _stream(bx)))
+    _launch("lrm_reach_any_dev", bx, _dp(bx), _dp(by), _dp(bz), nb, _dp(tx), _dp(ty), _dp(tz), nt, _capi._ptr(legs), len(legs),
+            _capi._ptr(q), _dp(out), _dp(all_legs))
     return out, all_legs
 
 
@@ -188,24 +238,16 @@ def footholds(bx, by, bz, tx, ty, tz, legs, quat=None, nominal=None, count=None,
     torch = _torch()
     nb = _check_f32(bx, by, bz)
     nt = _check_f32(tx, ty, tz)
-    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+    legs, q = _legs(legs), _q(quat)
     nom = None if nominal is None else np.ascontiguousarray(nominal, dtype=np.float32).reshape(len(legs), 3)
-    if count is None:
-        count = torch.empty((len(legs), nb), dtype=torch.int32, device=bx.device)
-    if best is None:
-        best = torch.empty((len(legs), nb), dtype=torch.int32, device=bx.device)
-    if best_d2 is None:
-        best_d2 = torch.empty((len(legs), nb), dtype=torch.float32, device=bx.device)
-    q = _q(quat)
-    _check_out(count, bx, torch.int32, len(legs) * nb, "per-leg counts")
-    _check_out(best, bx, torch.int32, len(legs) * nb, "per-leg choices")
-    _check_out(best_d2, bx, torch.float32, len(legs) * nb, "per-leg squared distances")
+    shape = (len(legs), nb)
+    count = _out(count, bx, shape, torch.int32, "per-leg counts")
+    best = _out(best, bx, shape, torch.int32, "per-leg choices")
+    best_d2 = _out(best_d2, bx, shape, torch.float32, "per-leg squared distances")
     if nt and tx.device != bx.device:
         raise ValueError("bodies and targets must live on one device")
-    with torch.cuda.device(bx.device):
-        _capi.check(_capi.load().lrm_footholds_dev(_dp(bx), _dp(by), _dp(bz), nb, _dp(tx), _dp(ty), _dp(tz), nt,
-                                                   _capi._ptr(legs), len(legs), _capi._ptr(q), _capi._ptr(nom), _dp(count),
-                                                   _dp(best), _dp(best_d2), _stream(bx)))
+    _launch("lrm_footholds_dev", bx, _dp(bx), _dp(by), _dp(bz), nb, _dp(tx), _dp(ty), _dp(tz), nt, _capi._ptr(legs), len(legs),
+            _capi._ptr(q), _capi._ptr(nom), _dp(count), _dp(best), _dp(best_d2))
     return count, best, best_d2
 
 
@@ -217,11 +259,8 @@ def foothold_offsets(count, out=None):
     n = count.numel()
     if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()):
         raise ValueError("count: expected a contiguous int32 CUDA tensor")
-    if out is None:
-        out = torch.empty(n + 1, dtype=torch.int64, device=count.device)
-    _check_out(out, count, torch.int64, n + 1, "offsets")
-    with torch.cuda.device(count.device):
-        _capi.check(_capi.load().lrm_foothold_offsets_dev(_dp(count) if n else None, n, _dp(out), _stream(count)))
+    out = _out(out, count, n + 1, torch.int64, "offsets")
+    _launch("lrm_foothold_offsets_dev", count, _dp(count) if n else None, n, _dp(out))
     return out
 
 
@@ -282,12 +321,10 @@ def positionability(bx, by, bz, tx, ty, tz, legs, quats, reference_culls=0, acti
     torch = _torch()
     nb = _check_f32(bx, by, bz)
     nt = _check_f32(tx, ty, tz) if tx.numel() else 0
-    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
+    legs = _legs(legs)
     quats = np.ascontiguousarray(quats, dtype=np.float32).reshape(-1, 4)
-    if out is None:
-        out = torch.empty(nb, dtype=torch.uint8, device=bx.device)
-    _check_out(out, bx, torch.uint8, nb, "accepted bytes")
-    _check_out(active, bx, torch.uint8, nb, "active bytes")
+    out = _out(out, bx, nb, torch.uint8, "accepted bytes")
+    _check_in(active, bx, torch.uint8, nb, "active bytes")
     ms = C.c_float(0)
     with torch.cuda.device(bx.device):
         torch.cuda.synchronize(bx.device)  # the library works on the null stream
@@ -298,28 +335,19 @@ def positionability(bx, by, bz, tx, ty, tz, legs, quats, reference_culls=0, acti
 
 
 def any_in_sphere(cx, cy, cz, tx, ty, tz, radius, out=None):
-    torch = _torch()
     nc = _check_f32(cx, cy, cz)
     nt = _check_f32(tx, ty, tz)
-    if out is None:
-        out = torch.empty(nc, dtype=torch.uint8, device=cx.device)
-    _check_out(out, cx, torch.uint8, nc, "results")
-    with torch.cuda.device(cx.device):
-        _capi.check(_capi.load().lrm_any_in_sphere_dev(_dp(cx), _dp(cy), _dp(cz), nc, _dp(tx), _dp(ty), _dp(tz), nt,
-                                                       radius, _dp(out), _stream(cx)))
+    out = _out(out, cx, nc, _torch().uint8, "results")
+    _launch("lrm_any_in_sphere_dev", cx, _dp(cx), _dp(cy), _dp(cz), nc, _dp(tx), _dp(ty), _dp(tz), nt, radius, _dp(out))
     return out
 
 
 def any_in_cylinder(cx, cy, cz, tx, ty, tz, radius, plus_z, minus_z, out=None):
-    torch = _torch()
     nc = _check_f32(cx, cy, cz)
     nt = _check_f32(tx, ty, tz)
-    if out is None:
-        out = torch.empty(nc, dtype=torch.uint8, device=cx.device)
-    _check_out(out, cx, torch.uint8, nc, "results")
-    with torch.cuda.device(cx.device):
-        _capi.check(_capi.load().lrm_any_in_cylinder_dev(_dp(cx), _dp(cy), _dp(cz), nc, _dp(tx), _dp(ty), _dp(tz), nt,
-                                                         radius, plus_z, minus_z, _dp(out), _stream(cx)))
+    out = _out(out, cx, nc, _torch().uint8, "results")
+    _launch("lrm_any_in_cylinder_dev", cx, _dp(cx), _dp(cy), _dp(cz), nc, _dp(tx), _dp(ty), _dp(tz), nt, radius, plus_z, minus_z,
+            _dp(out))
     return out
 
 
@@ -360,44 +388,27 @@ def stance_stability(tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None
     and may run next to anything."""
     torch = _torch()
     nt = _check_f32(tx, ty, tz)
-    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
-        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
-    nposes = quats.shape[0]
-    if nt and tx.device != quats.device:
-        raise ValueError("targets and poses must live on one device")
-    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
-                                 and tuple(body.shape) == (nposes, 3)):
-        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
+    nposes = _check_poses(quats, body)
+    _check_targets(nt, tx, quats)
     if not (foot.is_cuda and foot.device == quats.device and foot.dtype == torch.int32 and foot.dim() == 2 and foot.is_contiguous()
             and 1 <= foot.shape[0] <= 8):
         raise ValueError("foot: expected a contiguous int32 tensor of shape (nlegs, nstances), 1 to 8 legs, on the poses' device")
     nl, ns = foot.shape
-    _check_out(pose_idx, quats, torch.int32, ns, "pose_idx")
-    _check_out(live_in, quats, torch.uint8, ns, "live_in")
-    if pose_idx is not None and pose_idx.numel() != ns or live_in is not None and live_in.numel() != ns:
-        raise ValueError("pose_idx / live_in: one entry per stance")
+    _check_in(pose_idx, quats, torch.int32, ns, "pose_idx")
+    _check_in(live_in, quats, torch.uint8, ns, "live_in")
+    _one_per(ns, "pose_idx / live_in: one entry per stance", pose_idx, live_in)
     if pose_idx is None and ns > nposes:
         raise ValueError("without pose_idx stance s takes pose s: nstances <= nposes")
     com, plane = _capi._stance_host(com, plane)
     lift = _capi.stance_lift(lift, nl)
     nm = len(lift)
-    if margin is None:
-        margin = torch.empty((nm, ns), dtype=torch.float32, device=quats.device)
-    if edge is None:
-        edge = torch.empty((nm, ns), dtype=torch.uint8, device=quats.device)
-    if stable is None:
-        stable = torch.empty((nm, ns), dtype=torch.uint8, device=quats.device)
-    if feet is None:
-        feet = torch.empty(ns, dtype=torch.uint8, device=quats.device)
-    _check_out(margin, quats, torch.float32, nm * ns, "margins")
-    _check_out(edge, quats, torch.uint8, nm * ns, "edge codes")
-    _check_out(stable, quats, torch.uint8, nm * ns, "stable bytes")
-    _check_out(feet, quats, torch.uint8, ns, "per-stance feet")
-    with torch.cuda.device(quats.device):
-        _capi.check(_capi.load().lrm_stance_stability_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _dp(pose_idx),
-                                                          _dp(foot), ns, nl, _capi._ptr(com), _capi._ptr(plane), _capi._ptr(lift), nm,
-                                                          float(min_margin), _dp(live_in), _dp(margin), _dp(edge), _dp(stable), _dp(feet),
-                                                          _stream(quats)))
+    margin = _out(margin, quats, (nm, ns), torch.float32, "margins")
+    edge = _out(edge, quats, (nm, ns), torch.uint8, "edge codes")
+    stable = _out(stable, quats, (nm, ns), torch.uint8, "stable bytes")
+    feet = _out(feet, quats, ns, torch.uint8, "per-stance feet")
+    _launch("lrm_stance_stability_dev", quats, _dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _dp(pose_idx), _dp(foot),
+            ns, nl, _capi._ptr(com), _capi._ptr(plane), _capi._ptr(lift), nm, float(min_margin), _dp(live_in), _dp(margin), _dp(edge),
+            _dp(stable), _dp(feet))
     return margin, edge, stable, feet
 
 
@@ -418,61 +429,23 @@ def edge_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot, nsamples=9
     is directly the live_in of the other posed calls.  Every tensor must be contiguous.  One launch, no allocation beyond
     missing outputs, no shared buffer: it can be captured in a graph and may run next to anything."""
     torch = _torch()
-    nt = _check_f32(tx, ty, tz)
-    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
-        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
-    nposes = quats.shape[0]
-    if nt and tx.device != quats.device:
-        raise ValueError("targets and poses must live on one device")
-    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
-                                 and tuple(body.shape) == (nposes, 3)):
-        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
-    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
-    nl = len(legs)
-    if not 1 <= nl <= 8:
-        raise ValueError("legs: 1 to 8 legs")
-    ne = edge_a.numel()
-    _check_out(edge_a, quats, torch.int32, ne, "edge_a")
-    _check_out(edge_b, quats, torch.int32, ne, "edge_b")
-    if edge_b.numel() != ne:
-        raise ValueError("edge_a / edge_b: one pose index each per edge")
-    if not (foot.is_cuda and foot.device == quats.device and foot.dtype == torch.int32 and foot.dim() == 2 and foot.is_contiguous()
-            and tuple(foot.shape) == (nl, ne)):
-        raise ValueError(f"foot: expected a contiguous int32 tensor of shape ({nl}, {ne}) on the poses' device")
-    _check_out(live_in, quats, torch.uint8, ne, "live_in")
-    if live_in is not None and live_in.numel() != ne:
-        raise ValueError("live_in: one byte per edge")
+    nt, nposes, legs, ne = _check_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b)
+    shape = (len(legs), ne)
+    _check_feet(foot, quats, shape, "foot")
+    _check_in(live_in, quats, torch.uint8, ne, "live_in")
+    _one_per(ne, "live_in: one byte per edge", live_in)
     nsamples = _capi._nsamples(nsamples)
-    shape, n, dev = (nl, ne), nl * ne, quats.device
-    if mask is None:
-        mask = torch.empty(shape, dtype=torch.int64, device=dev)
-    if reached is None:
-        reached = torch.empty(shape, dtype=torch.int32, device=dev)
-    if first_miss is None:
-        first_miss = torch.empty(shape, dtype=torch.int32, device=dev)
-    if worst is None:
-        worst = torch.empty(shape, dtype=torch.int32, device=dev)
-    if worst_d2 is None:
-        worst_d2 = torch.empty(shape, dtype=torch.float32, device=dev)
-    if planted is None:
-        planted = torch.empty(ne, dtype=torch.uint8, device=dev)
-    if clear is None:
-        clear = torch.empty(ne, dtype=torch.uint8, device=dev)
-    if advance is None:
-        advance = torch.empty(ne, dtype=torch.int32, device=dev)
-    _check_out(mask, quats, torch.int64, n, "per-leg sample masks")
-    _check_out(reached, quats, torch.int32, n, "per-leg reached counts")
-    _check_out(first_miss, quats, torch.int32, n, "per-leg first misses")
-    _check_out(worst, quats, torch.int32, n, "per-leg worst samples")
-    _check_out(worst_d2, quats, torch.float32, n, "per-leg worst squared distances")
-    _check_out(planted, quats, torch.uint8, ne, "per-edge planted bits")
-    _check_out(clear, quats, torch.uint8, ne, "per-edge clear bytes")
-    _check_out(advance, quats, torch.int32, ne, "per-edge advances")
-    with torch.cuda.device(dev):
-        _capi.check(_capi.load().lrm_edge_transit_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _capi._ptr(legs),
-                                                            nl, _dp(edge_a), _dp(edge_b), ne, _dp(foot), nsamples, _dp(live_in), _dp(mask),
-                                                            _dp(reached), _dp(first_miss), _dp(worst), _dp(worst_d2), _dp(planted),
-                                                            _dp(clear), _dp(advance), _stream(quats)))
+    mask = _out(mask, quats, shape, torch.int64, "per-leg sample masks")
+    reached = _out(reached, quats, shape, torch.int32, "per-leg reached counts")
+    first_miss = _out(first_miss, quats, shape, torch.int32, "per-leg first misses")
+    worst = _out(worst, quats, shape, torch.int32, "per-leg worst samples")
+    worst_d2 = _out(worst_d2, quats, shape, torch.float32, "per-leg worst squared distances")
+    planted = _out(planted, quats, ne, torch.uint8, "per-edge planted bits")
+    clear = _out(clear, quats, ne, torch.uint8, "per-edge clear bytes")
+    advance = _out(advance, quats, ne, torch.int32, "per-edge advances")
+    _launch("lrm_edge_transit_posed_dev", quats, _dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _capi._ptr(legs),
+            len(legs), _dp(edge_a), _dp(edge_b), ne, _dp(foot), nsamples, _dp(live_in), _dp(mask), _dp(reached), _dp(first_miss),
+            _dp(worst), _dp(worst_d2), _dp(planted), _dp(clear), _dp(advance))
     return mask, reached, first_miss, worst, worst_d2, planted, clear, advance
 
 
@@ -518,97 +491,40 @@ def swing_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot_from, foot
     must be contiguous.  No table.  With foot_radius == 0 one launch and no shared buffer; with foot_radius > 0 and 4096 targets
     or more it uses the pair kernels' box buffer (their threading rules; graph capture after one call on the largest cloud)."""
     torch = _torch()
-    nt = _check_f32(tx, ty, tz)
-    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
-        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
-    nposes = quats.shape[0]
-    if nt and tx.device != quats.device:
-        raise ValueError("targets and poses must live on one device")
-    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
-                                 and tuple(body.shape) == (nposes, 3)):
-        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
-    legs = np.ascontiguousarray(legs, dtype=np.float32).reshape(-1, 14)
-    nl = len(legs)
-    if not 1 <= nl <= 8:
-        raise ValueError("legs: 1 to 8 legs")
-    ne = edge_a.numel()
-    _check_out(edge_a, quats, torch.int32, ne, "edge_a")
-    _check_out(edge_b, quats, torch.int32, ne, "edge_b")
-    if edge_b.numel() != ne:
-        raise ValueError("edge_a / edge_b: one pose index each per edge")
-    for foot, what in ((foot_from, "foot_from"), (foot_to, "foot_to")):
-        if not (foot.is_cuda and foot.device == quats.device and foot.dtype == torch.int32 and foot.dim() == 2 and foot.is_contiguous()
-                and tuple(foot.shape) == (nl, ne)):
-            raise ValueError(f"{what}: expected a contiguous int32 tensor of shape ({nl}, {ne}) on the poses' device")
-    _check_out(live_in, quats, torch.uint8, ne, "live_in")
-    if live_in is not None and live_in.numel() != ne:
-        raise ValueError("live_in: one byte per edge")
+    nt, nposes, legs, ne = _check_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b)
+    shape = (len(legs), ne)
+    _check_feet(foot_from, quats, shape, "foot_from")
+    _check_feet(foot_to, quats, shape, "foot_to")
+    _check_in(live_in, quats, torch.uint8, ne, "live_in")
+    _one_per(ne, "live_in: one byte per edge", live_in)
     nsamples = _capi._nsamples(nsamples)
     lift, up, foot_radius, margin, skip = _capi._swing_scalars(lift, up, foot_radius, margin, skip)
-    shape, n, dev = (nl, ne), nl * ne, quats.device
-    if mask is None:
-        mask = torch.empty(shape, dtype=torch.int64, device=dev)
-    if reached is None:
-        reached = torch.empty(shape, dtype=torch.int32, device=dev)
-    if first_miss is None:
-        first_miss = torch.empty(shape, dtype=torch.int32, device=dev)
-    if worst is None:
-        worst = torch.empty(shape, dtype=torch.int32, device=dev)
-    if worst_d2 is None:
-        worst_d2 = torch.empty(shape, dtype=torch.float32, device=dev)
-    if hits is None:
-        hits = torch.empty(shape, dtype=torch.int32, device=dev)
-    if hit_seg is None:
-        hit_seg = torch.empty(shape, dtype=torch.int32, device=dev)
-    if near is None:
-        near = torch.empty(shape, dtype=torch.int32, device=dev)
-    if pen is None:
-        pen = torch.empty(shape, dtype=torch.float32, device=dev)
-    if swinging is None:
-        swinging = torch.empty(ne, dtype=torch.uint8, device=dev)
-    if clear is None:
-        clear = torch.empty(ne, dtype=torch.uint8, device=dev)
-    _check_out(mask, quats, torch.int64, n, "per-leg sample masks")
-    _check_out(reached, quats, torch.int32, n, "per-leg reached counts")
-    _check_out(first_miss, quats, torch.int32, n, "per-leg first misses")
-    _check_out(worst, quats, torch.int32, n, "per-leg worst samples")
-    _check_out(worst_d2, quats, torch.float32, n, "per-leg worst squared distances")
-    _check_out(hits, quats, torch.int32, n, "per-leg hit counts")
-    _check_out(hit_seg, quats, torch.int32, n, "per-leg first hit segments")
-    _check_out(near, quats, torch.int32, n, "per-leg deepest near targets")
-    _check_out(pen, quats, torch.float32, n, "per-leg penetrations")
-    _check_out(swinging, quats, torch.uint8, ne, "per-edge swinging bits")
-    _check_out(clear, quats, torch.uint8, ne, "per-edge clear bytes")
-    with torch.cuda.device(dev):
-        _capi.check(_capi.load().lrm_swing_transit_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _capi._ptr(legs),
-                                                             nl, _dp(edge_a), _dp(edge_b), ne, _dp(foot_from), _dp(foot_to), nsamples, lift,
-                                                             _capi._ptr(up), foot_radius, margin, skip, _dp(live_in), _dp(mask),
-                                                             _dp(reached), _dp(first_miss), _dp(worst), _dp(worst_d2), _dp(hits),
-                                                             _dp(hit_seg), _dp(near), _dp(pen), _dp(swinging), _dp(clear),
-                                                             _stream(quats)))
+    mask = _out(mask, quats, shape, torch.int64, "per-leg sample masks")
+    reached = _out(reached, quats, shape, torch.int32, "per-leg reached counts")
+    first_miss = _out(first_miss, quats, shape, torch.int32, "per-leg first misses")
+    worst = _out(worst, quats, shape, torch.int32, "per-leg worst samples")
+    worst_d2 = _out(worst_d2, quats, shape, torch.float32, "per-leg worst squared distances")
+    hits = _out(hits, quats, shape, torch.int32, "per-leg hit counts")
+    hit_seg = _out(hit_seg, quats, shape, torch.int32, "per-leg first hit segments")
+    near = _out(near, quats, shape, torch.int32, "per-leg deepest near targets")
+    pen = _out(pen, quats, shape, torch.float32, "per-leg penetrations")
+    swinging = _out(swinging, quats, ne, torch.uint8, "per-edge swinging bits")
+    clear = _out(clear, quats, ne, torch.uint8, "per-edge clear bytes")
+    _launch("lrm_swing_transit_posed_dev", quats, _dp(tx), _dp(ty), _dp(tz), nt, _dp(quats), _dp(body), nposes, _capi._ptr(legs),
+            len(legs), _dp(edge_a), _dp(edge_b), ne, _dp(foot_from), _dp(foot_to), nsamples, lift, _capi._ptr(up), foot_radius, margin,
+            skip, _dp(live_in), _dp(mask), _dp(reached), _dp(first_miss), _dp(worst), _dp(worst_d2), _dp(hits), _dp(hit_seg), _dp(near),
+            _dp(pen), _dp(swinging), _dp(clear))
     return mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging, clear
 
 
 def dbg_edge_transit_samples(quats, body, edge_a, edge_b, nsamples):
     """lrm_dbg_edge_transit_samples_dev: the sampled path of edge_transit() -> float32 (nedges, nsamples, 7) on the device: the
     quaternion and the body position of every sample (nan for an edge with an end out of range); one sample per lane."""
-    torch = _torch()
-    if not (quats.is_cuda and quats.dtype == torch.float32 and quats.dim() == 2 and quats.shape[1] == 4 and quats.is_contiguous()):
-        raise ValueError("quats: expected a contiguous float32 CUDA tensor of shape (nposes, 4)")
-    nposes = quats.shape[0]
-    if body is not None and not (body.is_cuda and body.device == quats.device and body.dtype == torch.float32 and body.is_contiguous()
-                                 and tuple(body.shape) == (nposes, 3)):
-        raise ValueError("body: expected a contiguous float32 tensor of shape (nposes, 3) on the poses' device")
-    ne = edge_a.numel()
-    _check_out(edge_a, quats, torch.int32, ne, "edge_a")
-    _check_out(edge_b, quats, torch.int32, ne, "edge_b")
-    if edge_b.numel() != ne:
-        raise ValueError("edge_a / edge_b: one pose index each per edge")
+    nposes = _check_poses(quats, body)
+    ne = _check_edges(quats, edge_a, edge_b)
     nsamples = _capi._nsamples(nsamples)
-    out = torch.empty((ne, nsamples, 7), dtype=torch.float32, device=quats.device)
-    with torch.cuda.device(quats.device):
-        _capi.check(_capi.load().lrm_dbg_edge_transit_samples_dev(_dp(quats), _dp(body), nposes, _dp(edge_a), _dp(edge_b), ne, nsamples,
-                                                                  _dp(out), _stream(quats)))
+    out = _torch().empty((ne, nsamples, 7), dtype=_torch().float32, device=quats.device)
+    _launch("lrm_dbg_edge_transit_samples_dev", quats, _dp(quats), _dp(body), nposes, _dp(edge_a), _dp(edge_b), ne, nsamples, _dp(out))
     return out
 
 
@@ -619,11 +535,8 @@ def dbg_link_pair_dist(segs, out=None):
     if not (segs.is_cuda and segs.dtype == torch.float32 and segs.dim() == 2 and segs.shape[1] == 12 and segs.is_contiguous()):
         raise ValueError("segs: expected a contiguous float32 CUDA tensor of shape (n, 12)")
     n = segs.shape[0]
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=segs.device)
-    _check_out(out, segs, torch.float32, n, "distances")
-    with torch.cuda.device(segs.device):
-        _capi.check(_capi.load().lrm_dbg_link_pair_dist_dev(_dp(segs), n, _dp(out), _stream(segs)))
+    out = _out(out, segs, n, torch.float32, "distances")
+    _launch("lrm_dbg_link_pair_dist_dev", segs, _dp(segs), n, _dp(out))
     return out
 
 
@@ -634,12 +547,8 @@ def dbg_trunk_link_dist(segs, trunk_radius, plus_z, minus_z, out=None):
     if not (segs.is_cuda and segs.dtype == torch.float32 and segs.dim() == 2 and segs.shape[1] == 6 and segs.is_contiguous()):
         raise ValueError("segs: expected a contiguous float32 CUDA tensor of shape (n, 6)")
     n = segs.shape[0]
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=segs.device)
-    _check_out(out, segs, torch.float32, n, "distances")
-    with torch.cuda.device(segs.device):
-        _capi.check(_capi.load().lrm_dbg_trunk_link_dist_dev(_dp(segs), n, float(trunk_radius), float(plus_z), float(minus_z), _dp(out),
-                                                             _stream(segs)))
+    out = _out(out, segs, n, torch.float32, "distances")
+    _launch("lrm_dbg_trunk_link_dist_dev", segs, _dp(segs), n, float(trunk_radius), float(plus_z), float(minus_z), _dp(out))
     return out
 
 
@@ -696,6 +605,52 @@ class PoseSet:
     def nlegs(self):
         return len(self.legs)
 
+    def _need(self, table=None):
+        """ValueError unless the set owns that table ("footholds" or "ik") and update() has run"""
+        if table is not None and (self.fh_workspace if table == "footholds" else self.ik_workspace) is None:
+            raise ValueError(f"PoseSet: built without {table}=True")
+        if self.nposes == 0:
+            raise ValueError("PoseSet: update() before the first query")
+
+    def _cloud(self, tx, ty, tz, table="footholds"):
+        """the preamble of the calls that take a target cloud and read that table -> nt"""
+        nt = _check_f32(tx, ty, tz)
+        self._need(table)
+        _check_targets(nt, tx, self.workspace)
+        return nt
+
+    def _check_edge_range(self, edge_a, edge_b, check):
+        """check=True of the edge calls: the pose indices are read back (one host synchronisation)"""
+        if check and edge_a.numel() and edge_a.numel() == edge_b.numel():
+            lo = min(int(edge_a.min()), int(edge_b.min()))
+            hi = max(int(edge_a.max()), int(edge_b.max()))
+            if lo < 0 or hi >= self.nposes:
+                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
+
+    def _last_update(self, quats):
+        """quats must be the tensor of the last update(): the set keeps compiled records, not the poses"""
+        self._need()
+        if quats.dim() != 2 or quats.shape[0] != self.nposes:
+            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
+        if quats.device != self.workspace.device:
+            raise ValueError("quats and poses must live on one device")
+
+    def _sets(self, angles, radius, pose_idx, live_in):
+        """the sets of self_clearance() and trunk_clearance() -> (nsets, radius float32[3])"""
+        torch = _torch()
+        self._need("ik")
+        if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
+                and angles.shape[0] == 3 and angles.shape[1] % self.nlegs == 0 and angles.is_contiguous()):
+            raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {self.nlegs} * nsets) tensor on {self.workspace.device}")
+        ns = angles.shape[1] // self.nlegs
+        radius = _radius3(radius)
+        _check_in(pose_idx, self.workspace, torch.int32, ns, "pose_idx")
+        _check_in(live_in, self.workspace, torch.uint8, ns, "live_in")
+        _one_per(ns, "pose_idx / live_in: one entry per set", pose_idx, live_in)
+        if pose_idx is None and ns > self.nposes:
+            raise ValueError("without pose_idx set s takes pose s: nsets <= nposes")
+        return ns, radius
+
     def update(self, quats, body=None):
         """(Re)compile the records of poses 0 .. len(quats) - 1 from quats (float32 [nposes, 4], the quat convention
         of the single-pose calls) and body (float32 [nposes, 3] or None: no offset), both on this set's device."""
@@ -705,20 +660,17 @@ class PoseSet:
         nposes = quats.shape[0]
         if not 1 <= nposes <= self.nposes_max:
             raise ValueError(f"quats: 1 to {self.nposes_max} poses")
-        _check_out(quats, self.workspace, torch.float32, 4 * nposes, "quats")
-        _check_out(body, self.workspace, torch.float32, 3 * nposes, "body")
+        ws = self.workspace
+        _check_in(quats, ws, torch.float32, 4 * nposes, "quats")
+        _check_in(body, ws, torch.float32, 3 * nposes, "body")
         if body is not None and tuple(body.shape) != (nposes, 3):
             raise ValueError("body: expected a float32 tensor of shape (nposes, 3)")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_pose_compile_dev(_dp(quats), _dp(body), nposes, _capi._ptr(self.legs), self.nlegs,
-                                                          _dp(self.workspace), _stream(self.workspace)))
-            if self.ik_workspace is not None:
-                _capi.check(_capi.load().lrm_pose_ik_compile_dev(_dp(quats), nposes, _capi._ptr(self.legs), self.nlegs,
-                                                                 _dp(self.ik_workspace), _stream(self.workspace)))
-            if self.fh_workspace is not None:
-                _capi.check(_capi.load().lrm_pose_footholds_compile_dev(_dp(quats), nposes, _capi._ptr(self.legs), self.nlegs,
-                                                                        _capi._ptr(self.nominal), _dp(self.fh_workspace),
-                                                                        _stream(self.workspace)))
+        _launch("lrm_pose_compile_dev", ws, _dp(quats), _dp(body), nposes, _capi._ptr(self.legs), self.nlegs, _dp(ws))
+        if self.ik_workspace is not None:
+            _launch("lrm_pose_ik_compile_dev", ws, _dp(quats), nposes, _capi._ptr(self.legs), self.nlegs, _dp(self.ik_workspace))
+        if self.fh_workspace is not None:
+            _launch("lrm_pose_footholds_compile_dev", ws, _dp(quats), nposes, _capi._ptr(self.legs), self.nlegs,
+                    _capi._ptr(self.nominal), _dp(self.fh_workspace))
         self.nposes = nposes
         return self
 
@@ -729,30 +681,14 @@ class PoseSet:
         -> (count int32, best int32, best_d2 float32, each [nlegs, nposes]; all_legs uint8[nposes]).  One launch behind
         the cloud's bounding boxes; best.view(-1) is ik()'s target_idx with footholds_layout(nposes, nlegs, device)."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        if self.fh_workspace is None:
-            raise ValueError("PoseSet: built without footholds=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
-        shape, n = (self.nlegs, self.nposes), self.nlegs * self.nposes
-        if count is None:
-            count = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if best is None:
-            best = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if best_d2 is None:
-            best_d2 = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if all_legs is None:
-            all_legs = torch.empty(self.nposes, dtype=torch.uint8, device=self.device)
-        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
-        _check_out(best, self.workspace, torch.int32, n, "per-leg choices")
-        _check_out(best_d2, self.workspace, torch.float32, n, "per-leg squared distances")
-        _check_out(all_legs, self.workspace, torch.uint8, self.nposes, "per-pose bytes")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_footholds_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace), _dp(self.fh_workspace),
-                                                             self.nposes, self.nlegs, _dp(count), _dp(best), _dp(best_d2),
-                                                             _dp(all_legs), _stream(self.workspace)))
+        nt = self._cloud(tx, ty, tz)
+        ws, shape = self.workspace, (self.nlegs, self.nposes)
+        count = _out(count, ws, shape, torch.int32, "per-leg counts")
+        best = _out(best, ws, shape, torch.int32, "per-leg choices")
+        best_d2 = _out(best_d2, ws, shape, torch.float32, "per-leg squared distances")
+        all_legs = _out(all_legs, ws, self.nposes, torch.uint8, "per-pose bytes")
+        _launch("lrm_footholds_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.fh_workspace), self.nposes, self.nlegs,
+                _dp(count), _dp(best), _dp(best_d2), _dp(all_legs))
         return count, best, best_d2, all_legs
 
     def foothold_lists(self, tx, ty, tz, count=None, offsets=None, capacity=None, idx=None, d2=None, written=None, want_d2=True):
@@ -768,39 +704,24 @@ class PoseSet:
             -> foothold_offsets -> foothold_lists can be captured in a graph after one warm call on the largest cloud;
             a list that does not fit is cut short and written says so."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        if self.fh_workspace is None:
-            raise ValueError("PoseSet: built without footholds=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
-        n = self.nlegs * self.nposes
+        nt = self._cloud(tx, ty, tz)
+        ws, n = self.workspace, self.nlegs * self.nposes
         if offsets is None:
             if count is None:
                 count = self.footholds(tx, ty, tz)[0]
-            _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
+            _check_in(count, ws, torch.int32, n, "per-leg counts")
             offsets = foothold_offsets(count.view(-1)[:n])
-        _check_out(offsets, self.workspace, torch.int64, n + 1, "offsets")
+        _check_in(offsets, ws, torch.int64, n + 1, "offsets")
         if capacity is None:
             capacity = idx.numel() if idx is not None else max(int(offsets[n].item()), 0)  # the one synchronisation
         capacity = int(capacity)
         if capacity < 0:
             raise ValueError("capacity >= 0")
-        if idx is None:
-            idx = torch.empty(capacity, dtype=torch.int32, device=self.device)
-        if d2 is None and want_d2:
-            d2 = torch.empty(capacity, dtype=torch.float32, device=self.device)
-        if written is None:
-            written = torch.empty((self.nlegs, self.nposes), dtype=torch.int32, device=self.device)
-        _check_out(idx, self.workspace, torch.int32, capacity, "list indices")
-        _check_out(d2, self.workspace, torch.float32, capacity, "list squared distances")
-        _check_out(written, self.workspace, torch.int32, n, "per-leg written counts")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_foothold_lists_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
-                                                                  _dp(self.fh_workspace), self.nposes, self.nlegs, _dp(offsets),
-                                                                  capacity, _dp(idx), _dp(d2) if want_d2 else None, _dp(written),
-                                                                  _stream(self.workspace)))
+        idx = _out(idx, ws, capacity, torch.int32, "list indices")
+        d2 = _out(d2, ws, capacity, torch.float32, "list squared distances", want_d2)
+        written = _out(written, ws, (self.nlegs, self.nposes), torch.int32, "per-leg written counts")
+        _launch("lrm_foothold_lists_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.fh_workspace), self.nposes,
+                self.nlegs, _dp(offsets), capacity, _dp(idx), _dp(d2) if want_d2 else None, _dp(written))
         return offsets, idx, d2 if want_d2 else None, written
 
     def foothold_edges(self, tx, ty, tz, edge_a, edge_b, count=None, best=None, best_d2=None, all_legs=None, check=True):
@@ -813,41 +734,17 @@ class PoseSet:
         kernel (count 0, best -1, +inf, all_legs 0): the form for graph capture.  One launch behind the cloud's bounding
         boxes; best.view(-1) is ik()'s target_idx with foothold_edges_layout() for either end of the edges."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        if self.fh_workspace is None:
-            raise ValueError("PoseSet: built without footholds=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
-        ne = edge_a.numel()
-        _check_out(edge_a, self.workspace, torch.int32, ne, "edge_a")
-        _check_out(edge_b, self.workspace, torch.int32, ne, "edge_b")
-        if edge_b.numel() != ne:
-            raise ValueError("edge_a / edge_b: one pose index each per edge")
-        if check and ne:
-            lo = min(int(edge_a.min()), int(edge_b.min()))
-            hi = max(int(edge_a.max()), int(edge_b.max()))
-            if lo < 0 or hi >= self.nposes:
-                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
-        shape, n = (self.nlegs, ne), self.nlegs * ne
-        if count is None:
-            count = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if best is None:
-            best = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if best_d2 is None:
-            best_d2 = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if all_legs is None:
-            all_legs = torch.empty(ne, dtype=torch.uint8, device=self.device)
-        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
-        _check_out(best, self.workspace, torch.int32, n, "per-leg choices")
-        _check_out(best_d2, self.workspace, torch.float32, n, "per-leg squared distances")
-        _check_out(all_legs, self.workspace, torch.uint8, ne, "per-edge bytes")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_foothold_edges_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
-                                                                  _dp(self.fh_workspace), self.nposes, self.nlegs, _dp(edge_a),
-                                                                  _dp(edge_b), ne, _dp(count), _dp(best), _dp(best_d2), _dp(all_legs),
-                                                                  _stream(self.workspace)))
+        nt = self._cloud(tx, ty, tz)
+        ws = self.workspace
+        ne = _check_edges(ws, edge_a, edge_b)
+        self._check_edge_range(edge_a, edge_b, check)
+        shape = (self.nlegs, ne)
+        count = _out(count, ws, shape, torch.int32, "per-leg counts")
+        best = _out(best, ws, shape, torch.int32, "per-leg choices")
+        best_d2 = _out(best_d2, ws, shape, torch.float32, "per-leg squared distances")
+        all_legs = _out(all_legs, ws, ne, torch.uint8, "per-edge bytes")
+        _launch("lrm_foothold_edges_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.fh_workspace), self.nposes,
+                self.nlegs, _dp(edge_a), _dp(edge_b), ne, _dp(count), _dp(best), _dp(best_d2), _dp(all_legs))
         return count, best, best_d2, all_legs
 
     def foothold_misses(self, tx, ty, tz, margin, count=None, miss=None, m2=None, shift=None, near=None, want_shift=True):
@@ -863,39 +760,22 @@ class PoseSet:
         so update -> footholds -> foothold_misses can be captured in a graph after one warm call on the largest cloud.
         reach_dist on (miss, p, l) returns mask 0 and exactly the shift bits."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        if self.fh_workspace is None:
-            raise ValueError("PoseSet: built without footholds=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
+        nt = self._cloud(tx, ty, tz)
         margin = float(margin)
         if not margin >= 0.0:
             raise ValueError("margin: >= 0 or +inf")
-        shape, n = (self.nlegs, self.nposes), self.nlegs * self.nposes
-        if miss is None:
-            miss = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if m2 is None:
-            m2 = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if shift is None and want_shift:
-            shift = torch.empty((3,) + shape, dtype=torch.float32, device=self.device)
-        if near is None:
-            near = torch.empty(shape, dtype=torch.int32, device=self.device)
-        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
-        _check_out(miss, self.workspace, torch.int32, n, "per-leg misses")
-        _check_out(m2, self.workspace, torch.float32, n, "per-leg squared distances")
-        _check_out(near, self.workspace, torch.int32, n, "per-leg miss counts")
+        ws, shape, n = self.workspace, (self.nlegs, self.nposes), self.nlegs * self.nposes
+        _check_in(count, ws, torch.int32, n, "per-leg counts")
+        miss = _out(miss, ws, shape, torch.int32, "per-leg misses")
+        m2 = _out(m2, ws, shape, torch.float32, "per-leg squared distances")
+        near = _out(near, ws, shape, torch.int32, "per-leg miss counts")
         sx = sy = sz = None
         if want_shift:
-            _check_out(shift, self.workspace, torch.float32, 3 * n, "per-leg shift vectors")
+            shift = _out(shift, ws, (3,) + shape, torch.float32, "per-leg shift vectors")
             sv = shift.view(-1)
             sx, sy, sz = sv[:n], sv[n:2 * n], sv[2 * n:3 * n]
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_foothold_misses_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
-                                                                   _dp(self.fh_workspace), self.nposes, self.nlegs, margin,
-                                                                   _dp(count), _dp(miss), _dp(m2), _dp(sx), _dp(sy), _dp(sz),
-                                                                   _dp(near), _stream(self.workspace)))
+        _launch("lrm_foothold_misses_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.fh_workspace), self.nposes,
+                self.nlegs, margin, _dp(count), _dp(miss), _dp(m2), _dp(sx), _dp(sy), _dp(sz), _dp(near))
         return miss, m2, shift if want_shift else None, near
 
     def foothold_support(self, tx, ty, tz, pose_live=None, count=None, best_pose=None, best_d2=None, legs_mask=None):
@@ -910,37 +790,20 @@ class PoseSet:
         foothold_support(pose_live=all_legs) can be captured in a graph after one call on a cloud of the largest size.
         It does not use the pair kernels' box buffer.  foothold_support_layout() turns best_pose into ik()'s indices."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        if self.fh_workspace is None:
-            raise ValueError("PoseSet: built without footholds=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
-        _check_out(pose_live, self.workspace, torch.uint8, self.nposes, "pose_live")
-        shape, n = (self.nlegs, nt), self.nlegs * nt
-        if count is None:
-            count = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if best_pose is None:
-            best_pose = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if best_d2 is None:
-            best_d2 = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if legs_mask is None:
-            legs_mask = torch.empty(nt, dtype=torch.uint8, device=self.device)
-        _check_out(count, self.workspace, torch.int32, n, "per-leg counts")
-        _check_out(best_pose, self.workspace, torch.int32, n, "per-leg best poses")
-        _check_out(best_d2, self.workspace, torch.float32, n, "per-leg squared distances")
-        _check_out(legs_mask, self.workspace, torch.uint8, nt, "per-target leg masks")
+        nt = self._cloud(tx, ty, tz)
+        ws, shape = self.workspace, (self.nlegs, nt)
+        _check_in(pose_live, ws, torch.uint8, self.nposes, "pose_live")
+        count = _out(count, ws, shape, torch.int32, "per-leg counts")
+        best_pose = _out(best_pose, ws, shape, torch.int32, "per-leg best poses")
+        best_d2 = _out(best_d2, ws, shape, torch.float32, "per-leg squared distances")
+        legs_mask = _out(legs_mask, ws, nt, torch.uint8, "per-target leg masks")
         if nt == 0:
             return count, best_pose, best_d2, legs_mask
         need = _capi.load().lrm_foothold_support_workspace_bytes(self.nposes_max, self.nlegs, nt)
         if self.support_workspace is None or self.support_workspace.numel() < need:
             self.support_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_foothold_support_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
-                                                                    _dp(self.fh_workspace), self.nposes, self.nlegs, _dp(pose_live),
-                                                                    _dp(self.support_workspace), _dp(count), _dp(best_pose),
-                                                                    _dp(best_d2), _dp(legs_mask), _stream(self.workspace)))
+        _launch("lrm_foothold_support_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.fh_workspace), self.nposes,
+                self.nlegs, _dp(pose_live), _dp(self.support_workspace), _dp(count), _dp(best_pose), _dp(best_d2), _dp(legs_mask))
         return count, best_pose, best_d2, legs_mask
 
     def body_clearance(self, tx, ty, tz, radius, plus_z, minus_z, floor_z=None, live_in=None, hits=None, top=None, height=None,
@@ -957,34 +820,17 @@ class PoseSet:
         only launches, so update -> footholds -> body_clearance can be captured in a graph after one warm call on the
         largest cloud."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        if self.fh_workspace is None:
-            raise ValueError("PoseSet: built without footholds=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
+        nt = self._cloud(tx, ty, tz)
         radius, plus_z, minus_z = float(radius), float(plus_z), float(minus_z)
         floor_z = minus_z if floor_z is None else float(floor_z)
-        _check_out(live_in, self.workspace, torch.uint8, self.nposes, "live_in")
-        n = self.nposes
-        if hits is None:
-            hits = torch.empty(n, dtype=torch.int32, device=self.device)
-        if top is None:
-            top = torch.empty(n, dtype=torch.int32, device=self.device)
-        if height is None:
-            height = torch.empty(n, dtype=torch.float32, device=self.device)
-        if free is None:
-            free = torch.empty(n, dtype=torch.uint8, device=self.device)
-        _check_out(hits, self.workspace, torch.int32, n, "per-pose hit counts")
-        _check_out(top, self.workspace, torch.int32, n, "per-pose top targets")
-        _check_out(height, self.workspace, torch.float32, n, "per-pose heights")
-        _check_out(free, self.workspace, torch.uint8, n, "per-pose free bytes")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_body_clearance_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
-                                                                  _dp(self.fh_workspace), self.nposes, self.nlegs, radius, plus_z,
-                                                                  minus_z, floor_z, _dp(live_in), _dp(hits), _dp(top), _dp(height),
-                                                                  _dp(free), _stream(self.workspace)))
+        ws, n = self.workspace, self.nposes
+        _check_in(live_in, ws, torch.uint8, n, "live_in")
+        hits = _out(hits, ws, n, torch.int32, "per-pose hit counts")
+        top = _out(top, ws, n, torch.int32, "per-pose top targets")
+        height = _out(height, ws, n, torch.float32, "per-pose heights")
+        free = _out(free, ws, n, torch.uint8, "per-pose free bytes")
+        _launch("lrm_body_clearance_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.fh_workspace), self.nposes,
+                self.nlegs, radius, plus_z, minus_z, floor_z, _dp(live_in), _dp(hits), _dp(top), _dp(height), _dp(free))
         return hits, top, height, free
 
     def stance_stability(self, tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None, plane=None, lift=None, min_margin=0.0,
@@ -994,12 +840,7 @@ class PoseSet:
         legs, and everything lives on the set's device.  foot = footholds()'s best (a stance per pose), or foothold_edges()'s
         best with pose_idx = edge_a or edge_b.  -> (margin, edge, stable [nmasks, nstances]; feet [nstances]); stable[0] is
         body_clearance()'s live_in.  It only launches: update -> footholds -> stance_stability can be captured in a graph."""
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if quats.dim() != 2 or quats.shape[0] != self.nposes:
-            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
-        if quats.device != self.workspace.device:
-            raise ValueError("quats and poses must live on one device")
+        self._last_update(quats)
         if foot.dim() != 2 or foot.shape[0] != self.nlegs:
             raise ValueError(f"foot: expected an int32 tensor of shape ({self.nlegs}, nstances)")
         return stance_stability(tx, ty, tz, foot, quats, body, pose_idx, com, plane, lift, min_margin, live_in, margin, edge, stable,
@@ -1014,17 +855,8 @@ class PoseSet:
         the form for graph capture.  -> (mask, reached, first_miss, worst, worst_d2 [nlegs, nedges]; planted, clear, advance
         [nedges]); clear is the live_in of ik()'s callers and of stance_stability():
         update -> footholds -> foothold_edges -> edge_transit -> ik / stance_stability(live_in = clear)."""
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if quats.dim() != 2 or quats.shape[0] != self.nposes:
-            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
-        if quats.device != self.workspace.device:
-            raise ValueError("quats and poses must live on one device")
-        if check and edge_a.numel() and edge_a.numel() == edge_b.numel():
-            lo = min(int(edge_a.min()), int(edge_b.min()))
-            hi = max(int(edge_a.max()), int(edge_b.max()))
-            if lo < 0 or hi >= self.nposes:
-                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
+        self._last_update(quats)
+        self._check_edge_range(edge_a, edge_b, check)
         return edge_transit(tx, ty, tz, quats, body, self.legs, edge_a, edge_b, foot, nsamples, live_in, mask, reached, first_miss,
                             worst, worst_d2, planted, clear, advance)
 
@@ -1038,32 +870,19 @@ class PoseSet:
         first_miss, worst, worst_d2, hits, hit_seg, near, pen [nlegs, nedges]; swinging, clear [nedges]); give edge_transit()'s
         clear as live_in, and this clear to what follows:
         update -> footholds -> foothold_edges -> edge_transit -> swing_transit(live_in = clear) -> ik / stance_stability."""
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if quats.dim() != 2 or quats.shape[0] != self.nposes:
-            raise ValueError(f"quats: the ({self.nposes}, 4) tensor of the last update()")
-        if quats.device != self.workspace.device:
-            raise ValueError("quats and poses must live on one device")
-        if check and edge_a.numel() and edge_a.numel() == edge_b.numel():
-            lo = min(int(edge_a.min()), int(edge_b.min()))
-            hi = max(int(edge_a.max()), int(edge_b.max()))
-            if lo < 0 or hi >= self.nposes:
-                raise ValueError(f"edge_a / edge_b outside [0, {self.nposes})")
+        self._last_update(quats)
+        self._check_edge_range(edge_a, edge_b, check)
         return swing_transit(tx, ty, tz, quats, body, self.legs, edge_a, edge_b, foot_from, foot_to, nsamples, lift, up, foot_radius,
                              margin, skip, live_in, mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging,
                              clear)
 
     def _check_angles(self, angles):
         torch = _torch()
-        if self.ik_workspace is None:
-            raise ValueError("PoseSet: built without ik=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
+        self._need("ik")
         n = self.nlegs * self.nposes
         if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
                 and tuple(angles.shape) == (3, n) and angles.is_contiguous()):
             raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {n}) tensor on {self.workspace.device}")
-        return n
 
     def leg_clearance(self, tx, ty, tz, angles, radius, margin=0.0, tip_clear=0.0, live_in=None, hits=None, links=None, worst=None,
                       pen=None, free=None):
@@ -1079,36 +898,19 @@ class PoseSet:
         given outputs must be contiguous.  One launch behind the cloud's bounding boxes; it only launches, so
         update -> footholds -> ik -> leg_clearance can be captured in a graph after one warm call on the largest cloud."""
         torch = _torch()
-        nt = _check_f32(tx, ty, tz)
-        n = self._check_angles(angles)
-        if nt and tx.device != self.workspace.device:
-            raise ValueError("targets and poses must live on one device")
-        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
-        if len(radius) != 3:
-            raise ValueError("radius: three values (coxa, femur, tibia link)")
-        _check_out(live_in, self.workspace, torch.uint8, self.nposes, "live_in")
-        shape = (self.nlegs, self.nposes)
-        if hits is None:
-            hits = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if links is None:
-            links = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        if worst is None:
-            worst = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if pen is None:
-            pen = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if free is None:
-            free = torch.empty(self.nposes, dtype=torch.uint8, device=self.device)
-        _check_out(hits, self.workspace, torch.int32, n, "per-leg hit counts")
-        _check_out(links, self.workspace, torch.uint8, n, "per-leg link masks")
-        _check_out(worst, self.workspace, torch.int32, n, "per-leg worst targets")
-        _check_out(pen, self.workspace, torch.float32, n, "per-leg penetrations")
-        _check_out(free, self.workspace, torch.uint8, self.nposes, "per-pose free bytes")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_leg_clearance_posed_dev(_dp(tx), _dp(ty), _dp(tz), nt, _dp(self.workspace),
-                                                                 _dp(self.ik_workspace), self.nposes, self.nlegs, _dp(angles[0]),
-                                                                 _dp(angles[1]), _dp(angles[2]), _capi._ptr(radius), float(margin),
-                                                                 float(tip_clear), _dp(live_in), _dp(hits), _dp(links), _dp(worst),
-                                                                 _dp(pen), _dp(free), _stream(self.workspace)))
+        nt = self._cloud(tx, ty, tz, "ik")
+        self._check_angles(angles)
+        radius = _radius3(radius)
+        ws, shape = self.workspace, (self.nlegs, self.nposes)
+        _check_in(live_in, ws, torch.uint8, self.nposes, "live_in")
+        hits = _out(hits, ws, shape, torch.int32, "per-leg hit counts")
+        links = _out(links, ws, shape, torch.uint8, "per-leg link masks")
+        worst = _out(worst, ws, shape, torch.int32, "per-leg worst targets")
+        pen = _out(pen, ws, shape, torch.float32, "per-leg penetrations")
+        free = _out(free, ws, self.nposes, torch.uint8, "per-pose free bytes")
+        _launch("lrm_leg_clearance_posed_dev", ws, _dp(tx), _dp(ty), _dp(tz), nt, _dp(ws), _dp(self.ik_workspace), self.nposes,
+                self.nlegs, _dp(angles[0]), _dp(angles[1]), _dp(angles[2]), _capi._ptr(radius), float(margin), float(tip_clear),
+                _dp(live_in), _dp(hits), _dp(links), _dp(worst), _dp(pen), _dp(free))
         return hits, links, worst, pen, free
 
     def self_clearance(self, angles, radius, margin=0.0, tip_clear=0.0, pose_idx=None, live_in=None, hits=None, with_=None, links=None,
@@ -1127,49 +929,17 @@ class PoseSet:
         missing outputs, no shared buffer: update -> footholds -> ik -> self_clearance -> leg_clearance can be captured in a
         graph, and the call may run next to anything."""
         torch = _torch()
-        if self.ik_workspace is None:
-            raise ValueError("PoseSet: built without ik=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
-                and angles.shape[0] == 3 and angles.shape[1] % self.nlegs == 0 and angles.is_contiguous()):
-            raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {self.nlegs} * nsets) tensor on {self.workspace.device}")
-        ns = angles.shape[1] // self.nlegs
-        n = self.nlegs * ns
-        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
-        if len(radius) != 3:
-            raise ValueError("radius: three values (coxa, femur, tibia link)")
-        _check_out(pose_idx, self.workspace, torch.int32, ns, "pose_idx")
-        _check_out(live_in, self.workspace, torch.uint8, ns, "live_in")
-        if pose_idx is not None and pose_idx.numel() != ns or live_in is not None and live_in.numel() != ns:
-            raise ValueError("pose_idx / live_in: one entry per set")
-        if pose_idx is None and ns > self.nposes:
-            raise ValueError("without pose_idx set s takes pose s: nsets <= nposes")
-        shape = (self.nlegs, ns)
-        if hits is None:
-            hits = torch.empty(shape, dtype=torch.int32, device=self.device)
-        if with_ is None:
-            with_ = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        if links is None:
-            links = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        if worst is None:
-            worst = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        if pen is None:
-            pen = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if free is None:
-            free = torch.empty(ns, dtype=torch.uint8, device=self.device)
-        _check_out(hits, self.workspace, torch.int32, n, "per-leg hit counts")
-        _check_out(with_, self.workspace, torch.uint8, n, "per-leg leg masks")
-        _check_out(links, self.workspace, torch.uint8, n, "per-leg link masks")
-        _check_out(worst, self.workspace, torch.uint8, n, "per-leg worst pairs")
-        _check_out(pen, self.workspace, torch.float32, n, "per-leg penetrations")
-        _check_out(free, self.workspace, torch.uint8, ns, "per-set free bytes")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_self_clearance_posed_dev(_dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
-                                                                  _dp(pose_idx), ns, _dp(angles[0]), _dp(angles[1]), _dp(angles[2]),
-                                                                  _capi._ptr(radius), float(margin), float(tip_clear), _dp(live_in),
-                                                                  _dp(hits), _dp(with_), _dp(links), _dp(worst), _dp(pen), _dp(free),
-                                                                  _stream(self.workspace)))
+        ns, radius = self._sets(angles, radius, pose_idx, live_in)
+        ws, shape = self.workspace, (self.nlegs, ns)
+        hits = _out(hits, ws, shape, torch.int32, "per-leg hit counts")
+        with_ = _out(with_, ws, shape, torch.uint8, "per-leg leg masks")
+        links = _out(links, ws, shape, torch.uint8, "per-leg link masks")
+        worst = _out(worst, ws, shape, torch.uint8, "per-leg worst pairs")
+        pen = _out(pen, ws, shape, torch.float32, "per-leg penetrations")
+        free = _out(free, ws, ns, torch.uint8, "per-set free bytes")
+        _launch("lrm_self_clearance_posed_dev", ws, _dp(ws), _dp(self.ik_workspace), self.nposes, self.nlegs, _dp(pose_idx), ns,
+                _dp(angles[0]), _dp(angles[1]), _dp(angles[2]), _capi._ptr(radius), float(margin), float(tip_clear), _dp(live_in),
+                _dp(hits), _dp(with_), _dp(links), _dp(worst), _dp(pen), _dp(free))
         return hits, with_, links, worst, pen, free
 
     def trunk_clearance(self, angles, radius, trunk_radius, plus_z, minus_z, margin=0.0, tip_clear=0.0, links=0b110, pose_idx=None,
@@ -1188,72 +958,37 @@ class PoseSet:
         missing outputs, no shared buffer: update -> footholds -> ik -> trunk_clearance -> self_clearance -> leg_clearance can
         be captured in a graph, and the call may run next to anything."""
         torch = _torch()
-        if self.ik_workspace is None:
-            raise ValueError("PoseSet: built without ik=True")
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
-        if not (angles.is_cuda and angles.device == self.workspace.device and angles.dtype == torch.float32 and angles.dim() == 2
-                and angles.shape[0] == 3 and angles.shape[1] % self.nlegs == 0 and angles.is_contiguous()):
-            raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {self.nlegs} * nsets) tensor on {self.workspace.device}")
-        ns = angles.shape[1] // self.nlegs
-        n = self.nlegs * ns
-        radius = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
-        if len(radius) != 3:
-            raise ValueError("radius: three values (coxa, femur, tibia link)")
+        ns, radius = self._sets(angles, radius, pose_idx, live_in)
         links = _capi._links_mask(links)
-        _check_out(pose_idx, self.workspace, torch.int32, ns, "pose_idx")
-        _check_out(live_in, self.workspace, torch.uint8, ns, "live_in")
-        if pose_idx is not None and pose_idx.numel() != ns or live_in is not None and live_in.numel() != ns:
-            raise ValueError("pose_idx / live_in: one entry per set")
-        if pose_idx is None and ns > self.nposes:
-            raise ValueError("without pose_idx set s takes pose s: nsets <= nposes")
-        shape = (self.nlegs, ns)
-        if hit is None:
-            hit = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        if worst is None:
-            worst = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        if pen is None:
-            pen = torch.empty(shape, dtype=torch.float32, device=self.device)
-        if free is None:
-            free = torch.empty(ns, dtype=torch.uint8, device=self.device)
-        _check_out(hit, self.workspace, torch.uint8, n, "per-leg link masks")
-        _check_out(worst, self.workspace, torch.uint8, n, "per-leg worst links")
-        _check_out(pen, self.workspace, torch.float32, n, "per-leg penetrations")
-        _check_out(free, self.workspace, torch.uint8, ns, "per-set free bytes")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_trunk_clearance_posed_dev(_dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
-                                                                   _dp(pose_idx), ns, _dp(angles[0]), _dp(angles[1]), _dp(angles[2]),
-                                                                   _capi._ptr(radius), float(margin), float(tip_clear),
-                                                                   float(trunk_radius), float(plus_z), float(minus_z), links,
-                                                                   _dp(live_in), _dp(hit), _dp(worst), _dp(pen), _dp(free),
-                                                                   _stream(self.workspace)))
+        ws, shape = self.workspace, (self.nlegs, ns)
+        hit = _out(hit, ws, shape, torch.uint8, "per-leg link masks")
+        worst = _out(worst, ws, shape, torch.uint8, "per-leg worst links")
+        pen = _out(pen, ws, shape, torch.float32, "per-leg penetrations")
+        free = _out(free, ws, ns, torch.uint8, "per-set free bytes")
+        _launch("lrm_trunk_clearance_posed_dev", ws, _dp(ws), _dp(self.ik_workspace), self.nposes, self.nlegs, _dp(pose_idx), ns,
+                _dp(angles[0]), _dp(angles[1]), _dp(angles[2]), _capi._ptr(radius), float(margin), float(tip_clear),
+                float(trunk_radius), float(plus_z), float(minus_z), links, _dp(live_in), _dp(hit), _dp(worst), _dp(pen), _dp(free))
         return hit, worst, pen, free
 
     def leg_joints(self, angles, tip_clear=0.0, out=None):
         """lrm_leg_joints_posed_dev: the four joints of every (leg, pose) under angles (ik()'s (3, nlegs*nposes) tensor under
         footholds_layout): coxa joint, femur joint, knee and the tibia's end tip_clear short of the foot, body position
         added -> float32 (nlegs, nposes, 4, 3).  One launch."""
-        torch = _torch()
-        n = self._check_angles(angles)
-        if out is None:
-            out = torch.empty((self.nlegs, self.nposes, 4, 3), dtype=torch.float32, device=self.device)
-        _check_out(out, self.workspace, torch.float32, 12 * n, "joints")
-        with torch.cuda.device(self.device):
-            _capi.check(_capi.load().lrm_leg_joints_posed_dev(_dp(angles[0]), _dp(angles[1]), _dp(angles[2]), self.nposes, self.nlegs,
-                                                              _dp(self.workspace), _dp(self.ik_workspace), float(tip_clear), _dp(out),
-                                                              _stream(self.workspace)))
+        self._check_angles(angles)
+        ws = self.workspace
+        out = _out(out, ws, (self.nlegs, self.nposes, 4, 3), _torch().float32, "joints")
+        _launch("lrm_leg_joints_posed_dev", ws, _dp(angles[0]), _dp(angles[1]), _dp(angles[2]), self.nposes, self.nlegs, _dp(ws),
+                _dp(self.ik_workspace), float(tip_clear), _dp(out))
         return out
 
     def _check_indices(self, ref, n, pose_idx, leg_idx, check):
         torch = _torch()
-        if self.nposes == 0:
-            raise ValueError("PoseSet: update() before the first query")
+        self._need()
         if ref.device != self.workspace.device:
             raise ValueError("queries and poses must live on one device")
-        _check_out(pose_idx, ref, torch.int32, n, "pose_idx")
-        _check_out(leg_idx, ref, torch.uint8, n, "leg_idx")
-        if pose_idx is not None and pose_idx.numel() != n or leg_idx is not None and leg_idx.numel() != n:
-            raise ValueError("pose_idx / leg_idx: one index per query")
+        _check_in(pose_idx, ref, torch.int32, n, "pose_idx")
+        _check_in(leg_idx, ref, torch.uint8, n, "leg_idx")
+        _one_per(n, "pose_idx / leg_idx: one index per query", pose_idx, leg_idx)
         if check and n:
             if pose_idx is not None:
                 lo, hi = torch.aminmax(pose_idx)
@@ -1274,7 +1009,7 @@ class PoseSet:
             raise ValueError("PoseSet: built without ik=True")
         if target_idx is not None:
             n = target_idx.numel()
-            _check_out(target_idx, x, torch.int32, n, "target_idx")
+            _check_in(target_idx, x, torch.int32, n, "target_idx")
         else:
             n = nt
         self._check_indices(x, n, pose_idx, leg_idx, check)
@@ -1283,35 +1018,24 @@ class PoseSet:
                 raise ValueError("seed: three tensors (coxa, femur, tibia) or None")
             if _check_f32(*seed) != n or seed[0].device != x.device:
                 raise ValueError("seed: one angle per query, on the queries' device")
-        if out is None:
-            out = torch.empty((3, n), dtype=torch.float32, device=x.device)
-        if status is None:
-            status = torch.empty(n, dtype=torch.uint8, device=x.device)
-        _check_field(out, x, n)
-        _check_out(status, x, torch.uint8, n, "status")
+        out = _out_field(out, x, n)
+        status = _out(status, x, n, torch.uint8, "status")
         sc, sf, st = (None, None, None) if seed is None else seed
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.load().lrm_ik_posed_dev(_dp(x), _dp(y), _dp(z), nt, _dp(target_idx), n, _dp(pose_idx), _dp(leg_idx),
-                                                      _dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
-                                                      _dp(sc), _dp(sf), _dp(st), _dp(out[0]), _dp(out[1]), _dp(out[2]),
-                                                      _dp(status), _stream(x)))
+        _launch("lrm_ik_posed_dev", x, _dp(x), _dp(y), _dp(z), nt, _dp(target_idx), n, _dp(pose_idx), _dp(leg_idx), _dp(self.workspace),
+                _dp(self.ik_workspace), self.nposes, self.nlegs, _dp(sc), _dp(sf), _dp(st), _dp(out[0]), _dp(out[1]), _dp(out[2]),
+                _dp(status))
         return out, status
 
     def fk(self, coxa, femur, tibia, pose_idx=None, leg_idx=None, out=None, check=True):
         """lrm_fk_posed_dev: the tip of angles i for leg leg_idx[i] under pose pose_idx[i], plus that pose's body
         position -> float32 (3, n).  One launch."""
-        torch = _torch()
         n = _check_f32(coxa, femur, tibia)
         if self.ik_workspace is None:
             raise ValueError("PoseSet: built without ik=True")
         self._check_indices(coxa, n, pose_idx, leg_idx, check)
-        if out is None:
-            out = torch.empty((3, n), dtype=torch.float32, device=coxa.device)
-        _check_field(out, coxa, n)
-        with torch.cuda.device(coxa.device):
-            _capi.check(_capi.load().lrm_fk_posed_dev(_dp(coxa), _dp(femur), _dp(tibia), n, _dp(pose_idx), _dp(leg_idx),
-                                                      _dp(self.workspace), _dp(self.ik_workspace), self.nposes, self.nlegs,
-                                                      _dp(out[0]), _dp(out[1]), _dp(out[2]), _stream(coxa)))
+        out = _out_field(out, coxa, n)
+        _launch("lrm_fk_posed_dev", coxa, _dp(coxa), _dp(femur), _dp(tibia), n, _dp(pose_idx), _dp(leg_idx), _dp(self.workspace),
+                _dp(self.ik_workspace), self.nposes, self.nlegs, _dp(out[0]), _dp(out[1]), _dp(out[2]))
         return out
 
     def reach_dist(self, x, y, z, pose_idx=None, leg_idx=None, mask=None, out=None, valid=None, want_dist=True, check=True):
@@ -1322,21 +1046,13 @@ class PoseSet:
         torch = _torch()
         n = _check_f32(x, y, z)
         self._check_indices(x, n, pose_idx, leg_idx, check)
-        if mask is None:
-            mask = torch.empty(n, dtype=torch.uint8, device=x.device)
-        _check_out(mask, x, torch.uint8, n, "mask")
+        mask = _out(mask, x, n, torch.uint8, "mask")
         if want_dist:
-            if out is None:
-                out = torch.empty((3, n), dtype=torch.float32, device=x.device)
-            if valid is None:
-                valid = torch.empty(n, dtype=torch.uint8, device=x.device)
-            _check_field(out, x, n)
-            _check_out(valid, x, torch.uint8, n, "validity bytes")
+            out = _out_field(out, x, n)
+            valid = _out(valid, x, n, torch.uint8, "validity bytes")
         else:
             out = valid = None
         f = (None, None, None) if out is None else (_dp(out[0]), _dp(out[1]), _dp(out[2]))
-        with torch.cuda.device(x.device):
-            _capi.check(_capi.load().lrm_reach_dist_posed_dev(_dp(x), _dp(y), _dp(z), n, _dp(pose_idx), _dp(leg_idx),
-                                                              _dp(self.workspace), self.nposes, self.nlegs, _dp(mask),
-                                                              _dp(valid), *f, _stream(x)))
+        _launch("lrm_reach_dist_posed_dev", x, _dp(x), _dp(y), _dp(z), n, _dp(pose_idx), _dp(leg_idx), _dp(self.workspace), self.nposes,
+                self.nlegs, _dp(mask), _dp(valid), *f)
         return mask, out, valid
