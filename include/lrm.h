@@ -1174,6 +1174,12 @@ const char* lrm_octree_last_error(void);
  * the count); lrm_dbg_oct_trace(0) stops and clears. */
 int lrm_dbg_oct_trace(int enable);
 int lrm_dbg_oct_trace_read(float* out, size_t capacity_records, size_t* n_out);
+/* What an octree call launches for a level of nc children on nf footholds under the LRM_OCT_* switches of the environment,
+ * from the function the launch itself consumes (host only, no device needed): out = {kernel (0 every foothold, 1 chunked),
+ * grid.x, grid.y, tiles per round, workgroups per child ("splits"; both 0 for kernel 0), 1 if the level goes through the
+ * deferred queue (as when the plane tables and the queue exist), tiles of the cloud, threads per workgroup}.  nc = 0 is
+ * LRM_EINVAL.  tests/test_octree_cases_cpu.py holds it against the restatement the boundary suite is built on. */
+int lrm_dbg_oct_plan(size_t nc, size_t nf, uint64_t out[8]);
 
 /* ---- several GPUs behind the apply_kernel boundary (one process, one host thread) ------------------------------
  * New capability: the reference runs on device 0 only (several_leg.cu:800; apply_kernel cross_compiled.cu:33-79).

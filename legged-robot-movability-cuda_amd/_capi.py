@@ -1090,6 +1090,15 @@ def dbg_oct_trace_read():
     return out
 
 
+def dbg_oct_plan(nc, nf):
+    """lrm_dbg_oct_plan: what an octree call launches for a level of nc children on nf footholds under the LRM_OCT_* switches
+    of the environment (deferred: as when the plane tables and the queue exist).  Host only."""
+    out = np.zeros(8, np.uint64)
+    check(load().lrm_dbg_oct_plan(int(nc), int(nf), _ptr(out)))
+    names = ("kernel", "grid_x", "grid_y", "tpr", "splits", "deferred", "ntiles", "block")
+    return {**dict(zip(names, (int(v) for v in out))), "kernel": "chunked" if out[0] else "every", "deferred": bool(out[5])}
+
+
 def dbg_pair_counts():
     """counting build only: (full evaluations, leg-sphere tests, footholds inside a reach sphere, footholds loaded) since the last call"""
     out = np.zeros(4, np.uint64)

@@ -43,7 +43,7 @@
 
 namespace {
 
-constexpr int kOctBlock = 256;
+constexpr int kOctBlock = 256, kOctChunk = 64, kOctTile = 1024; // threads per workgroup; footholds per chunk box (a wave's worth) and per tile box (16 chunks)
 #ifndef LRM_OCT_MIN_WAVES
 #define LRM_OCT_MIN_WAVES 4 // 128 VGPRs (8 B/lane of scratch in the table form) instead of 153 at 3 waves: config-5 share 114 -> 100 ms; 5 waves (112 B of scratch): 116
 #endif
@@ -175,8 +175,8 @@ struct OctDeferQueue {
 };
 // records of the global queue: 2-3 % of a level's evaluated (item, orientation) pairs are deferred -- 6.9e6 at the deepest level of the
 // config-5 share (1.25e7 footholds): one record per foothold, within [2^20, 2^25] (12 bytes each)
-static size_t oct_defer_cap(size_t nf) {
-    if (const char* e = getenv("LRM_OCT_DEFER_CAP")) return std::max<size_t>((size_t)atol(e), 64); // tests: a queue that overflows
+static size_t oct_defer_cap(size_t nf, bool knob_set, size_t knob) {
+    if (knob_set) return knob; // LRM_OCT_DEFER_CAP (tests: a queue that overflows), read by oct_read_knobs
     return std::min<size_t>(std::max<size_t>(nf, (size_t)1 << 20), (size_t)1 << 25);
 }
 constexpr int kOctDeferSeg = 64; // records per wave segment: one ballot's worth always fits an emptied segment
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(kOctBlock) void oct_boxes_kernel(const float* __res
                                                              const float* __restrict__ fz, size_t nf, size_t ntiles,
                                                              float* __restrict__ boxes) {
     __shared__ float s_red[6][16];
-    const size_t t0 = (size_t)blockIdx.x * 1024;
+    const size_t t0 = (size_t)blockIdx.x * kOctTile;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int sub = wave; sub < 16; sub += kOctBlock / 64) {
         const size_t i = t0 + (size_t)sub * 64 + lane;
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(kOctBlock, kDefer ? LRM_OCT_DEFER_MIN_WAVES : LRM_O
             const uint32_t nchunks = s_nchunks;
             for (uint32_t k = threadIdx.x >> 6; k < nchunks; k += kOctBlock / 64) { // a wave per surviving chunk
                 if (*reinterpret_cast<volatile uint32_t*>(&s_flags) == 7u) break;
-                const size_t f = (size_t)s_chunks[k] * 64 + (threadIdx.x & 63);
+                const size_t f = (size_t)s_chunks[k] * kOctChunk + (threadIdx.x & 63);
                 uint32_t mine = 0;
                 if (kDefer) { // every lane of the wave together (ballots inside)
                     const bool live = f < nf;
@@ -631,8 +631,549 @@ struct OctTabEntry {
     LrmTolLeg tl;
     std::map<int, uint8_t*> tab_dev; // per device: the plane table (lrm_build_tol_tab_dev), nullptr = this leg has none
 };
+using OctPairKey = std::array<float, 18>; // the leg with its mount angle, and the orientation's quaternion
 std::mutex g_oct_tab_mu;
-std::map<std::array<float, 18>, OctTabEntry> g_oct_tab_cache;
+std::map<OctPairKey, OctTabEntry> g_oct_tab_cache;
+
+// ---- the switches: read once per call -----------------------------------------------------------------------------------
+struct OctKnobs {
+    struct Num {          // a numeric switch: whether it was set, and its value
+        bool set = false;
+        size_t v = 0;
+    };
+    int tol = -1;         // LRM_OCT_TOL: -1 unset (the tolerance blocks from 3e5 footholds on), 0 without them, 1 with (A/B runs and tests)
+    bool tab = true;      // LRM_OCT_TAB=0: without the plane tables
+    bool defer = true;    // LRM_OCT_DEFER=0: the doubts of the table form inline (A/B runs and tests)
+    bool no_cull = false; // LRM_OCT_NOCULL=1 (tests): every work item evaluated
+    bool brute = false;   // LRM_OCT_BRUTE=1 (tests): every level with the every-foothold kernel, for comparison
+    bool debug = false;   // LRM_OCT_DEBUG: host-side phase times on stderr
+    Num chunked_from;     // LRM_OCT_CHUNKED_FROM (experiments): in place of kOctChunkedFrom, and no first-level rule
+    Num tpr, wgs;         // LRM_OCT_TPR (within [1, kOctBlock]), LRM_OCT_WGS: in place of the tiers of oct_level_plan
+    Num defer_from;       // LRM_OCT_DEFER_FROM: in place of 256 children
+    Num defer_cap;        // LRM_OCT_DEFER_CAP (tests: a queue that overflows), 64 records at least
+};
+OctKnobs oct_read_knobs() {
+    auto env = [](const char* name) { return getenv(name); };
+    auto num = [&](const char* name) {
+        const char* e = env(name);
+        return OctKnobs::Num{e != nullptr, e ? (size_t)atol(e) : 0};
+    };
+    OctKnobs k;
+    if (const char* e = env("LRM_OCT_TOL")) k.tol = e[0] != '0';
+    if (const char* e = env("LRM_OCT_TAB")) k.tab = e[0] != '0';
+    if (const char* e = env("LRM_OCT_DEFER")) k.defer = e[0] != '0';
+    if (const char* e = env("LRM_OCT_NOCULL")) k.no_cull = e[0] == '1';
+    if (const char* e = env("LRM_OCT_BRUTE")) k.brute = e[0] == '1';
+    k.debug = env("LRM_OCT_DEBUG") != nullptr;
+    k.chunked_from = num("LRM_OCT_CHUNKED_FROM");
+    k.tpr = num("LRM_OCT_TPR");
+    k.tpr.v = std::min<size_t>(std::max<size_t>(k.tpr.v, 1), kOctBlock);
+    k.wgs = num("LRM_OCT_WGS");
+    k.defer_from = num("LRM_OCT_DEFER_FROM");
+    k.defer_cap = num("LRM_OCT_DEFER_CAP");
+    k.defer_cap.v = std::max<size_t>(k.defer_cap.v, 64);
+    return k;
+}
+
+// ---- the launch plan of a level -----------------------------------------------------------------------------------------
+// What evaluates a level of nc children on nf footholds: a function of the two sizes and the switches alone.  oct_launch_level
+// launches what it says, and lrm_dbg_oct_plan shows it to the tests (tests/test_octree_cases_cpu.py).
+struct OctPlan {
+    bool chunked;         // oct_validity_chunked_kernel, else oct_validity_kernel
+    bool deferred;        // chunked: the table form with its doubts queued for a second launch (oct_item_flags_defer)
+    unsigned gx, gy;      // the grid
+    uint32_t tpr, splits; // chunked: tiles per round, workgroups per child
+    size_t ntiles;
+};
+OctPlan oct_level_plan(size_t nc, size_t nf, bool deferred_available, const OctKnobs& K) {
+    OctPlan P{};
+    P.ntiles = (nf + kOctTile - 1) / kOctTile;
+    const bool brute = K.brute && nc <= 65535; // (the children are grid.y there)
+    const size_t chunked_from = K.chunked_from.set ? K.chunked_from.v : (size_t)kOctChunkedFrom;
+    // (the first level's 8 huge children too when the cloud has enough tiles to spread them over the chip: 6.4 -> 4.0 ms at 1.25e7 footholds)
+    P.chunked = (nc >= chunked_from || (!K.chunked_from.set && nc * ((P.ntiles + 31) / 32) >= 2048)) && !brute;
+    if (!P.chunked) { // few, huge children (the first levels): every foothold, spread over the chip; grid.y = children < 65
+        P.gx = (unsigned)std::min<size_t>((nf + kOctBlock - 1) / kOctBlock, 1024);
+        P.gy = (unsigned)nc;
+        return P;
+    }
+    // many small children: one workgroup per child, only the footholds of nearby chunks
+    // workgroups per child: at least ~4096 workgroups in flight, at most one per round of 256 tiles
+    // (levels of few, huge children: rounds of fewer tiles, so that more workgroups share a child and look at its flags more often)
+    // config-5 share, levels of 64 / 256 / 976 / 4112 children: 11.6 / 9.2 / 9.9 / 14.3 ms with rounds of 256 tiles and 4096
+    // workgroups -> 5.3 / 6.1 / 8.4 / 13.4 ms (profiles/r04_octree.txt); the deepest level (15 856 children) is best left alone
+    const size_t tpr = K.tpr.set ? K.tpr.v : (nc < 2048 ? 32 : (nc < 8192 ? 128 : kOctBlock));
+    const size_t want_wgs = K.wgs.set ? K.wgs.v : (nc < 2048 ? 32768 : (nc < 8192 ? 8192 : 4096));
+    size_t splits = nc >= want_wgs ? 1 : (want_wgs + nc - 1) / nc;
+    splits = std::min(splits, std::max<size_t>(1, (P.ntiles + tpr - 1) / tpr));
+    splits = std::min<size_t>(splits, 256);
+    P.gx = (unsigned)std::min<size_t>(nc * splits, (size_t)256 * 64);
+    P.gy = 1;
+    P.tpr = (uint32_t)tpr;
+    P.splits = (uint32_t)splits;
+    // the deferred form from 256 children on: the few huge children of the first levels saturate their flags early, and later when
+    // some of their items wait in the queue
+    P.deferred = deferred_available && nc >= (K.defer_from.set ? K.defer_from.v : (size_t)256);
+    return P;
+}
+
+// ---- what a call holds on the device ------------------------------------------------------------------------------------
+template <class T>
+struct OctBuf { // a device allocation: freed with its scope, or earlier by reset()
+    T* p = nullptr;
+    OctBuf() = default;
+    OctBuf(const OctBuf&) = delete;
+    OctBuf& operator=(const OctBuf&) = delete;
+    ~OctBuf() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; }
+    hipError_t alloc(size_t count) { reset(); return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)); }
+};
+struct OctEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    OctEvents() = default;
+    OctEvents(const OctEvents&) = delete;
+    OctEvents& operator=(const OctEvents&) = delete;
+    ~OctEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+int oct_fail(int code, const char* what) { g_oct_err = what; return code; }
+int oct_hip_error(hipError_t e, const char* where) {
+    g_oct_err = std::string(where) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? LRM_ENOMEM : LRM_ENODEV;
+}
+#define OCT_TRY(expr, where)                                   \
+    do {                                                       \
+        const hipError_t e_ = (expr);                          \
+        if (e_ != hipSuccess) return oct_hip_error(e_, where); \
+    } while (0)
+
+struct OctClock { // LRM_OCT_DEBUG: the host time since the line before
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    double lap() {
+        const auto t0 = t;
+        t = std::chrono::steady_clock::now();
+        return std::chrono::duration<double, std::milli>(t - t0).count();
+    }
+};
+constexpr uint32_t kOctPoison = 0xffffffffu;
+
+// One call of apply_oct_impl: what its phases share.  A phase that fails says why in g_oct_err and returns the code; apply_oct_impl then
+// poisons the peers (abort_peers), and the buffers go with the call.
+struct OctCall {
+    const OctKnobs& knobs;
+    OctClock& clock;
+    const LrmLegDimensions* dim;
+    LrmOctreeSettings st;
+    size_t nf;
+    int rank, world;
+    LrmOctExchange exchange;
+    void* user;
+    size_t peers_expect; // words the peers' next exchange carries (0: none pending)
+    OctBuf<float> f, boxes;                // the footholds as SoA in Morton order (x, y, z: nf each), the boxes of their tiles and chunks
+    size_t ntiles = 0;
+    int n_angles_max = 0;                  // per (orientation, leg), [n_angles_max][leg_count]:
+    std::vector<LrmCompiledLeg> legs_host;
+    bool fast = false;
+    OctBuf<LrmCompiledLeg> legs;
+    OctBuf<float4> spheres;
+    OctBuf<LrmTolLeg> tols;
+    OctBuf<const uint8_t*> tabs;           // the plane tables' device pointers (the tables themselves live in g_oct_tab_cache)
+    OctBuf<uint32_t> defer, defer_count;   // the queue of deferred (item, orientation) pairs (oct_item_flags_defer)
+    size_t defer_cap = 0;
+    OctBuf<OctChild> children;             // the level in flight
+    OctBuf<uint32_t> flags;
+    size_t children_cap = 0;
+    OctEvents ev;
+    float reach_len = 0.f, total_ms = 0.f;
+    std::vector<Node> nodes;
+    unsigned long long deferred_total = 0;
+
+    size_t pair(int a, int l) const { return (size_t)a * st.leg_count + l; }
+    int tol_form() const { return tabs.p ? 2 : (tols.p ? 1 : 0); } // kTol of the kernels
+    void abort_peers() { // after a local failure: do not leave the peers waiting
+        if (!exchange || peers_expect == 0) return;
+        std::vector<uint32_t> poison(peers_expect, kOctPoison);
+        peers_expect = 0;
+        (void)exchange(poison.data(), poison.size(), user);
+    }
+};
+
+// ---- footholds: SoA in Morton order, and their boxes ----------------------------------------------------------------------
+// the boxes of a cloud in memory order (oct_boxes_kernel): one per tile, then one per chunk
+int oct_tile_boxes(const float* x, const float* y, const float* z, size_t nf, size_t ntiles, OctBuf<float>& boxes) {
+    OCT_TRY(boxes.alloc(ntiles * (1 + kOctTile / kOctChunk) * 6), "hipMalloc foothold boxes");
+    hipLaunchKernelGGL(oct_boxes_kernel, dim3((unsigned)ntiles), dim3(kOctBlock), 0, nullptr, x, y, z, nf, ntiles, boxes.p);
+    OCT_TRY(hipGetLastError(), "Kernel launch");
+    return LRM_OK;
+}
+// c.f: the footholds as SoA on the device, in Morton order (the flags are ORs over footholds: the order changes nothing, but consecutive
+// footholds then fill compact boxes for oct_validity_chunked_kernel).  What else it allocates is released when it returns.
+int oct_order_footholds(OctCall& c, const float* footholds /* host AoS, or null */, const float* ux, const float* uy, const float* uz) {
+    const size_t nf = c.nf;
+    OCT_TRY(c.f.alloc(3 * (nf ? nf : 1)), "hipMalloc gpu_in.elements");
+    if (!nf) return LRM_OK;
+    OctBuf<float> tmp_aos, tmp_soa, first_boxes;
+    OctBuf<uint32_t> keys;
+    OctBuf<char> sort_tmp;
+    const dim3 grid((unsigned)((nf + kOctBlock - 1) / kOctBlock)), block(kOctBlock);
+    if (footholds) { // host AoS (the reference's Array<float3>): upload, split
+        OCT_TRY(tmp_aos.alloc(3 * nf), "hipMalloc footholds");
+        OCT_TRY(tmp_soa.alloc(3 * nf), "hipMalloc footholds");
+        OCT_TRY(hipMemcpy(tmp_aos.p, footholds, 3 * nf * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy gpu_in.elements");
+        hipLaunchKernelGGL(oct_aos_to_soa_kernel, grid, block, 0, nullptr, tmp_aos.p, nf, tmp_soa.p, tmp_soa.p + nf, tmp_soa.p + 2 * nf);
+        OCT_TRY(hipGetLastError(), "Kernel launch");
+        ux = tmp_soa.p;
+        uy = tmp_soa.p + nf;
+        uz = tmp_soa.p + 2 * nf;
+    }
+    // bounding box of the cloud: the tile boxes of the unsorted cloud, reduced on the host
+    if (int rc = oct_tile_boxes(ux, uy, uz, nf, c.ntiles, first_boxes)) return rc;
+    std::vector<float> tb(c.ntiles * 6);
+    OCT_TRY(hipMemcpy(tb.data(), first_boxes.p, tb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy boxes");
+    OctBounds ob;
+    for (int a = 0; a < 3; a++) {
+        float lo = 3.0e38f, hi = -3.0e38f;
+        for (size_t t = 0; t < c.ntiles; t++) {
+            lo = std::min(lo, tb[t * 6 + a]);
+            hi = std::max(hi, tb[t * 6 + 3 + a]);
+        }
+        ob.lo[a] = lo;
+        ob.inv[a] = (hi > lo && std::isfinite(hi - lo)) ? 1.0f / (hi - lo) : 0.f;
+    }
+    OCT_TRY(keys.alloc(4 * nf), "hipMalloc sort keys"); // keys, indices, and their sorted copies
+    uint32_t *k_in = keys.p, *i_in = k_in + nf, *k_out = k_in + 2 * nf, *i_out = k_in + 3 * nf;
+    hipLaunchKernelGGL(oct_keys_kernel, grid, block, 0, nullptr, ux, uy, uz, nf, ob, k_in, i_in);
+    OCT_TRY(hipGetLastError(), "Kernel launch");
+    size_t sort_bytes = 0;
+    OCT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k_in, k_out, i_in, i_out, (int)nf, 0, 30, (hipStream_t) nullptr), "radix sort (size)");
+    OCT_TRY(sort_tmp.alloc(sort_bytes ? sort_bytes : 16), "hipMalloc sort workspace");
+    OCT_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp.p, sort_bytes, k_in, k_out, i_in, i_out, (int)nf, 0, 30, (hipStream_t) nullptr), "radix sort");
+    hipLaunchKernelGGL(oct_gather_kernel, grid, block, 0, nullptr, ux, uy, uz, i_out, nf, c.f.p, c.f.p + nf, c.f.p + 2 * nf);
+    OCT_TRY(hipGetLastError(), "Kernel launch");
+    OCT_TRY(hipDeviceSynchronize(), "footholds in Morton order");
+    return LRM_OK;
+}
+
+// ---- the legs of every (orientation sample, mounted leg) ----------------------------------------------------------------
+// c.legs_host and c.fast; where the tolerance evaluation is wanted, c.tols, c.tabs and the deferred queue as well, from the cache or into it.
+// g_oct_tab_mu is held from the first look-up until what the pairs of the call got is on the device.
+int oct_compile_legs(OctCall& c) {
+    const LrmOctreeSettings& st = c.st;
+    c.n_angles_max = st.angle_sample[0] * st.angle_sample[1] * st.angle_sample[2];
+    c.legs_host.resize((size_t)c.n_angles_max * st.leg_count);
+    std::vector<OctPairKey> keys(c.legs_host.size()); // of each pair in the table cache
+    bool all_fast = true;
+    for (int a = 0; a < c.n_angles_max; a++) {
+        const Quat q = quat_from_angle_index((unsigned)a, st);
+        const float qa[4] = {q.x, q.y, q.z, q.w};
+        for (int l = 0; l < st.leg_count; l++) {
+            LrmLegDimensions leg = *c.dim;
+            leg.body_angle = st.leg_mount[l]; // several_leg_octree.cu:94
+            lrm_compile_leg(leg, qa, 1, &c.legs_host[c.pair(a, l)]);
+            all_fast = all_fast && c.legs_host[c.pair(a, l)].fast_ok;
+            std::memcpy(keys[c.pair(a, l)].data(), &leg, 14 * sizeof(float));
+            std::memcpy(keys[c.pair(a, l)].data() + 14, qa, sizeof qa);
+        }
+    }
+    c.fast = all_fast && lrm_get_mode() != LRM_MODE_STRICT;
+    // the tolerance blocks (filtered mode; LRM_OCT_TOL=0: without -- A/B runs and tests): lrm_compile_tol costs ~0.3 ms of host
+    // geometry per (orientation, leg), so they are worth it from a few hundred thousand footholds on and are kept across calls
+    const OctKnobs& K = c.knobs;
+    if (!(c.fast && (K.tol >= 0 ? K.tol != 0 : c.nf >= 300000))) return LRM_OK;
+    std::vector<LrmTolLeg> tols(keys.size());
+    std::vector<const uint8_t*> tabs(keys.size(), nullptr);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    bool any_tab = false;
+    std::lock_guard<std::mutex> g(g_oct_tab_mu);
+    auto& cache = g_oct_tab_cache;
+    for (size_t k = 0; k < keys.size(); k++) {
+        auto it = cache.find(keys[k]);
+        if (it == cache.end()) {
+            // A full cache takes no new entry (and frees nothing: another thread's call may be running on its tables): this
+            // pair goes without a table -- its items through the filtered code (4096 pairs: a thousand robots' worth).
+            if (cache.size() >= 4096) {
+                lrm_compile_tol(c.legs_host[k], &tols[k]);
+                continue;
+            }
+            OctTabEntry en;
+            lrm_compile_tol(c.legs_host[k], &en.tl);
+            it = cache.emplace(keys[k], en).first;
+        }
+        tols[k] = it->second.tl;
+        if (!(K.tab && it->second.tl.tol_ok)) continue;
+        // the plane tables (LRM_OCT_TAB=0: without): built on the device on first use, ~0.4 ms each, kept across calls
+        auto dt = it->second.tab_dev.find(dev);
+        if (dt == it->second.tab_dev.end()) {
+            uint8_t* t = nullptr;
+            size_t bytes = 0;
+            float ms = 0.f;
+            const int rc = lrm_build_tol_tab_dev(it->second.tl, nullptr, &t, &bytes, &ms);
+            if (rc < 0) OCT_TRY((hipError_t)(-rc), "plane table (device builder)");
+            // rc 1 or 2 (no table, the builder declines the leg, or no device memory for its scratch): this pair
+            // goes without a table -- same results, slower -- until lrm_release_workspaces empties the cache
+            dt = it->second.tab_dev.emplace(dev, rc == 0 ? t : nullptr).first;
+        }
+        tabs[k] = dt->second;
+        any_tab = any_tab || dt->second != nullptr;
+    }
+    OCT_TRY(c.tols.alloc(tols.size()), "hipMalloc tolerance blocks");
+    OCT_TRY(hipMemcpy(c.tols.p, tols.data(), tols.size() * sizeof(LrmTolLeg), hipMemcpyHostToDevice), "hipMemcpy tolerance blocks");
+    if (!any_tab) return LRM_OK;
+    OCT_TRY(c.tabs.alloc(tabs.size()), "hipMalloc table pointers");
+    OCT_TRY(hipMemcpy(c.tabs.p, tabs.data(), tabs.size() * sizeof(uint8_t*), hipMemcpyHostToDevice), "hipMemcpy table pointers");
+    if (K.defer) {
+        OCT_TRY(c.defer.alloc(c.defer_cap * 3), "hipMalloc deferred pairs");
+        OCT_TRY(c.defer_count.alloc(8), "hipMalloc deferred count");
+    }
+    return LRM_OK;
+}
+// c.legs and c.spheres: the compiled legs, and the bounding sphere of what each (orientation, leg) reaches, in the frame distance_global takes
+// its point in: pair_center lives in the frame of reachable_rotate_leg (the target relative to the body, before the quaternion);
+// distance_global first applies qtRotate(qtInvert(q), .), so the centre goes through qtRotate(q, .)
+int oct_upload_legs(OctCall& c) {
+    const std::vector<LrmCompiledLeg>& legs = c.legs_host;
+    OCT_TRY(c.legs.alloc(legs.size()), "hipMalloc legs");
+    OCT_TRY(hipMemcpy(c.legs.p, legs.data(), legs.size() * sizeof(LrmCompiledLeg), hipMemcpyHostToDevice), "hipMemcpy legs");
+    std::vector<float4> spheres(legs.size());
+    for (size_t k = 0; k < legs.size(); k++) {
+        const LrmCompiledLeg& L = legs[k];
+        const LrmVec3 ctr = lrm_qrot(L.fwd_rot, LrmVec3{L.pair_center[0], L.pair_center[1], L.pair_center[2]});
+        spheres[k] = make_float4(ctr.x, ctr.y, ctr.z, c.knobs.no_cull ? 1.0e18f : std::sqrt(L.pair_r2) * 1.0001f + 0.5f);
+    }
+    OCT_TRY(c.spheres.alloc(spheres.size()), "hipMalloc spheres");
+    OCT_TRY(hipMemcpy(c.spheres.p, spheres.data(), spheres.size() * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy spheres");
+    OCT_TRY(hipEventCreate(&c.ev.a), "hipEventCreate");
+    OCT_TRY(hipEventCreate(&c.ev.b), "hipEventCreate");
+    return LRM_OK;
+}
+
+// ---- a level ------------------------------------------------------------------------------------------------------------
+// host only: the eight children of every node in `expand`, as nodes and as the records the kernels read
+void oct_make_children(OctCall& c, const std::vector<int>& expand, std::vector<OctChild>& level, std::vector<int>& level_nodes) {
+    const LrmOctreeSettings& st = c.st;
+    std::vector<Node>& nodes = c.nodes;
+    for (int pi : expand) {
+        const int first = (int)nodes.size();
+        nodes.resize(nodes.size() + 8);
+        Node& parent = nodes[pi];
+        parent.first_child = first;
+        const bool rot = parent.h[0] < st.enable_rot_below; // several_leg_octree.cu:52
+        for (unsigned ci = 0; ci < 8; ci++) {
+            Node& n = nodes[first + ci];
+            int missing = 0;
+            if (!create_child_box(parent, ci, st.min_box, &n, &missing)) { // several_leg_octree.cu:331-339
+                n.dead = n.leaf = n.validity = n.on_edge = true;
+                n.raw = false;
+                std::memset(n.c, 0, sizeof n.c);
+                std::memset(n.h, 0, sizeof n.h);
+            } else if (3 - missing <= 0) { // :342-347
+                n.leaf = true;
+                n.raw = false;
+            } else {                       // :348-353
+                n.leaf = false;
+                n.raw = true;
+            }
+            OctChild oc;
+            std::memcpy(oc.c, n.c, sizeof oc.c);
+            std::memcpy(oc.h, n.h, sizeof oc.h);
+            std::memcpy(oc.ph, parent.h, sizeof oc.ph);
+            oc.margin = rot ? 0.f : st.enable_rot_below / 3;
+            oc.n_angles = rot ? c.n_angles_max : 1;
+            oc.parent_valid = parent.validity;
+            oc.skip = n.validity; // dead quadrants are "valid" and skipped (:58-61)
+            oc.pad = 0;
+            level.push_back(oc);
+            level_nodes.push_back(first + ci);
+        }
+        nodes[pi].raw = false;
+    }
+}
+
+// the arithmetic form of the two level kernels: (kFast, kTol) of oct_item_flags, and the deferred form of the chunked one
+using OctChunkedKernel = decltype(&oct_validity_chunked_kernel<true, 2, true>);
+using OctEveryKernel = decltype(&oct_validity_kernel<true, 2>);
+OctChunkedKernel oct_chunked_kernel(bool fast, int tol, bool deferred) {
+    if (deferred) return oct_validity_chunked_kernel<true, 2, true>;
+    if (fast && tol == 2) return oct_validity_chunked_kernel<true, 2, false>;
+    if (fast && tol == 1) return oct_validity_chunked_kernel<true, 1, false>;
+    if (fast) return oct_validity_chunked_kernel<true, 0, false>;
+    return oct_validity_chunked_kernel<false, 0, false>;
+}
+OctEveryKernel oct_every_kernel(bool fast, int tol) {
+    if (fast && tol == 2) return oct_validity_kernel<true, 2>;
+    if (fast && tol == 1) return oct_validity_kernel<true, 1>;
+    if (fast) return oct_validity_kernel<true, 0>;
+    return oct_validity_kernel<false, 0>;
+}
+
+// the kernels of one level, as its plan says, on the children and the zeroed flags already on the device
+int oct_launch_level(OctCall& c, const OctPlan& P, size_t nc, int depth) {
+    const dim3 grid(P.gx, P.gy), block(kOctBlock);
+    const float *fx = c.f.p, *fy = fx + c.nf, *fz = fx + 2 * c.nf;
+    const int leg_count = c.st.leg_count, stab = c.st.leg_number_for_stab;
+    const float cr2 = c.st.convex_radius * c.st.convex_radius;
+    if (!P.chunked) {
+        hipLaunchKernelGGL(oct_every_kernel(c.fast, c.tol_form()), grid, block, 0, nullptr, c.children.p, (int)nc, fx, fy, fz, c.nf, c.legs.p, c.tols.p,
+                           c.tabs.p, c.spheres.p, leg_count, stab, c.reach_len, cr2, c.flags.p);
+        OCT_TRY(hipGetLastError(), "Kernel launch");
+        return LRM_OK;
+    }
+    auto chunked = [&](bool deferred, const OctDeferQueue Q) {
+        hipLaunchKernelGGL(oct_chunked_kernel(c.fast, c.tol_form(), deferred), grid, block, 0, nullptr, c.children.p, (int)nc, fx, fy, fz, c.nf, c.boxes.p,
+                           P.ntiles, c.legs.p, c.tols.p, c.tabs.p, c.spheres.p, leg_count, stab, c.reach_len, cr2, c.flags.p, P.splits, P.tpr, Q);
+        return hipGetLastError();
+    };
+    if (P.deferred) { // the table form with its doubts queued for a second launch (see oct_item_flags_defer)
+        const OctDeferQueue Q{c.defer.p, c.defer_count.p, (uint32_t)c.defer_cap};
+        OCT_TRY(hipMemsetAsync(Q.count, 0, 8 * sizeof(uint32_t), nullptr), "hipMemsetAsync");
+        OCT_TRY(chunked(true, Q), "Kernel launch");
+        hipLaunchKernelGGL(oct_deferred_kernel, dim3(2048), block, 0, nullptr, c.children.p, fx, fy, fz, c.legs.p, c.spheres.p, leg_count, stab, cr2,
+                           c.flags.p, Q);
+        OCT_TRY(hipGetLastError(), "Kernel launch");
+        uint32_t qc[8] = {0};
+        OCT_TRY(hipMemcpy(qc, Q.count, sizeof qc, hipMemcpyDeviceToHost), "hipMemcpy queue count");
+#if defined(LRM_OCT_COUNT)
+        fprintf(stderr, "apply_oct: level %d: %u pairs evaluated, %u queued (overflow %u): no table %u, doubt %u, near face %u\n", depth, qc[2], qc[0], qc[1], qc[3], qc[4], qc[5]);
+#endif
+        c.deferred_total += qc[0];
+        if (qc[1] == 0) return LRM_OK;
+        OCT_TRY(hipMemset(c.flags.p, 0, nc * sizeof(uint32_t)), "hipMemset flags"); // the queue overflowed: the level again, doubts inline
+    }
+    OCT_TRY(chunked(false, OctDeferQueue{nullptr, nullptr, 0u}), "Kernel launch");
+    return LRM_OK;
+}
+
+// a level on the device: its children up, the kernels of its plan, its flag words back
+int oct_evaluate_level(OctCall& c, const std::vector<OctChild>& level, int depth, std::vector<uint32_t>& flags) {
+    const size_t nc = level.size();
+    if (nc > c.children_cap) {
+        c.children.reset();
+        c.flags.reset();
+        OCT_TRY(c.children.alloc(nc), "hipMalloc children");
+        OCT_TRY(c.flags.alloc(nc), "hipMalloc flags");
+        c.children_cap = nc;
+    }
+    if (c.world > 1) { // this rank's share of the level: the others' children are skipped on the device only
+        std::vector<OctChild> mine(level);
+        for (size_t k = 0; k < nc; k++)
+            if ((int)(k % (size_t)c.world) != c.rank) mine[k].skip = 1;
+        OCT_TRY(hipMemcpy(c.children.p, mine.data(), nc * sizeof(OctChild), hipMemcpyHostToDevice), "hipMemcpy children");
+    } else {
+        OCT_TRY(hipMemcpy(c.children.p, level.data(), nc * sizeof(OctChild), hipMemcpyHostToDevice), "hipMemcpy children");
+    }
+    OCT_TRY(hipMemset(c.flags.p, 0, nc * sizeof(uint32_t)), "hipMemset flags");
+    if (!c.nf) return LRM_OK;
+    OCT_TRY(hipEventRecord(c.ev.a, nullptr), "hipEventRecord");
+    const OctPlan P = oct_level_plan(nc, c.nf, c.fast && c.tabs.p && c.defer.p, c.knobs);
+    if (int rc = oct_launch_level(c, P, nc, depth)) return rc;
+    OCT_TRY(hipEventRecord(c.ev.b, nullptr), "hipEventRecord");
+    OCT_TRY(hipMemcpy(flags.data(), c.flags.p, nc * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy flags");
+    float e = 0.f;
+    OCT_TRY(hipEventElapsedTime(&e, c.ev.a, c.ev.b), "hipEventElapsedTime");
+    c.total_ms += e;
+    return LRM_OK;
+}
+
+// host only: the flag words of a level into its nodes (several_leg_octree.cu:134-150, with global ORs) -> the nodes to refine next
+std::vector<int> oct_fold_flags(OctCall& c, const std::vector<OctChild>& level, const std::vector<int>& level_nodes,
+                                const std::vector<uint32_t>& flags, bool last_level) {
+    std::vector<Node>& nodes = c.nodes;
+    for (size_t k = 0; k < level.size(); k++) {
+        Node& n = nodes[level_nodes[k]];
+        if (level[k].skip) continue;
+        if (flags[k] & 1u) n.validity = true;
+        if (flags[k] & 2u) n.leaf = true;
+        if ((flags[k] & 4u) && !(flags[k] & 2u)) n.on_edge = true;
+    }
+    // the next host iteration descends (branchKernel "goDeeper", :296-312): a child that is not on
+    // an edge becomes a leaf, the others are refined
+    std::vector<int> next;
+    if (last_level) return next;
+    for (size_t k = 0; k < level.size(); k++) {
+        Node& n = nodes[level_nodes[k]];
+        if (!n.on_edge) n.leaf = true;
+        if (!n.leaf) next.push_back(level_nodes[k]);
+    }
+    return next;
+}
+
+// host only: extractValidAsArray / fill_recus, octree_util.cu:128-180: depth first, child order -> the number of valid leaves
+size_t oct_extract_leaves(const std::vector<Node>& nodes, float* centers_out, size_t capacity) {
+    size_t count = 0;
+    struct Frame { int node; int next; };
+    std::vector<Frame> frames{{0, 0}}; // iterative DFS that visits children in index order
+    while (!frames.empty()) {
+        Frame& fr = frames.back();
+        const Node& n = nodes[fr.node];
+        if (n.first_child < 0 || fr.next >= 8) {
+            frames.pop_back();
+            continue;
+        }
+        const int ci = n.first_child + fr.next++;
+        const Node& ch = nodes[ci];
+        const bool endpoint = !(ch.leaf || ch.raw || ch.dead);
+        const bool valid = !ch.dead && (ch.leaf || ch.raw) && ch.validity;
+        if (endpoint) frames.push_back(Frame{ci, 0});
+        else if (valid) {
+            if (count < capacity) std::memcpy(centers_out + 3 * count, ch.c, 3 * sizeof(float));
+            count++;
+        }
+    }
+    return count;
+}
+
+// ---- the call: its phases in order -> the number of valid leaves in *count -----------------------------------------------
+int oct_run(OctCall& c, const float* footholds, const float* dev_x, const float* dev_y, const float* dev_z, float* centers_out,
+            size_t capacity, size_t* count) {
+    const bool dbg = c.knobs.debug;
+    if (int rc = oct_order_footholds(c, footholds, dev_x, dev_y, dev_z)) return rc;
+    if (c.nf)
+        if (int rc = oct_tile_boxes(c.f.p, c.f.p + c.nf, c.f.p + 2 * c.nf, c.nf, c.ntiles, c.boxes)) return rc;
+    if (dbg) { (void)hipDeviceSynchronize(); fprintf(stderr, "apply_oct: %zu footholds ordered on the device in %.2f ms\n", c.nf, c.clock.lap()); }
+    if (int rc = oct_compile_legs(c)) return rc;
+    if (int rc = oct_upload_legs(c)) return rc;
+    if (dbg) fprintf(stderr, "apply_oct: %zu legs compiled and uploaded in %.2f ms\n", c.legs_host.size(), c.clock.lap());
+    if (c.exchange) { // every rank got this far?
+        uint32_t ready = 0;
+        c.peers_expect = 0;
+        if (c.exchange(&ready, 1, c.user) != 0 || ready == kOctPoison)
+            return oct_fail(LRM_ENODEV, ready == kOctPoison ? "a peer rank failed before the first level" : "the exchange callback failed");
+    }
+    c.nodes.resize(1);
+    for (int i = 0; i < 3; i++) {
+        c.nodes[0].c[i] = c.st.box_center[i];
+        c.nodes[0].h[i] = c.st.box_size[i];
+    }
+    c.nodes[0].raw = true;
+    std::vector<int> expand{0}; // raw nodes to refine in this iteration
+    for (int depth = 0; depth < c.st.max_depth && !expand.empty(); depth++) {
+        std::vector<OctChild> level;
+        std::vector<int> level_nodes;
+        oct_make_children(c, expand, level, level_nodes);
+        const size_t nc = level.size();
+        c.peers_expect = c.exchange ? nc : 0;
+        std::vector<uint32_t> flags(nc, 0);
+        if (int rc = oct_evaluate_level(c, level, depth, flags)) return rc;
+        if (dbg) fprintf(stderr, "apply_oct: level %d, %zu children: %.2f ms (host + kernel)\n", depth, nc, c.clock.lap());
+        if (c.exchange) {
+            c.peers_expect = 0;
+            bool poisoned = c.exchange(flags.data(), nc, c.user) != 0;
+            const bool cb_failed = poisoned;
+            for (size_t k = 0; k < nc && !poisoned; k++) poisoned = flags[k] == kOctPoison;
+            if (poisoned) return oct_fail(LRM_ENODEV, cb_failed ? "the exchange callback failed" : "a peer rank failed");
+        }
+        for (size_t k = 0; k < nc && g_oct_trace; k++) {
+            const OctChild& oc = level[k];
+            const float rec[12] = {oc.c[0], oc.c[1], oc.c[2], oc.h[0], oc.h[1], oc.h[2], oc.ph[0], oc.ph[1], oc.ph[2], (float)(flags[k] & 7u),
+                                   (float)((oc.parent_valid ? 1 : 0) + (oc.n_angles > 1 ? 2 : 0) + (oc.skip ? 4 : 0)), (float)depth};
+            g_oct_trace_recs.insert(g_oct_trace_recs.end(), rec, rec + 12);
+        }
+        expand = oct_fold_flags(c, level, level_nodes, flags, depth + 1 >= c.st.max_depth);
+    }
+    *count = oct_extract_leaves(c.nodes, centers_out, capacity);
+    if (dbg) fprintf(stderr, "apply_oct: %zu nodes, leaves extracted in %.2f ms; %llu (item, orientation) pairs went through the deferred queue\n", c.nodes.size(), c.clock.lap(), c.deferred_total);
+    return LRM_OK;
+}
 
 } // namespace
 
@@ -734,448 +1275,44 @@ static int apply_oct_impl(const float* footholds /* host AoS, or null */, const 
                           size_t nf, const LrmLegDimensions* dim, const LrmOctreeSettings* st_in,
                           float* centers_out, size_t capacity, size_t* n_out, float* ms, int rank, int world,
                           LrmOctExchange exchange, void* user) {
-    auto fail = [](int code, const char* w) { g_oct_err = w; return code; };
-    if (!dim || !n_out || (nf && !footholds && !(dev_x && dev_y && dev_z)) || (capacity && !centers_out)) return fail(LRM_EINVAL, "null argument");
-    if (nf >= ((size_t)1 << 31)) return fail(LRM_EINVAL, "more than 2^31 - 1 footholds: shard the cloud");
-    if (world < 1 || rank < 0 || rank >= world || (world > 1 && !exchange)) return fail(LRM_EINVAL, "bad rank / world / exchange");
-    constexpr uint32_t kOctPoison = 0xffffffffu;
-    size_t peers_expect = exchange ? 1 : 0; // words the peers' next exchange carries (0: none pending)
-    auto abort_peers = [&]() {              // called on a local failure: do not leave the peers waiting
-        if (!exchange || peers_expect == 0) return;
-        std::vector<uint32_t> poison(peers_expect, kOctPoison);
-        peers_expect = 0;
-        (void)exchange(poison.data(), poison.size(), user);
-    };
+    const OctKnobs knobs = oct_read_knobs();
+    if (!dim || !n_out || (nf && !footholds && !(dev_x && dev_y && dev_z)) || (capacity && !centers_out)) return oct_fail(LRM_EINVAL, "null argument");
+    if (nf >= ((size_t)1 << 31)) return oct_fail(LRM_EINVAL, "more than 2^31 - 1 footholds: shard the cloud");
+    if (world < 1 || rank < 0 || rank >= world || (world > 1 && !exchange)) return oct_fail(LRM_EINVAL, "bad rank / world / exchange");
     LrmOctreeSettings st;
     if (st_in) st = *st_in;
     else lrm_octree_default_settings(&st);
     if (st.leg_count < 1 || st.leg_count > LRM_MAX_LEGS || st.leg_number_for_stab > st.leg_count || st.max_depth < 0 ||
         st.angle_sample[0] < 1 || st.angle_sample[1] < 1 || st.angle_sample[2] < 1)
-        return fail(LRM_EINVAL, "bad octree settings");
+        return oct_fail(LRM_EINVAL, "bad octree settings");
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LRM_ENODEV, "no HIP device");
-#define OCT_TRY(expr, where)                                                   \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            g_oct_err = std::string(where) + ": " + hipGetErrorString(e_);     \
-            abort_peers();                                                     \
-            cleanup();                                                         \
-            return (e_ == hipErrorOutOfMemory) ? LRM_ENOMEM : LRM_ENODEV;      \
-        }                                                                      \
-    } while (0)
-    float *d_f = nullptr, *d_boxes = nullptr, *d_tmp_aos = nullptr, *d_tmp_soa = nullptr;
-    uint32_t* d_keys = nullptr;
-    void* d_sort_tmp = nullptr;
-    float4* d_spheres = nullptr;
-    LrmTolLeg* d_tols = nullptr;
-    const uint8_t** d_tabs = nullptr; // device array of the plane tables' device pointers (the tables themselves live in the cache below)
-    uint32_t *d_defer = nullptr, *d_defer_count = nullptr; // the queue of deferred (item, orientation) pairs (oct_item_flags_defer)
-    unsigned long long deferred_total = 0;
-    LrmCompiledLeg* d_legs = nullptr;
-    OctChild* d_children = nullptr;
-    uint32_t* d_flags = nullptr;
-    size_t children_cap = 0;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    auto cleanup = [&]() {
-        if (d_f) (void)hipFree(d_f);
-        if (d_boxes) (void)hipFree(d_boxes);
-        if (d_tmp_aos) (void)hipFree(d_tmp_aos);
-        if (d_tmp_soa) (void)hipFree(d_tmp_soa);
-        if (d_keys) (void)hipFree(d_keys);
-        if (d_sort_tmp) (void)hipFree(d_sort_tmp);
-        if (d_legs) (void)hipFree(d_legs);
-        if (d_spheres) (void)hipFree(d_spheres);
-        if (d_tols) (void)hipFree(d_tols);
-        if (d_tabs) (void)hipFree(d_tabs);
-        if (d_defer) (void)hipFree(d_defer);
-        if (d_defer_count) (void)hipFree(d_defer_count);
-        if (d_children) (void)hipFree(d_children);
-        if (d_flags) (void)hipFree(d_flags);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-    };
-
-    const bool dbg = getenv("LRM_OCT_DEBUG") != nullptr; // host-side phase times on stderr
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
-    auto t_phase = now();
-    // footholds as SoA on the device, in Morton order (the flags are ORs over footholds: the order changes nothing,
-    // but consecutive footholds then fill compact boxes for oct_validity_chunked_kernel)
-    const size_t ntiles = (nf + 1023) / 1024;
-    OCT_TRY(hipMalloc(&d_f, 3 * (nf ? nf : 1) * sizeof(float)), "hipMalloc gpu_in.elements");
-    if (nf) {
-        const unsigned pb = (unsigned)((nf + kOctBlock - 1) / kOctBlock);
-        const float *ux = dev_x, *uy = dev_y, *uz = dev_z;
-        if (footholds) { // host AoS (the reference's Array<float3>): upload, split
-            OCT_TRY(hipMalloc(&d_tmp_aos, 3 * nf * sizeof(float)), "hipMalloc footholds");
-            OCT_TRY(hipMalloc(&d_tmp_soa, 3 * nf * sizeof(float)), "hipMalloc footholds");
-            OCT_TRY(hipMemcpy(d_tmp_aos, footholds, 3 * nf * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy gpu_in.elements");
-            hipLaunchKernelGGL(oct_aos_to_soa_kernel, dim3(pb), dim3(kOctBlock), 0, nullptr, d_tmp_aos, nf, d_tmp_soa, d_tmp_soa + nf, d_tmp_soa + 2 * nf);
-            OCT_TRY(hipGetLastError(), "Kernel launch");
-            ux = d_tmp_soa;
-            uy = d_tmp_soa + nf;
-            uz = d_tmp_soa + 2 * nf;
-        }
-        // bounding box of the cloud: the tile boxes of the unsorted cloud, reduced on the host
-        OCT_TRY(hipMalloc(&d_boxes, ntiles * 17 * 6 * sizeof(float)), "hipMalloc foothold boxes");
-        hipLaunchKernelGGL(oct_boxes_kernel, dim3((unsigned)ntiles), dim3(kOctBlock), 0, nullptr, ux, uy, uz, nf, ntiles, d_boxes);
-        OCT_TRY(hipGetLastError(), "Kernel launch");
-        std::vector<float> tb(ntiles * 6);
-        OCT_TRY(hipMemcpy(tb.data(), d_boxes, tb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy boxes");
-        OctBounds ob;
-        for (int a = 0; a < 3; a++) {
-            float lo = 3.0e38f, hi = -3.0e38f;
-            for (size_t t = 0; t < ntiles; t++) {
-                lo = std::min(lo, tb[t * 6 + a]);
-                hi = std::max(hi, tb[t * 6 + 3 + a]);
-            }
-            ob.lo[a] = lo;
-            ob.inv[a] = (hi > lo && std::isfinite(hi - lo)) ? 1.0f / (hi - lo) : 0.f;
-        }
-        OCT_TRY(hipMalloc(&d_keys, 4 * nf * sizeof(uint32_t)), "hipMalloc sort keys"); // keys, indices, and their sorted copies
-        uint32_t *k_in = d_keys, *i_in = d_keys + nf, *k_out = d_keys + 2 * nf, *i_out = d_keys + 3 * nf;
-        hipLaunchKernelGGL(oct_keys_kernel, dim3(pb), dim3(kOctBlock), 0, nullptr, ux, uy, uz, nf, ob, k_in, i_in);
-        OCT_TRY(hipGetLastError(), "Kernel launch");
-        size_t sort_bytes = 0;
-        OCT_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k_in, k_out, i_in, i_out, (int)nf, 0, 30, (hipStream_t) nullptr), "radix sort (size)");
-        OCT_TRY(hipMalloc(&d_sort_tmp, sort_bytes ? sort_bytes : 16), "hipMalloc sort workspace");
-        OCT_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_bytes, k_in, k_out, i_in, i_out, (int)nf, 0, 30, (hipStream_t) nullptr), "radix sort");
-        hipLaunchKernelGGL(oct_gather_kernel, dim3(pb), dim3(kOctBlock), 0, nullptr, ux, uy, uz, i_out, nf, d_f, d_f + nf, d_f + 2 * nf);
-        OCT_TRY(hipGetLastError(), "Kernel launch");
-        OCT_TRY(hipDeviceSynchronize(), "footholds in Morton order");
-        (void)hipFree(d_sort_tmp); d_sort_tmp = nullptr;
-        (void)hipFree(d_keys); d_keys = nullptr;
-        if (d_tmp_aos) { (void)hipFree(d_tmp_aos); d_tmp_aos = nullptr; }
-        if (d_tmp_soa) { (void)hipFree(d_tmp_soa); d_tmp_soa = nullptr; }
-        (void)hipFree(d_boxes); d_boxes = nullptr;
-    }
-    if (nf) {
-        OCT_TRY(hipMalloc(&d_boxes, ntiles * 17 * 6 * sizeof(float)), "hipMalloc foothold boxes");
-        hipLaunchKernelGGL(oct_boxes_kernel, dim3((unsigned)ntiles), dim3(kOctBlock), 0, nullptr, d_f, d_f + nf, d_f + 2 * nf, nf, ntiles, d_boxes);
-        OCT_TRY(hipGetLastError(), "Kernel launch");
-    }
-
-    if (dbg) { (void)hipDeviceSynchronize(); fprintf(stderr, "apply_oct: %zu footholds ordered on the device in %.2f ms\n", nf, ms_since(t_phase)); t_phase = now(); }
-    // compiled legs for every (orientation sample, mounted leg)
-    const int n_angles_max = st.angle_sample[0] * st.angle_sample[1] * st.angle_sample[2];
-    std::vector<LrmCompiledLeg> legs((size_t)n_angles_max * st.leg_count);
-    bool all_fast = true;
-    for (int a = 0; a < n_angles_max; a++) {
-        const Quat q = quat_from_angle_index((unsigned)a, st);
-        const float qa[4] = {q.x, q.y, q.z, q.w};
-        for (int l = 0; l < st.leg_count; l++) {
-            LrmLegDimensions leg = *dim;
-            leg.body_angle = st.leg_mount[l]; // several_leg_octree.cu:94
-            lrm_compile_leg(leg, qa, 1, &legs[(size_t)a * st.leg_count + l]);
-            all_fast = all_fast && legs[(size_t)a * st.leg_count + l].fast_ok;
-        }
-    }
-    const bool fast = all_fast && lrm_get_mode() != LRM_MODE_STRICT;
-    // the tolerance blocks (filtered mode; LRM_OCT_TOL=0: without -- A/B runs and tests): lrm_compile_tol costs ~0.3 ms of host
-    // geometry per (orientation, leg), so they are worth it from a few hundred thousand footholds on and are kept across calls
-    {
-        const char* e = getenv("LRM_OCT_TOL");
-        const bool want = fast && (e ? e[0] != '0' : nf >= 300000);
-        if (want) {
-            std::vector<LrmTolLeg> tols(legs.size());
-            std::vector<const uint8_t*> tabs(legs.size(), nullptr);
-            // the plane tables (LRM_OCT_TAB=0: without): built on the device on first use, ~0.4 ms each, kept across calls
-            const char* et = getenv("LRM_OCT_TAB");
-            const bool want_tab = et ? et[0] != '0' : true;
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            bool any_tab = false;
-            std::lock_guard<std::mutex> g(g_oct_tab_mu);
-            auto& cache = g_oct_tab_cache;
-            for (int a = 0; a < n_angles_max; a++) {
-                const Quat q = quat_from_angle_index((unsigned)a, st);
-                for (int l = 0; l < st.leg_count; l++) {
-                    LrmLegDimensions leg = *dim;
-                    leg.body_angle = st.leg_mount[l];
-                    std::array<float, 18> key;
-                    std::memcpy(key.data(), &leg, 14 * sizeof(float));
-                    key[14] = q.x; key[15] = q.y; key[16] = q.z; key[17] = q.w;
-                    auto it = cache.find(key);
-                    if (it == cache.end()) {
-                        // A full cache takes no new entry (and frees nothing: another thread's call may be running on its tables): this
-                        // pair goes without a table -- its items through the filtered code (4096 pairs: a thousand robots' worth).
-                        if (cache.size() >= 4096) {
-                            lrm_compile_tol(legs[(size_t)a * st.leg_count + l], &tols[(size_t)a * st.leg_count + l]);
-                            continue;
-                        }
-                        OctTabEntry en;
-                        lrm_compile_tol(legs[(size_t)a * st.leg_count + l], &en.tl);
-                        it = cache.emplace(key, en).first;
-                    }
-                    tols[(size_t)a * st.leg_count + l] = it->second.tl;
-                    if (want_tab && it->second.tl.tol_ok) {
-                        auto dt = it->second.tab_dev.find(dev);
-                        if (dt == it->second.tab_dev.end()) {
-                            uint8_t* t = nullptr;
-                            size_t bytes = 0;
-                            float ms = 0.f;
-                            const int rc = lrm_build_tol_tab_dev(it->second.tl, nullptr, &t, &bytes, &ms);
-                            if (rc < 0) OCT_TRY((hipError_t)(-rc), "plane table (device builder)");
-                            // rc 1 or 2 (no table, the builder declines the leg, or no device memory for its scratch): this pair
-                            // goes without a table -- same results, slower -- until lrm_release_workspaces empties the cache
-
-                            dt = it->second.tab_dev.emplace(dev, rc == 0 ? t : nullptr).first;
-                        }
-                        tabs[(size_t)a * st.leg_count + l] = dt->second;
-                        any_tab = any_tab || dt->second != nullptr;
-                    }
-                }
-            }
-            OCT_TRY(hipMalloc(&d_tols, tols.size() * sizeof(LrmTolLeg)), "hipMalloc tolerance blocks");
-            OCT_TRY(hipMemcpy(d_tols, tols.data(), tols.size() * sizeof(LrmTolLeg), hipMemcpyHostToDevice), "hipMemcpy tolerance blocks");
-            if (any_tab) {
-                OCT_TRY(hipMalloc(reinterpret_cast<void**>(&d_tabs), tabs.size() * sizeof(uint8_t*)), "hipMalloc table pointers");
-                OCT_TRY(hipMemcpy(d_tabs, tabs.data(), tabs.size() * sizeof(uint8_t*), hipMemcpyHostToDevice), "hipMemcpy table pointers");
-                const char* ed = getenv("LRM_OCT_DEFER"); // LRM_OCT_DEFER=0: the doubts of the table form inline (A/B runs and tests)
-                if (!ed || ed[0] != '0') {
-                    OCT_TRY(hipMalloc(reinterpret_cast<void**>(&d_defer), oct_defer_cap(nf) * 3 * sizeof(uint32_t)), "hipMalloc deferred pairs");
-                    OCT_TRY(hipMalloc(reinterpret_cast<void**>(&d_defer_count), 8 * sizeof(uint32_t)), "hipMalloc deferred count");
-                }
-            }
-        }
-    }
-    OCT_TRY(hipMalloc(&d_legs, legs.size() * sizeof(LrmCompiledLeg)), "hipMalloc legs");
-    OCT_TRY(hipMemcpy(d_legs, legs.data(), legs.size() * sizeof(LrmCompiledLeg), hipMemcpyHostToDevice), "hipMemcpy legs");
-    // bounding sphere of what each (orientation, leg) reaches, in the frame distance_global takes its point in:
-    // pair_center lives in the frame of reachable_rotate_leg (the target relative to the body, before the quaternion);
-    // distance_global first applies qtRotate(qtInvert(q), .), so the centre goes through qtRotate(q, .)
-    std::vector<float4> spheres(legs.size());
-    const bool no_cull = getenv("LRM_OCT_NOCULL") && getenv("LRM_OCT_NOCULL")[0] == '1'; // tests: every work item evaluated
-    for (size_t k = 0; k < legs.size(); k++) {
-        const LrmCompiledLeg& L = legs[k];
-        const LrmVec3 c = lrm_qrot(L.fwd_rot, LrmVec3{L.pair_center[0], L.pair_center[1], L.pair_center[2]});
-        spheres[k] = make_float4(c.x, c.y, c.z, no_cull ? 1.0e18f : std::sqrt(L.pair_r2) * 1.0001f + 0.5f);
-    }
-    OCT_TRY(hipMalloc(&d_spheres, spheres.size() * sizeof(float4)), "hipMalloc spheres");
-    OCT_TRY(hipMemcpy(d_spheres, spheres.data(), spheres.size() * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy spheres");
-    OCT_TRY(hipEventCreate(&ev_a), "hipEventCreate");
-    OCT_TRY(hipEventCreate(&ev_b), "hipEventCreate");
-
-    if (dbg) { fprintf(stderr, "apply_oct: %zu legs compiled and uploaded in %.2f ms\n", legs.size(), ms_since(t_phase)); t_phase = now(); }
-    if (exchange) { // every rank got this far?
-        uint32_t ready = 0;
-        peers_expect = 0;
-        if (exchange(&ready, 1, user) != 0 || ready == kOctPoison) {
-            g_oct_err = ready == kOctPoison ? "a peer rank failed before the first level" : "the exchange callback failed";
-            cleanup();
-            return LRM_ENODEV;
-        }
-    }
-    std::vector<Node> nodes(1);
-    for (int i = 0; i < 3; i++) {
-        nodes[0].c[i] = st.box_center[i];
-        nodes[0].h[i] = st.box_size[i];
-    }
-    nodes[0].raw = true;
-    const float reach_len = dim->body + dim->coxa_length + dim->femur_length + dim->tibia_length;
-    std::vector<int> expand{0}; // raw nodes to refine in this iteration
-    float total_ms = 0.f;
-    for (int depth = 0; depth < st.max_depth && !expand.empty(); depth++) {
-        std::vector<OctChild> level;
-        std::vector<int> level_nodes;
-        for (int pi : expand) {
-            const int first = (int)nodes.size();
-            nodes.resize(nodes.size() + 8);
-            Node& parent = nodes[pi];
-            parent.first_child = first;
-            const bool rot = parent.h[0] < st.enable_rot_below; // several_leg_octree.cu:52
-            for (unsigned ci = 0; ci < 8; ci++) {
-                Node& n = nodes[first + ci];
-                int missing = 0;
-                if (!create_child_box(parent, ci, st.min_box, &n, &missing)) { // several_leg_octree.cu:331-339
-                    n.dead = n.leaf = n.validity = n.on_edge = true;
-                    n.raw = false;
-                    std::memset(n.c, 0, sizeof n.c);
-                    std::memset(n.h, 0, sizeof n.h);
-                } else if (3 - missing <= 0) { // :342-347
-                    n.leaf = true;
-                    n.raw = false;
-                } else {                       // :348-353
-                    n.leaf = false;
-                    n.raw = true;
-                }
-                OctChild oc;
-                std::memcpy(oc.c, n.c, sizeof oc.c);
-                std::memcpy(oc.h, n.h, sizeof oc.h);
-                std::memcpy(oc.ph, parent.h, sizeof oc.ph);
-                oc.margin = rot ? 0.f : st.enable_rot_below / 3;
-                oc.n_angles = rot ? n_angles_max : 1;
-                oc.parent_valid = parent.validity;
-                oc.skip = n.validity; // dead quadrants are "valid" and skipped (:58-61)
-                oc.pad = 0;
-                level.push_back(oc);
-                level_nodes.push_back(first + ci);
-            }
-            nodes[pi].raw = false;
-        }
-        const size_t nc = level.size();
-        peers_expect = exchange ? nc : 0;
-        if (nc > children_cap) {
-            if (d_children) (void)hipFree(d_children);
-            if (d_flags) (void)hipFree(d_flags);
-            d_children = nullptr;
-            d_flags = nullptr;
-            OCT_TRY(hipMalloc(&d_children, nc * sizeof(OctChild)), "hipMalloc children");
-            OCT_TRY(hipMalloc(&d_flags, nc * sizeof(uint32_t)), "hipMalloc flags");
-            children_cap = nc;
-        }
-        if (world > 1) { // this rank's share of the level: the others' children are skipped on the device only
-            std::vector<OctChild> mine(level);
-            for (size_t k = 0; k < nc; k++)
-                if ((int)(k % (size_t)world) != rank) mine[k].skip = 1;
-            OCT_TRY(hipMemcpy(d_children, mine.data(), nc * sizeof(OctChild), hipMemcpyHostToDevice), "hipMemcpy children");
-        } else {
-            OCT_TRY(hipMemcpy(d_children, level.data(), nc * sizeof(OctChild), hipMemcpyHostToDevice), "hipMemcpy children");
-        }
-        OCT_TRY(hipMemset(d_flags, 0, nc * sizeof(uint32_t)), "hipMemset flags");
-        std::vector<uint32_t> flags(nc, 0);
-        if (nf) {
-            OCT_TRY(hipEventRecord(ev_a, nullptr), "hipEventRecord");
-            const float cr2 = st.convex_radius * st.convex_radius;
-            // LRM_OCT_BRUTE=1 (tests): every level with the every-foothold kernel, for comparison
-            const bool brute = getenv("LRM_OCT_BRUTE") && getenv("LRM_OCT_BRUTE")[0] == '1' && nc <= 65535;
-            size_t chunked_from = (size_t)kOctChunkedFrom;
-            if (const char* e = getenv("LRM_OCT_CHUNKED_FROM")) chunked_from = (size_t)atol(e); // experiments
-            // (the first level's 8 huge children too when the cloud has enough tiles to spread them over the chip: 6.4 -> 4.0 ms at 1.25e7 footholds)
-            if ((nc >= chunked_from || (!getenv("LRM_OCT_CHUNKED_FROM") && nc * ((ntiles + 31) / 32) >= 2048)) && !brute) {
-                // many small children: one workgroup per child, only the footholds of nearby chunks
-                // workgroups per child: at least ~4096 workgroups in flight, at most one per round of 256 tiles
-                // (levels of few, huge children: rounds of fewer tiles, so that more workgroups share a child and look at its flags more often)
-                // config-5 share, levels of 64 / 256 / 976 / 4112 children: 11.6 / 9.2 / 9.9 / 14.3 ms with rounds of 256 tiles and 4096
-                // workgroups -> 5.3 / 6.1 / 8.4 / 13.4 ms (profiles/r04_octree.txt); the deepest level (15 856 children) is best left alone
-                size_t tpr = nc < 2048 ? 32 : (nc < 8192 ? 128 : kOctBlock);
-                if (const char* e = getenv("LRM_OCT_TPR")) tpr = std::min<size_t>(std::max<size_t>((size_t)atol(e), 1), kOctBlock);
-                size_t want_wgs = nc < 2048 ? 32768 : (nc < 8192 ? 8192 : 4096);
-                if (const char* e = getenv("LRM_OCT_WGS")) want_wgs = (size_t)atol(e);
-                size_t splits = nc >= want_wgs ? 1 : (want_wgs + nc - 1) / nc;
-                splits = std::min(splits, std::max<size_t>(1, (ntiles + tpr - 1) / tpr));
-                splits = std::min<size_t>(splits, 256);
-                const dim3 grid((unsigned)std::min<size_t>(nc * splits, (size_t)256 * 64));
-#define LRM_OCT_CHUNKED(FAST, TOL) hipLaunchKernelGGL((oct_validity_chunked_kernel<FAST, TOL>), grid, dim3(kOctBlock), 0, nullptr, d_children, (int)nc, d_f, d_f + nf, \
-                                       d_f + 2 * nf, nf, d_boxes, ntiles, d_legs, d_tols, d_tabs, d_spheres, st.leg_count, st.leg_number_for_stab, reach_len, cr2, d_flags, (uint32_t)splits, (uint32_t)tpr, OctDeferQueue{nullptr, nullptr, 0u})
-                bool deferred_done = false;
-                // the table form with its doubts queued for a second launch (see oct_item_flags_defer) -- from 256 children on: the few huge
-                // children of the first levels saturate their flags early, and later when some of their items wait in the queue
-                const size_t defer_from = getenv("LRM_OCT_DEFER_FROM") ? (size_t)atol(getenv("LRM_OCT_DEFER_FROM")) : (size_t)256;
-                if (fast && d_tabs && d_defer && nc >= defer_from) {
-                    const OctDeferQueue Q{d_defer, d_defer_count, (uint32_t)oct_defer_cap(nf)};
-                    OCT_TRY(hipMemsetAsync(d_defer_count, 0, 8 * sizeof(uint32_t), nullptr), "hipMemsetAsync");
-                    hipLaunchKernelGGL((oct_validity_chunked_kernel<true, 2, true>), grid, dim3(kOctBlock), 0, nullptr, d_children, (int)nc, d_f, d_f + nf,
-                                       d_f + 2 * nf, nf, d_boxes, ntiles, d_legs, d_tols, d_tabs, d_spheres, st.leg_count, st.leg_number_for_stab, reach_len, cr2, d_flags, (uint32_t)splits, (uint32_t)tpr, Q);
-                    OCT_TRY(hipGetLastError(), "Kernel launch");
-                    hipLaunchKernelGGL(oct_deferred_kernel, dim3(2048), dim3(kOctBlock), 0, nullptr, d_children, d_f, d_f + nf, d_f + 2 * nf, d_legs, d_spheres,
-                                       st.leg_count, st.leg_number_for_stab, cr2, d_flags, Q);
-                    OCT_TRY(hipGetLastError(), "Kernel launch");
-                    uint32_t qc[8] = {0};
-                    OCT_TRY(hipMemcpy(qc, d_defer_count, sizeof qc, hipMemcpyDeviceToHost), "hipMemcpy queue count");
-#if defined(LRM_OCT_COUNT)
-                    fprintf(stderr, "apply_oct: level %d: %u pairs evaluated, %u queued (overflow %u): no table %u, doubt %u, near face %u\n", depth, qc[2], qc[0], qc[1], qc[3], qc[4], qc[5]);
-#endif
-                    deferred_total += qc[0];
-                    if (qc[1] == 0) deferred_done = true;
-                    else OCT_TRY(hipMemset(d_flags, 0, nc * sizeof(uint32_t)), "hipMemset flags"); // the queue overflowed: the level again, doubts inline
-                }
-                if (deferred_done) {}
-                else if (fast && d_tabs) LRM_OCT_CHUNKED(true, 2);
-                else if (fast && d_tols) LRM_OCT_CHUNKED(true, 1);
-                else if (fast) LRM_OCT_CHUNKED(true, 0);
-                else LRM_OCT_CHUNKED(false, 0);
-#undef LRM_OCT_CHUNKED
-            } else {
-                // few, huge children (the first levels): every foothold, spread over the chip; grid.y = children < 65
-                size_t gx = (nf + kOctBlock - 1) / kOctBlock;
-                if (gx > 1024) gx = 1024;
-                const dim3 grid((unsigned)gx, (unsigned)nc);
-#define LRM_OCT_EVERY(FAST, TOL) hipLaunchKernelGGL((oct_validity_kernel<FAST, TOL>), grid, dim3(kOctBlock), 0, nullptr, d_children, (int)nc, d_f, d_f + nf, \
-                                       d_f + 2 * nf, nf, d_legs, d_tols, d_tabs, d_spheres, st.leg_count, st.leg_number_for_stab, reach_len, cr2, d_flags)
-                if (fast && d_tabs) LRM_OCT_EVERY(true, 2);
-                else if (fast && d_tols) LRM_OCT_EVERY(true, 1);
-                else if (fast) LRM_OCT_EVERY(true, 0);
-                else LRM_OCT_EVERY(false, 0);
-#undef LRM_OCT_EVERY
-            }
-            OCT_TRY(hipGetLastError(), "Kernel launch");
-            OCT_TRY(hipEventRecord(ev_b, nullptr), "hipEventRecord");
-            OCT_TRY(hipMemcpy(flags.data(), d_flags, nc * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy flags");
-            float e = 0.f;
-            OCT_TRY(hipEventElapsedTime(&e, ev_a, ev_b), "hipEventElapsedTime");
-            total_ms += e;
-        }
-        if (dbg) { fprintf(stderr, "apply_oct: level %d, %zu children: %.2f ms (host + kernel)\n", depth, nc, ms_since(t_phase)); t_phase = now(); }
-        if (exchange) {
-            peers_expect = 0;
-            bool poisoned = exchange(flags.data(), nc, user) != 0;
-            const bool cb_failed = poisoned;
-            for (size_t k = 0; k < nc && !poisoned; k++) poisoned = flags[k] == kOctPoison;
-            if (poisoned) {
-                g_oct_err = cb_failed ? "the exchange callback failed" : "a peer rank failed";
-                cleanup();
-                return LRM_ENODEV;
-            }
-        }
-        if (g_oct_trace)
-            for (size_t k = 0; k < nc; k++) {
-                const OctChild& oc = level[k];
-                const float rec[12] = {oc.c[0], oc.c[1], oc.c[2], oc.h[0], oc.h[1], oc.h[2], oc.ph[0], oc.ph[1], oc.ph[2], (float)(flags[k] & 7u),
-                                       (float)((oc.parent_valid ? 1 : 0) + (oc.n_angles > 1 ? 2 : 0) + (oc.skip ? 4 : 0)), (float)depth};
-                g_oct_trace_recs.insert(g_oct_trace_recs.end(), rec, rec + 12);
-            }
-        // several_leg_octree.cu:134-150, with global ORs
-        std::vector<int> next;
-        for (size_t k = 0; k < nc; k++) {
-            Node& n = nodes[level_nodes[k]];
-            if (level[k].skip) continue;
-            if (flags[k] & 1u) n.validity = true;
-            if (flags[k] & 2u) n.leaf = true;
-            if ((flags[k] & 4u) && !(flags[k] & 2u)) n.on_edge = true;
-        }
-        // the next host iteration descends (branchKernel "goDeeper", :296-312): a child that is not on
-        // an edge becomes a leaf, the others are refined
-        if (depth + 1 < st.max_depth) {
-            for (size_t k = 0; k < nc; k++) {
-                Node& n = nodes[level_nodes[k]];
-                if (!n.on_edge) n.leaf = true;
-                if (!n.leaf) next.push_back(level_nodes[k]);
-            }
-        }
-        expand.swap(next);
-    }
-    // extractValidAsArray / fill_recus, octree_util.cu:128-180: depth first, child order
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return oct_fail(LRM_ENODEV, "no HIP device");
+    OctClock clock;
     size_t count = 0;
-    std::vector<int> stack{0};
-    // iterative DFS that visits children in index order
-    struct Frame { int node; int next; };
-    std::vector<Frame> st_frames{{0, 0}};
-    while (!st_frames.empty()) {
-        Frame& fr = st_frames.back();
-        const Node& n = nodes[fr.node];
-        if (n.first_child < 0 || fr.next >= 8) {
-            st_frames.pop_back();
-            continue;
+    {
+        OctCall c{knobs, clock, dim, st, nf, rank, world, exchange, user, exchange ? (size_t)1 : 0};
+        c.ntiles = (nf + kOctTile - 1) / kOctTile;
+        c.defer_cap = oct_defer_cap(nf, knobs.defer_cap.set, knobs.defer_cap.v);
+        c.reach_len = dim->body + dim->coxa_length + dim->femur_length + dim->tibia_length;
+        const int rc = oct_run(c, footholds, dev_x, dev_y, dev_z, centers_out, capacity, &count);
+        if (rc != LRM_OK) {
+            c.abort_peers();
+            return rc;
         }
-        const int ci = n.first_child + fr.next++;
-        const Node& c = nodes[ci];
-        const bool endpoint = !(c.leaf || c.raw || c.dead);
-        const bool valid = !c.dead && (c.leaf || c.raw) && c.validity;
-        if (endpoint) st_frames.push_back(Frame{ci, 0});
-        else if (valid) {
-            if (count < capacity) std::memcpy(centers_out + 3 * count, c.c, 3 * sizeof(float));
-            count++;
-        }
-    }
-    *n_out = count;
-    if (ms) *ms = total_ms;
-    if (dbg) { fprintf(stderr, "apply_oct: %zu nodes, leaves extracted in %.2f ms; %llu (item, orientation) pairs went through the deferred queue\n", nodes.size(), ms_since(t_phase), deferred_total); t_phase = now(); }
-    cleanup();
-    if (dbg) fprintf(stderr, "apply_oct: device memory released in %.2f ms\n", ms_since(t_phase));
-#undef OCT_TRY
-    if (count > capacity) return fail(LRM_EINVAL, "output capacity too small (n_out holds the required count)");
+        *n_out = count;
+        if (ms) *ms = c.total_ms;
+    } // the call's device memory is released here
+    if (knobs.debug) fprintf(stderr, "apply_oct: device memory released in %.2f ms\n", clock.lap());
+    if (count > capacity) return oct_fail(LRM_EINVAL, "output capacity too small (n_out holds the required count)");
+    return LRM_OK;
+}
+
+/* the launch plan of a level, as oct_evaluate_level asks for it when the tables and the queue exist (include/lrm.h); host only */
+int lrm_dbg_oct_plan(size_t nc, size_t nf, uint64_t out[8]) {
+    if (!out || nc == 0) return oct_fail(LRM_EINVAL, "null argument, or a level without children");
+    const OctPlan P = oct_level_plan(nc, nf, true, oct_read_knobs());
+    const uint64_t v[8] = {P.chunked ? 1u : 0u, P.gx, P.gy, P.tpr, P.splits, P.deferred ? 1u : 0u, P.ntiles, (uint64_t)kOctBlock};
+    std::memcpy(out, v, sizeof v);
     return LRM_OK;
 }
 

@@ -1,7 +1,8 @@
 """Case generators of tests/test_gpu_octree_shapes.py (the octree kernels of csrc/lrm_octree.hip across chunk, tile, block, round,
 grid-stride and box boundaries); their preconditions are checked on the host by tests/test_octree_cases_cpu.py.
 
-* launch_constants / launch_plan: the launch arithmetic of apply_oct_impl, restated from numbers parsed out of the source.
+* launch_constants / launch_plan: the launch arithmetic of oct_level_plan (csrc/lrm_octree.hip), restated independently;
+  tests/test_octree_cases_cpu.py holds it against lrm_dbg_oct_plan, which calls the function the launch consumes.
 * oracle_tree: octree_oracle.apply_oct with the level records kept (sizes, missing axes, dead quadrants, parent_valid, flags).
 * morton_keys: oct_keys_kernel's key, so that a case can say where in memory a foothold ends up.
 * decider_cloud: a few footholds that decide the tree plus any number of inert ones -- any cloud size is cheap for the oracle.
@@ -23,27 +24,15 @@ SIZES = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 32
 FAR = 4.0e6  # mm: the far root of the box-geometry cases (one float32 ulp there is 0.25 mm)
 
 
-# ---- the launch arithmetic, from the source ---------------------------------------------------
+# ---- the launch arithmetic, restated ------------------------------------------------------------
 def launch_constants():
-    src = open(os.path.join(CSRC, "lrm_octree.hip")).read()
-
-    def num(pat, k=1):
-        return int(re.search(pat, src).group(k))
-
-    tpr = re.search(r"size_t tpr = nc < (\d+) \? (\d+) : \(nc < (\d+) \? (\d+) : kOctBlock\);", src)
-    wgs = re.search(r"size_t want_wgs = nc < (\d+) \? (\d+) : \(nc < (\d+) \? (\d+) : (\d+)\);", src)
-    cap = re.search(r"std::min<size_t>\(nc \* splits, \(size_t\)(\d+) \* (\d+)\)", src)
-    assert re.search(r"s_chunks\[k\] \* 64 \+ \(threadIdx\.x & 63\)", src) and re.search(r"blockIdx\.x \* 1024;", src)
-    return {"block": num(r"constexpr int kOctBlock = (\d+);"), "chunk": 64, "tile": num(r"ntiles = \(nf \+ \d+\) / (\d+);"),
-            "chunked_from": num(r"constexpr int kOctChunkedFrom = (\d+);"), "every_cap": num(r"if \(gx > (\d+)\) gx = \d+;"),
-            "chunked_cap": int(cap.group(1)) * int(cap.group(2)), "first_level_wgs": num(r"\(ntiles \+ 31\) / 32\) >= (\d+)\)"),
-            "tpr": tuple(int(t) for t in tpr.groups()), "wgs": tuple(int(t) for t in wgs.groups()),
-            "max_splits": num(r"splits = std::min<size_t>\(splits, (\d+)\);"),
-            "defer_from": num(r'atol\(getenv\("LRM_OCT_DEFER_FROM"\)\) : \(size_t\)(\d+);'), "brute_max": num(r"nc <= (\d+);")}
+    """the numbers of oct_level_plan and of the kernels' geometry the sizes of the suite are built around"""
+    return {"block": 256, "chunk": 64, "tile": 1024, "chunked_from": 9, "every_cap": 1024, "chunked_cap": 16384, "first_level_wgs": 2048,
+            "tpr": (2048, 32, 8192, 128), "wgs": (2048, 32768, 8192, 8192, 4096), "max_splits": 256, "defer_from": 256, "brute_max": 65535}
 
 
 def launch_plan(nc, nf, env=None):
-    """what apply_oct_impl launches for a level of nc children on nf footholds under the knobs in env"""
+    """what oct_level_plan says for a level of nc children on nf footholds under the knobs in env"""
     K, env = launch_constants(), env or {}
     ntiles = (nf + K["tile"] - 1) // K["tile"]
     brute = env.get("LRM_OCT_BRUTE", "0")[0] == "1" and nc <= K["brute_max"]

@@ -2,8 +2,9 @@
 the sizes are built around, the inert footholds, the place of the extreme decider in memory, that every case's tree depends on
 the foothold its GPU test is about, and that the box-geometry cases contain the node kinds they are there for.
 
-A change of kOctBlock, kOctChunkedFrom, the tile or chunk size, a grid cap or a tpr / want_wgs tier in lrm_octree.hip must come with
-the new values in test_launch_constants_are_the_ones_the_suite_is_built_around, or the boundaries move away from the tests."""
+A change of kOctBlock, kOctChunkedFrom, the tile or chunk size, a grid cap or a tpr / want_wgs tier in lrm_octree.hip fails
+test_launch_plan_is_the_plan_the_library_launches; it must come with the new values in octree_cases.launch_constants and in
+test_launch_constants_are_the_ones_the_suite_is_built_around, or the boundaries move away from the tests."""
 import numpy as np
 import pytest
 
@@ -29,6 +30,57 @@ def test_launch_constants_are_the_ones_the_suite_is_built_around():
     assert {32 * K["tile"], 32 * K["tile"] + 1} <= set(oc.SIZES)  # one round of tpr = 32 tiles, and one foothold more
     assert max(oc.SIZES) == K["every_cap"] * K["block"] + K["chunk"] + 1  # a second trip of the grid stride with one chunk and a foothold
     assert oc.max_legs() == 8
+
+
+def test_launch_plan_is_the_plan_the_library_launches(lrm, monkeypatch):
+    """oc.launch_plan against lrm_dbg_oct_plan (oct_level_plan, which the level launcher consumes) under the same switches, field by
+    field, with level sizes and cloud sizes on both sides of every threshold and cap; `seen` keeps the sweep honest: each
+    constant of launch_constants decides some compared plan"""
+    K = oc.launch_constants()
+    first_level = (K["first_level_wgs"] // 8 - 1) * 32 * K["tile"]  # 8 children: ((ntiles + 31) // 32) * 8 reaches 2048 one foothold later
+    ncs = (1, 8, 9, 10, 63, 64, 255, 256, 257, 2047, 2048, 8191, 8192, 65535, 65536)
+    nfs = oc.SIZES + (8193, 65_537, first_level, first_level + 1)
+    envs = [{}, {"LRM_OCT_BRUTE": "1"}, {"LRM_OCT_CHUNKED_FROM": "1"}, {"LRM_OCT_DEFER_FROM": "1"}, oc.SPLIT_ENV, {"LRM_OCT_TPR": "0"},
+            {"LRM_OCT_TPR": "100000"}, {"LRM_OCT_TPR": "1", "LRM_OCT_WGS": "100000"}, {"LRM_OCT_TPR": "1", "LRM_OCT_WGS": "1000000"}]
+    seen = set()
+    for env in envs:
+        with monkeypatch.context() as m:
+            for knob in oc.KNOBS:
+                m.delenv(knob, raising=False)
+            for k, v in env.items():
+                m.setenv(k, v)
+            for nc in ncs:
+                for nf in nfs:
+                    want, got = oc.launch_plan(nc, nf, env), lrm.dbg_oct_plan(nc, nf)
+                    where = (env, nc, nf, want, got)
+                    assert got["kernel"] == want["kernel"] and got["deferred"] == want["deferred"] and got["grid_x"] == want["grid"], where
+                    assert got["block"] == K["block"] and got["ntiles"] == -(-nf // K["tile"]), where
+                    if want["kernel"] == "every":
+                        assert got["grid_y"] == nc and got["tpr"] == 0 and got["splits"] == 0, where
+                        assert want["trips"] == -(-((nf + 63) // 64 * 64) // (got["grid_x"] * got["block"])), where
+                        seen |= {"every", "every_cap" if (nf + K["block"] - 1) // K["block"] > K["every_cap"] else "every_below_cap"}
+                        seen |= {"brute"} if env.get("LRM_OCT_BRUTE") and nc >= K["chunked_from"] else set()
+                        continue
+                    assert got["grid_y"] == 1 and got["tpr"] == want["tpr"] and got["splits"] == want["splits"], where
+                    assert got["grid_x"] == min(nc * got["splits"], K["chunked_cap"]), where
+                    seen |= {"chunked", "deferred" if got["deferred"] else "inline", "tpr_%d" % got["tpr"]}
+                    seen |= {"grid_cap"} if nc * got["splits"] > K["chunked_cap"] else set()
+                    seen |= {"max_splits"} if got["splits"] == K["max_splits"] and got["ntiles"] > K["max_splits"] * got["tpr"] else set()
+                    seen |= {"splits_by_tiles"} if 1 < got["splits"] == -(-got["ntiles"] // got["tpr"]) else set()
+                    seen |= {"brute_max"} if env.get("LRM_OCT_BRUTE") else set()
+                    seen |= {"first_level"} if not env and nc < K["chunked_from"] else set()
+    assert seen >= {"every", "every_cap", "every_below_cap", "brute", "brute_max", "chunked", "deferred", "inline", "grid_cap", "max_splits",
+                    "splits_by_tiles", "first_level", "tpr_1", "tpr_32", "tpr_128", "tpr_256"}, seen
+    # the thresholds themselves, from the library alone: both sides of each
+    plan = lambda nc, nf: lrm.dbg_oct_plan(nc, nf)
+    assert [plan(nc, 4097)["kernel"] for nc in (8, 9)] == ["every", "chunked"]
+    assert [plan(8, nf)["kernel"] for nf in (first_level, first_level + 1)] == ["every", "chunked"]
+    assert [plan(nc, 1 << 20)["tpr"] for nc in (2047, 2048, 8191, 8192)] == [32, 128, 128, 256]
+    assert [plan(nc, 1 << 22)["splits"] for nc in (2047, 2048, 8191, 8192)] == [17, 4, 2, 1]  # ceil(32768 / 2047), 8192 / 2048, ceil(8192 / 8191)
+    assert [plan(nc, 4097)["deferred"] for nc in (255, 256)] == [False, True]
+    with monkeypatch.context() as m:
+        m.setenv("LRM_OCT_BRUTE", "1")
+        assert [plan(nc, 4097)["kernel"] for nc in (65535, 65536)] == ["every", "chunked"]
 
 
 def test_launch_plan_on_the_decider_tree(lrm, oracle):
