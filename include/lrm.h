@@ -1075,6 +1075,87 @@ int lrm_swing_transit_posed_cpu(const float* targets_aos, size_t nt, const float
                                 const uint8_t* live_in /* may be NULL */, uint64_t* mask_out, int32_t* reached_out,
                                 int32_t* first_miss_out, int32_t* worst_out, float* worst_d2_out, int32_t* hits_out, int32_t* hit_seg_out,
                                 int32_t* near_out, float* pen_out, uint8_t* swinging_out, uint8_t* clear_out, double* ms);
+/* STATIC FOOT LOADS AND JOINT TORQUES per set and lift set: can the actuators hold the stance.  lrm_stance_stability_dev says
+ * that the centre of mass lies over the support polygon and lrm_ik_posed_dev gives the joint angles; neither says what every
+ * planted foot carries, nor what the coxa, femur and tibia joints must hold when a leg or a tripod is lifted.  The reference has
+ * no such query.  THE MODEL: contacts are frictionless points; every planted foot pushes along `up` only; THE LEGS ARE MASSLESS
+ * (link weights are ignored: the whole weight acts at the centre of mass); the weight is 1, so loads are fractions of the
+ * robot's weight and torques are load x mm -- the caller multiplies both by m g.  The call reads no cloud and no body position
+ * (the feet are the FK tips relative to the body): `workspace` and `ik_workspace` are the pose table and the IK table of
+ * lrm_self_clearance_posed_dev, and sets, pose_idx, nposes, nlegs and the angles at [l*nsets + s] are that call's; com, plane,
+ * lift, nmasks and live_in are lrm_stance_stability_dev's; quats (nposes x 4) is read for the centre of mass only.  Everything
+ * is float32 without contraction, only + - * /, comparisons, the correctly rounded square root and the sincos of the IK: device
+ * and host give the same bits (csrc/lrm_stance_loads.h is the one source of both).
+ * Leg l of set s: J0..J3 are lrm_leg_clearance_posed_dev's joints with tip_clear = 0; the leg is VALID iff its twelve
+ *   coordinates are finite; its foot is P = J3 (relative to the body) and its plane point f_l is lrm_stance_stability_dev's
+ *   projection of P.  c is that call's centre of mass, and a set is DEAD under that call's rules: live_in[s] == 0, p outside
+ *   [0, nposes), or c not finite.  up = (0, 0, 1) with plane == NULL, else u x v = (u.y v.z - u.z v.y, u.z v.x - u.x v.z,
+ *   u.x v.y - u.y v.x), formed once per call.  xi_l = f_l.x - c.x, eta_l = f_l.y - c.y.
+ * Lever arms: with (sc, cc), (sf, cf), (sa, ca) the sincos of coxa, femur and femur + tibia, C, F, T the link lengths of the
+ *   joints (T = 0 unless T > 0), ts = T sa, tc = T ca, v = F sf + ts, w = F cf + tc, h3 = C + w, the columns of the tip's
+ *   Jacobian in the coxa frame are col_c = (-sc h3, cc h3, 0), col_f = (-cc v, -sc v, w), col_t = (-cc ts, -sc ts, tc) (the
+ *   negation applies to the sine or cosine before the product).  Lin is the coxa-frame-to-caller's-frame chain of the joints
+ *   WITHOUT its translation by body_length (a direction, not a point), and g_j = (up.x a.x + up.y a.y) + up.z a.z with
+ *   a = Lin(col_j): how fast the foot rises along `up` per radian of joint j.  tau_j = load g_j is the moment of the ground
+ *   force about joint j in the angle's positive sense; the actuator holds the opposite.
+ * Loads of lift set m: the planted set is S = valid & ~lift[m].  Three stages, in order:
+ *   ALL (status 1): over the feet of A = S in ascending leg order the six sums n = sum 1, sx = sum xi, sy = sum eta,
+ *     sxx = sum xi xi, sxy = sum xi eta, syy = sum eta eta; c00 = sxx syy - sxy sxy, c01 = sxy sy - sx syy,
+ *     c02 = sx sxy - sxx sy, det = (n c00 + sx c01) + sy c02, which must be > 0 and < inf; alpha = c00 / det, beta = c01 / det,
+ *     gamma = c02 / det; load_i = (alpha + beta xi_i) + gamma eta_i: the minimum-norm solution of sum load = 1,
+ *     sum load xi = 0, sum load eta = 0.  Accepted iff every load >= 0 (a nan is not).
+ *   DROPPED (status 2): while the solve is not accepted, its det passed and A has more than three feet, the foot of A with the
+ *     smallest load leaves A (the first foot of A, replaced by a later one only if that is strictly smaller: ties to the
+ *     smaller leg; a nan is never smaller) and the solve is repeated on A.  Removed feet get load +0.
+ *   TRIPOD (status 3), entered when a det fails or three feet remain with a load not >= 0: every triple i < j < k of S (not
+ *     of A) in lexicographic order; d = (xi_j - xi_i)(eta_k - eta_i) - (xi_k - xi_i)(eta_j - eta_i) must be nonzero and
+ *     finite; l_i = (xi_j eta_k - xi_k eta_j) / d, l_j = (xi_k eta_i - xi_i eta_k) / d, l_k = (xi_i eta_j - xi_j eta_i) / d;
+ *     the triple counts iff all three are >= 0; the triple with the largest minimum wins, the first one on ties; the other
+ *     feet get +0.
+ *   Otherwise -- fewer than three planted feet, or no stage succeeds -- status 4: the feet of S get load and torques nan
+ *     (0x7fc00000).  A dead set has status 0 for every m and no planted foot.
+ *   Statuses 1..3 mean that an equilibrium with non-negative loads exists (by Caratheodory's theorem the tripod stage finds
+ *   one whenever there is one), up to rounding; they do not mean that the loads are the ones a compliant robot settles into.
+ * Outputs, all written:
+ *   status_out, holdable_out (uint8) at [m*nsets + s]: holdable = status in 1..3 and |tau_j| <= tau_max[j] for every planted
+ *             leg and joint; a row of holdable_out is a valid live_in of the other posed calls;
+ *   peak_out    (float) at [m*nsets + s]: with status 1..3 the largest |tau_j| / tau_max[j] over the planted legs, else -inf;
+ *   peak_at_out (uint8, may be NULL) its code l*4 + j, ties to the smaller code (a nan ratio never wins), 255 with -inf;
+ *   load_out    (float, may be NULL) at [(m*nlegs + l)*nsets + s];
+ *   tau_out     (float, may be NULL) at [((m*nlegs + l)*3 + j)*nsets + s].
+ *   Lifted and invalid legs get load +0 and tau +0; a stored -0 is +0 and a stored nan is 0x7fc00000.
+ * tau_max: host float[3] (coxa, femur, tibia), each > 0, +inf allowed (that joint never limits: its ratio is 0, or nan for an
+ * infinite torque).
+ * Checked first, in this order (all LRM_EINVAL): nlegs outside 1..LRM_MAX_LEGS; nmasks outside 1..256; nposes or nsets >
+ * INT32_MAX; nmasks * nlegs * 3 * nsets past 2^32 - 1; NULL lift; a lift bit at or above nlegs; NULL tau_max, or an entry that
+ * is nan or <= 0; a non-finite com or plane value; pose_idx == NULL with nsets > nposes.  Then nsets == 0 is a no-op; a NULL
+ * table, quats, angle array, status_out, holdable_out or peak_out gives LRM_EINVAL.
+ * lrm_stance_loads_posed_dev: ONE launch (with up to eight lift sets a lane per set, from nine on a wave per set and a lane per
+ * lift set; the same functions and the same bits either way): no allocation, no host synchronisation, no
+ * atomics, no shared buffer -- it can be captured in a graph and may run concurrently with anything, from any host thread.
+ * Bit-deterministic.
+ * lrm_stance_loads_posed_cpu: host quats, legs and angles_aos (nlegs * nsets triples {coxa, femur, tibia} at [l*nsets + s]);
+ * it compiles its own tables and runs a serial loop over every (set, lift set) with the same functions: the reference the GPU
+ * tests compare with bit for bit; *ms = the loop's time.
+ * Chain: ... -> ik -> stance_loads -> stance_stability / self_clearance(live_in = a holdable row). */
+#define LRM_LOADS_DEAD 0
+#define LRM_LOADS_ALL 1
+#define LRM_LOADS_DROPPED 2
+#define LRM_LOADS_TRIPOD 3
+#define LRM_LOADS_NONE 4
+int lrm_stance_loads_posed_dev(const void* workspace, const void* ik_workspace, const float* quats /* device, nposes x 4 */,
+                               size_t nposes, size_t nlegs, const int32_t* pose_idx /* device, nsets, may be NULL */, size_t nsets,
+                               const float* coxa, const float* femur, const float* tibia /* device, nlegs*nsets at [l*nsets + s] */,
+                               const float* com /* host, 3, may be NULL */, const float* plane /* host, 6, may be NULL */,
+                               const uint8_t* lift /* host, nmasks */, size_t nmasks, const float* tau_max /* host, 3 */,
+                               const uint8_t* live_in /* device, nsets, may be NULL */, uint8_t* status_out, uint8_t* holdable_out,
+                               float* peak_out, uint8_t* peak_at_out /* may be NULL */, float* load_out /* may be NULL */,
+                               float* tau_out /* may be NULL */, void* stream);
+int lrm_stance_loads_posed_cpu(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs,
+                               const int32_t* pose_idx /* host, may be NULL */, size_t nsets, const float* angles_aos,
+                               const float* com, const float* plane, const uint8_t* lift, size_t nmasks, const float* tau_max,
+                               const uint8_t* live_in /* host, may be NULL */, uint8_t* status_out, uint8_t* holdable_out,
+                               float* peak_out, uint8_t* peak_at_out, float* load_out, float* tau_out, double* ms);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

@@ -707,6 +707,57 @@ def self_clearance_posed_cpu(quats, legs, angles, radius, margin=0.0, tip_clear=
     return hits, with_, links, worst, pen, free, ms.value
 
 
+def _tau_max(tau_max):
+    tau_max = _f32(tau_max).reshape(-1)
+    if len(tau_max) != 3:
+        raise ValueError("tau_max: three values (coxa, femur, tibia joint), each > 0, inf allowed")
+    return tau_max
+
+
+LOADS_DEAD, LOADS_ALL, LOADS_DROPPED, LOADS_TRIPOD, LOADS_NONE = range(5)
+
+
+def stance_loads_posed_cpu(quats, legs, angles, tau_max, pose_idx=None, com=None, plane=None, lift=None, live_in=None,
+                           want_peak_at=True, want_load=True, want_tau=True):
+    """lrm_stance_loads_posed_cpu: what every planted foot carries and what the joints must hold.  A set s is a pose
+    (pose_idx[s], or pose s with pose_idx None) and one (coxa, femur, tibia) triple per leg, angles float32 [nlegs*nsets, 3]
+    at [l*nsets + s]: apply_ik_posed_cpu's output in that layout.  Frictionless point contacts pushing along `up` (the normal
+    of `plane`, None: +z), massless legs, weight 1: loads are fractions of the weight, torques load x mm.  com, plane and lift
+    are stance_stability_cpu's; tau_max: three limits (coxa, femur, tibia; > 0, inf allowed) in the torques' unit.  Per
+    (lift set, set): status (LOADS_DEAD, _ALL, _DROPPED, _TRIPOD, _NONE), holdable = status 1..3 and every |tau| <= tau_max,
+    peak = the largest |tau| / tau_max (-inf if none), peak_at = its code l*4 + j (255 if none); per (lift set, leg, set) the
+    load; per (lift set, leg, joint, set) the torque.  live_in: uint8[nsets] or None; 0 = dead, as is a pose index outside the
+    poses.  Serial host loop; want_* False pass NULL.
+    -> (status uint8[nmasks, nsets], holdable uint8[nmasks, nsets], peak float32[nmasks, nsets], peak_at uint8[nmasks, nsets] or
+    None, load float32[nmasks, nlegs, nsets] or None, tau float32[nmasks, nlegs, 3, nsets] or None, ms)"""
+    quats = _f32(quats, (-1, 4))
+    legs = _f32(legs, (-1, 14))
+    n, nl = len(quats), len(legs)
+    angles = _f32(angles)
+    if nl == 0 or angles.size % (3 * nl):
+        raise ValueError("angles: one (coxa, femur, tibia) triple per (leg, set), at [l*nsets + s]")
+    ns = angles.size // (3 * nl)
+    angles = angles.reshape(nl * ns, 3)
+    if pose_idx is not None:
+        pose_idx = np.ascontiguousarray(pose_idx, np.int32).reshape(-1)
+        if len(pose_idx) != ns:
+            raise ValueError("pose_idx: one pose per set")
+    live_in = _u8_per(live_in, ns, "live_in: one byte per set")
+    com, plane = _stance_host(com, plane)
+    lift = stance_lift(lift, nl)
+    tau_max = _tau_max(tau_max)
+    nm = len(lift)
+    status, holdable, peak = np.zeros((nm, ns), np.uint8), np.zeros((nm, ns), np.uint8), np.zeros((nm, ns), np.float32)
+    peak_at = np.zeros((nm, ns), np.uint8) if want_peak_at else None
+    load = np.zeros((nm, nl, ns), np.float32) if want_load else None
+    tau = np.zeros((nm, nl, 3, ns), np.float32) if want_tau else None
+    ms = C.c_double(0)
+    check(lib().lrm_stance_loads_posed_cpu(_ptr(quats), n, _ptr(legs), nl, _ptr(pose_idx), ns, _ptr(angles), _ptr(com), _ptr(plane),
+                                                _ptr(lift), nm, _ptr(tau_max), _ptr(live_in), _ptr(status), _ptr(holdable), _ptr(peak),
+                                                _ptr(peak_at), _ptr(load), _ptr(tau), C.addressof(ms)))
+    return status, holdable, peak, peak_at, load, tau, ms.value
+
+
 def _links_mask(links):
     links = int(links)
     if not 0 <= links <= 255:

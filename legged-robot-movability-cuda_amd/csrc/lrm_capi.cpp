@@ -27,6 +27,7 @@
 #include "lrm_trunk_clearance.h"
 #include "lrm_edge_transit.h"
 #include "lrm_swing.h"
+#include "lrm_stance_loads.h"
 #include "lrm_ik.h"
 #include "lrm_dbg_math.h"
 #include "lrm_launch.h"
@@ -2546,6 +2547,111 @@ int lrm_swing_transit_posed_cpu(const float* targets, size_t nt, const float* qu
         }
         if (swinging_out) swinging_out[e] = (uint8_t)swing_bits;
         if (clear_out) clear_out[e] = clear;
+    }
+    return LRM_OK;
+}
+
+// ---- static foot loads and joint torques per set and lift set (lrm_stance_loads.hip) -----------
+namespace {
+// every range and scalar check in the documented order, before any early return; fills *P
+int stance_loads_args(size_t nposes, size_t nlegs, const int32_t* pose_idx, size_t nsets, const float* com, const float* plane,
+                      const uint8_t* lift, size_t nmasks, const float* tau_max, LrmLoadsParams* P) {
+    if (nlegs < 1 || nlegs > LRM_MAX_LEGS) return fail(LRM_EINVAL, "stance loads: nlegs must be 1..LRM_MAX_LEGS");
+    if (nmasks < 1 || nmasks > LRM_STANCE_MAX_MASKS) return fail(LRM_EINVAL, "stance loads: nmasks must be 1..256");
+    if (nposes > (size_t)INT32_MAX || nsets > (size_t)INT32_MAX)
+        return fail(LRM_EINVAL, "stance loads: nposes and nsets must not exceed INT32_MAX");
+    if ((uint64_t)nmasks * (uint64_t)nlegs * 3ull * (uint64_t)nsets > 0xffffffffull)
+        return fail(LRM_EINVAL, "stance loads: more than 2^32 - 1 (lift set, leg, joint, set) answers");
+    if (!lift) return fail(LRM_EINVAL, "null argument");
+    for (size_t m = 0; m < nmasks; m++)
+        if (lift[m] >> nlegs) return fail(LRM_EINVAL, "stance loads: a lift set names a leg at or above nlegs");
+    if (!tau_max) return fail(LRM_EINVAL, "null argument");
+    for (int k = 0; k < 3; k++)
+        if (!(tau_max[k] > 0.f)) return fail(LRM_EINVAL, "stance loads: tau_max must be > 0 (+inf allowed)");
+    for (int k = 0; k < 3; k++)
+        if (com && !lrm_stance_finite(com[k])) return fail(LRM_EINVAL, "stance loads: com must be finite");
+    for (int k = 0; k < 6; k++)
+        if (plane && !lrm_stance_finite(plane[k])) return fail(LRM_EINVAL, "stance loads: plane must be finite");
+    if (!pose_idx && nsets > nposes) return fail(LRM_EINVAL, "stance loads: without pose_idx, set s takes pose s: nsets <= nposes");
+    *P = LrmLoadsParams{};
+    for (int k = 0; k < 3; k++) {
+        P->S.com[k] = com ? com[k] : 0.f;
+        P->S.u[k] = plane ? plane[k] : 0.f;
+        P->S.v[k] = plane ? plane[3 + k] : 0.f;
+        P->tau_max[k] = tau_max[k];
+    }
+    P->S.on = plane ? 1u : 0u;
+    P->S.nmasks = (uint32_t)nmasks;
+    for (size_t m = 0; m < nmasks; m++) P->S.lift[m] = lift[m];
+    lrm_loads_up(P->S, P->up);
+    return LRM_OK;
+}
+} // namespace
+
+int lrm_stance_loads_posed_dev(const void* workspace, const void* ik_workspace, const float* quats, size_t nposes, size_t nlegs,
+                               const int32_t* pose_idx, size_t nsets, const float* coxa, const float* femur, const float* tibia,
+                               const float* com, const float* plane, const uint8_t* lift, size_t nmasks, const float* tau_max,
+                               const uint8_t* live_in, uint8_t* status_out, uint8_t* holdable_out, float* peak_out, uint8_t* peak_at_out,
+                               float* load_out, float* tau_out, void* stream) {
+    LrmLoadsParams P;
+    const int rc = stance_loads_args(nposes, nlegs, pose_idx, nsets, com, plane, lift, nmasks, tau_max, &P);
+    if (rc != LRM_OK) return rc;
+    if (nsets == 0) return LRM_OK;
+    if (!workspace || !ik_workspace || !quats || !coxa || !femur || !tibia || !status_out || !holdable_out || !peak_out)
+        return fail(LRM_EINVAL, "null argument");
+    if (((uintptr_t)workspace | (uintptr_t)ik_workspace) & 15) return fail(LRM_EINVAL, "posed ik: the workspaces must be 16-byte aligned");
+    HIP_TRY(lrm_launch_stance_loads_posed(workspace, ik_workspace, quats, nposes, nlegs, pose_idx, nsets, coxa, femur, tibia, P, live_in,
+                                          status_out, holdable_out, peak_out, peak_at_out, load_out, tau_out, (hipStream_t)stream),
+            "posed stance loads launch");
+    return LRM_OK;
+}
+
+int lrm_stance_loads_posed_cpu(const float* quats, size_t nposes, const LrmLegDimensions* legs, size_t nlegs, const int32_t* pose_idx,
+                               size_t nsets, const float* angles, const float* com, const float* plane, const uint8_t* lift,
+                               size_t nmasks, const float* tau_max, const uint8_t* live_in, uint8_t* status_out, uint8_t* holdable_out,
+                               float* peak_out, uint8_t* peak_at_out, float* load_out, float* tau_out, double* ms) {
+    LrmLoadsParams P;
+    const int rc = stance_loads_args(nposes, nlegs, pose_idx, nsets, com, plane, lift, nmasks, tau_max, &P);
+    if (rc != LRM_OK) return rc;
+    if (nsets == 0) return LRM_OK;
+    if (!legs || (nposes && !quats) || !angles || !status_out || !holdable_out || !peak_out) return fail(LRM_EINVAL, "null argument");
+    std::vector<LrmPoseRecord> recs(nposes * nlegs);
+    std::vector<LrmIkLeg> iks(nposes * nlegs);
+    host_pose_records(quats, nullptr, nposes, legs, nlegs, recs.data()); // the body position is not read
+    host_pose_ik_records(quats, nposes, legs, nlegs, iks.data());
+    const ScopeMs timer{ms};
+    for (size_t s = 0; s < nsets; s++) {
+        const int64_t p = pose_idx ? (int64_t)pose_idx[s] : (int64_t)s;
+        bool live = !(live_in && !live_in[s]) && p >= 0 && (uint64_t)p < nposes;
+        LrmStancePt c{0.f, 0.f};
+        if (live) c = lrm_stance_com(P.S, quats + 4 * p, &live);
+        float xi[8] = {}, eta[8] = {}, g[8][3] = {};
+        uint32_t feet = 0u;
+        for (size_t l = 0; live && l < nlegs; l++) { // the joints and the lever arms once per (set, leg)
+            const size_t o = l * nsets + s;
+            LrmLoadsLeg A;
+            if (!lrm_loads_leg(P, reinterpret_cast<const LrmCompiledLeg&>(recs[p * nlegs + l].head), iks[p * nlegs + l], c, angles[3 * o],
+                               angles[3 * o + 1], angles[3 * o + 2], &A))
+                continue;
+            xi[l] = A.xi, eta[l] = A.eta;
+            for (int j = 0; j < 3; j++) g[l][j] = A.g[j];
+            feet |= 1u << l;
+        }
+        for (size_t m = 0; m < nmasks; m++) { // every (set, lift set)
+            const uint32_t S = lrm_stance_planted(feet, P.S.lift[m]);
+            float load[8] = {}, load_o[8], tau_o[8][3];
+            const uint8_t st = live ? lrm_loads_solve(xi, eta, S, load) : (uint8_t)LRM_LOADS_DEAD;
+            const LrmLoadsPeak Q = lrm_loads_answer(P.tau_max, S, st, load, g, load_o, tau_o);
+            const size_t o = m * nsets + s;
+            status_out[o] = st;
+            holdable_out[o] = Q.holdable;
+            peak_out[o] = Q.peak;
+            if (peak_at_out) peak_at_out[o] = Q.at;
+            for (size_t l = 0; l < nlegs; l++) {
+                if (load_out) load_out[(m * nlegs + l) * nsets + s] = load_o[l];
+                for (size_t j = 0; tau_out && j < 3; j++) tau_out[((m * nlegs + l) * 3 + j) * nsets + s] = tau_o[l][j];
+            }
+        }
     }
     return LRM_OK;
 }

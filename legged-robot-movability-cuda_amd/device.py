@@ -412,6 +412,57 @@ def stance_stability(tx, ty, tz, foot, quats, body=None, pose_idx=None, com=None
     return margin, edge, stable, feet
 
 
+def stance_loads(workspace, ik_workspace, quats, nlegs, angles, tau_max, pose_idx=None, com=None, plane=None, lift=None, live_in=None,
+                 status=None, holdable=None, peak=None, peak_at=None, load=None, tau=None, want_peak_at=True, want_load=True,
+                 want_tau=True):
+    """lrm_stance_loads_posed_dev: what every planted foot carries and what the coxa, femur and tibia joints must hold, for
+    every set and lift set.  workspace / ik_workspace: a PoseSet's pose and IK tables (uint8 tensors) compiled from quats
+    float32 (nposes, 4) by update(); a set s is a pose (pose_idx[s], int32 on the device; None: pose s) and one angle triple per
+    leg: angles is ik()'s (3, nlegs*nsets) tensor, entry l*nsets + s.  The model: frictionless point contacts that push along
+    `up` (the normal u x v of plane, None: +z), massless legs, weight 1 -- loads are fractions of the robot's weight, torques
+    load x mm.  com, plane and lift are stance_stability()'s; tau_max: three host floats (coxa, femur, tibia; > 0, inf allowed).
+    status[m, s]: 0 dead set, 1 all planted feet carry, 2 some were dropped, 3 a tripod carries, 4 no equilibrium (loads and
+    torques nan); holdable[m, s] = status 1..3 and every |tau| <= tau_max; peak[m, s] = the largest |tau| / tau_max (-inf if
+    none); peak_at[m, s] = its code l*4 + j (255 if none); load[m, l, s]; tau[m, l, j, s].  Lifted legs and legs with nan
+    angles get load 0 and tau 0.  live_in: uint8 [nsets] on the device, 0 = dead.
+    -> (status uint8, holdable uint8, peak float32, peak_at uint8 or None, each [nmasks, nsets]; load float32 [nmasks, nlegs,
+    nsets] or None; tau float32 [nmasks, nlegs, 3, nsets] or None); want_* False (and no tensor given) pass NULL.  Every tensor
+    must be contiguous.  holdable[m] is directly the live_in of the other posed calls.  One launch, no allocation beyond missing
+    outputs, no shared buffer: it can be captured in a graph and may run next to anything."""
+    torch = _torch()
+    nposes = _check_poses(quats, None)
+    nl = int(nlegs)
+    if not 1 <= nl <= 8:
+        raise ValueError("nlegs: 1 to 8 legs")
+    for ws, per, what in ((workspace, _capi.POSE_RECORD_BYTES, "workspace"), (ik_workspace, _capi.POSE_IK_RECORD_BYTES, "ik_workspace")):
+        if ws is None or not (ws.is_cuda and ws.device == quats.device and ws.dtype == torch.uint8 and ws.is_contiguous()
+                              and ws.numel() >= per * nposes * nl):
+            raise ValueError(f"{what}: expected a contiguous uint8 tensor of >= {per} * nposes * nlegs bytes on the poses' device")
+    if not (angles.is_cuda and angles.device == quats.device and angles.dtype == torch.float32 and angles.dim() == 2
+            and angles.shape[0] == 3 and angles.shape[1] % nl == 0 and angles.is_contiguous()):
+        raise ValueError(f"angles: expected ik()'s contiguous float32 (3, {nl} * nsets) tensor on {quats.device}")
+    ns = angles.shape[1] // nl
+    _check_in(pose_idx, quats, torch.int32, ns, "pose_idx")
+    _check_in(live_in, quats, torch.uint8, ns, "live_in")
+    _one_per(ns, "pose_idx / live_in: one entry per set", pose_idx, live_in)
+    if pose_idx is None and ns > nposes:
+        raise ValueError("without pose_idx set s takes pose s: nsets <= nposes")
+    com, plane = _capi._stance_host(com, plane)
+    lift = _capi.stance_lift(lift, nl)
+    tau_max = _capi._tau_max(tau_max)
+    nm = len(lift)
+    status = _out(status, quats, (nm, ns), torch.uint8, "status bytes")
+    holdable = _out(holdable, quats, (nm, ns), torch.uint8, "holdable bytes")
+    peak = _out(peak, quats, (nm, ns), torch.float32, "peak ratios")
+    peak_at = _out(peak_at, quats, (nm, ns), torch.uint8, "peak codes", want_peak_at)
+    load = _out(load, quats, (nm, nl, ns), torch.float32, "loads", want_load)
+    tau = _out(tau, quats, (nm, nl, 3, ns), torch.float32, "torques", want_tau)
+    _launch("lrm_stance_loads_posed_dev", quats, _dp(workspace), _dp(ik_workspace), _dp(quats), nposes, nl, _dp(pose_idx), ns,
+            _dp(angles[0]), _dp(angles[1]), _dp(angles[2]), _capi._ptr(com), _capi._ptr(plane), _capi._ptr(lift), nm, _capi._ptr(tau_max),
+            _dp(live_in), _dp(status), _dp(holdable), _dp(peak), _dp(peak_at), _dp(load), _dp(tau))
+    return status, holdable, peak, peak_at, load, tau
+
+
 def edge_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot, nsamples=9, live_in=None, mask=None, reached=None,
                  first_miss=None, worst=None, worst_d2=None, planted=None, clear=None, advance=None):
     """lrm_edge_transit_posed_dev: does a planted foot stay reachable while the body moves from pose edge_a[e] to pose edge_b[e].
@@ -941,6 +992,20 @@ class PoseSet:
                 _dp(angles[0]), _dp(angles[1]), _dp(angles[2]), _capi._ptr(radius), float(margin), float(tip_clear), _dp(live_in),
                 _dp(hits), _dp(with_), _dp(links), _dp(worst), _dp(pen), _dp(free))
         return hits, with_, links, worst, pen, free
+
+    def stance_loads(self, angles, quats, tau_max, pose_idx=None, com=None, plane=None, lift=None, live_in=None, status=None,
+                     holdable=None, peak=None, peak_at=None, load=None, tau=None, want_peak_at=True, want_load=True, want_tau=True):
+        """device.stance_loads() on this set's tables (built with ik=True): quats is the tensor of the last update() -- the set
+        keeps compiled records, not the poses, and the centre of mass needs the quaternion -- so its pose count must be the
+        set's.  angles: ik()'s (3, nlegs*nsets) tensor, entry l*nsets + s, under footholds_layout a set per pose, under
+        foothold_edges_layout a set per edge with pose_idx = edge_a or edge_b.
+        -> (status, holdable, peak, peak_at [nmasks, nsets]; load [nmasks, nlegs, nsets]; tau [nmasks, nlegs, 3, nsets]);
+        holdable[m] is the live_in of stance_stability(), self_clearance() and the other posed calls.  It only launches:
+        update -> footholds -> ik -> stance_loads -> stance_stability(live_in = holdable[0]) can be captured in a graph."""
+        self._need("ik")
+        self._last_update(quats)
+        return stance_loads(self.workspace, self.ik_workspace, quats, self.nlegs, angles, tau_max, pose_idx, com, plane, lift, live_in,
+                            status, holdable, peak, peak_at, load, tau, want_peak_at, want_load, want_tau)
 
     def trunk_clearance(self, angles, radius, trunk_radius, plus_z, minus_z, margin=0.0, tip_clear=0.0, links=0b110, pose_idx=None,
                         live_in=None, hit=None, worst=None, pen=None, free=None):
