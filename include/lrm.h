@@ -1156,6 +1156,68 @@ int lrm_stance_loads_posed_cpu(const float* quats, size_t nposes, const LrmLegDi
                                const float* com, const float* plane, const uint8_t* lift, size_t nmasks, const float* tau_max,
                                const uint8_t* live_in /* host, may be NULL */, uint8_t* status_out, uint8_t* holdable_out,
                                float* peak_out, uint8_t* peak_at_out, float* load_out, float* tau_out, double* ms);
+
+/* ---- pose-graph routes: cost, hops and predecessor per pose ------------------------------------------------------------
+ * New capability: every posed call ends in a byte per pose (all_legs, free, stable, holdable) or per transition (all_legs of
+ * lrm_foothold_edges_posed_dev, clear of the transit calls); this call composes them into the answer: which poses the robot
+ * can get to from where it stands, in how many steps and at what cost, and through which transition it arrives.  Single- or
+ * multi-source shortest routes over the caller's pose graph with INTEGER costs; the answer is bit-deterministic and the same
+ * on device and host (csrc/lrm_pose_routes.h is the one source of both).  The reference has no such query.
+ * Inputs (device pointers for _dev, host pointers for _cpu):
+ *   nposes;  edge_a, edge_b (int32, nedges): the arrays the edge calls take;
+ *   edge_live (uint8, nedges, may be NULL): a clear or all_legs byte as it stands, 0 = dead;
+ *   pose_live (uint8, nposes, may be NULL): a free, stable or holdable row, 0 = dead;
+ *   edge_cost (int32, nedges, may be NULL = 1 for every edge, so that cost equals hops); a negative cost makes the edge dead;
+ *   sources (int32, nsources);
+ *   direction: 0 an edge serves both ways; 1 a -> b only; 2 b -> a only (with the goal as source: the cost-to-go field and
+ *     the next edge towards the goal).
+ * USABLE: edge e is usable iff it is live, both ends lie in [0, nposes), both ends are live poses and its cost is >= 0.
+ * SOURCE: a pose named in sources is a source iff it is in range and live; duplicates, dead and out-of-range entries are
+ *   ignored.
+ * KEY of pose v: the lexicographic minimum of (sum of costs, number of arcs) over all walks from a source along arcs of usable
+ *   edges whose sum of costs is <= 4 294 967 294.  Costs are integers, so addition is exact, every prefix of a minimal walk is
+ *   minimal, and the key is the unique least fixed point of key[v] = min(key[v], key[u] + (w_e, 1)) -- the same in whatever
+ *   order the relaxations happen.  Zero-cost cycles and self-loops never lower a key: the arc count is the tie-break.
+ * Outputs per pose, all written (each of the four may be NULL, but not all of them):
+ *   cost_out      (int64) the sum of costs, -1 if unreachable;
+ *   hops_out      (int32) the number of arcs, -1 if unreachable;
+ *   pred_edge_out (int32) the smallest usable e that has an arc u -> v with key[u] + (w_e, 1) == key[v]; -1 for a source and
+ *                 for an unreachable pose;
+ *   pred_pose_out (int32) that arc's u, or -1.  Following pred_pose from any reached pose ends at a source after exactly
+ *                 hops steps.
+ * Outputs per call: reached_out (int32[1], may be NULL) the number of poses with hops >= 0; done_out (int32[1], _dev only, may
+ *   be NULL): >= 1 when the fixed point was proven within `rounds` relaxation launches (the number of launches that did work;
+ *   only its sign is a contract), -1 otherwise.  With -1 the per-pose outputs are written and memory-safe but unspecified,
+ *   and the workspace holds the state: a further call with resume = 1 and otherwise equal arguments continues from it.  The
+ *   fixed point is unique, so the final answer is the same bits however the work was cut.
+ * lrm_pose_routes_dev further takes workspace (device, lrm_pose_routes_workspace_bytes(nposes, rounds) bytes, 8-byte aligned:
+ *   the 64-bit keys and one flag per launch), rounds (1..4096), resume (0 or 1) and the stream.  It launches init, seed,
+ *   `rounds` relax launches and up to three finish launches back to back: no allocation, no host synchronisation, no wait of
+ *   one workgroup for another (no grid barrier, no cooperative launch, no loop on memory) -- it can be captured in a graph as
+ *   one linear chain.  Relax launch i returns at once when launch i - 1 changed nothing.  Calls on different streams need
+ *   different workspaces and outputs.  All atomics are integer min / add.
+ * Checked first, in this order (all LRM_EINVAL): direction outside 0..2; rounds outside 1..4096; resume outside 0..1; nposes,
+ *   nedges or nsources > INT32_MAX.  Then nposes == 0 is a no-op that still writes reached_out = 0 and done_out = 1.  Then
+ *   NULL (or misaligned) workspace; NULL edge_a or edge_b with nedges > 0; NULL sources with nsources > 0; all four per-pose
+ *   outputs NULL give LRM_EINVAL.  nedges == 0 and nsources == 0 are valid: only the sources, or nothing, are reached.  Any
+ *   contents of edge_a, edge_b and sources are safe: an index is checked before an address is formed from it.
+ * lrm_pose_routes_cpu: the same without workspace, rounds, resume and done_out; it always finishes: a binary-heap Dijkstra on
+ *   the keys over a counting-sorted arc list, then the predecessor by the rule above in a loop over the edges: the reference
+ *   the GPU tests compare with bit for bit; *ms = its time.
+ * lrm_dbg_pose_routes_plan: the launch arithmetic of a relax launch on nedges edges, from the function the launch itself
+ *   consumes (host only): out = {edges per workgroup C, grid cap G, sweeps per launch K, workgroups launched}.
+ * Chain: ... -> foothold_edges -> edge_transit -> swing_transit -> routes(edge_live = clear, pose_live = all_legs). */
+size_t lrm_pose_routes_workspace_bytes(size_t nposes, size_t rounds);
+int lrm_pose_routes_dev(size_t nposes, const int32_t* edge_a, const int32_t* edge_b, size_t nedges,
+                        const uint8_t* edge_live /* may be NULL */, const uint8_t* pose_live /* may be NULL */,
+                        const int32_t* edge_cost /* may be NULL */, const int32_t* sources, size_t nsources, int direction,
+                        void* workspace, size_t rounds, int resume, int64_t* cost_out, int32_t* hops_out, int32_t* pred_edge_out,
+                        int32_t* pred_pose_out, int32_t* reached_out, int32_t* done_out, void* stream);
+int lrm_pose_routes_cpu(size_t nposes, const int32_t* edge_a, const int32_t* edge_b, size_t nedges, const uint8_t* edge_live,
+                        const uint8_t* pose_live, const int32_t* edge_cost, const int32_t* sources, size_t nsources, int direction,
+                        int64_t* cost_out, int32_t* hops_out, int32_t* pred_edge_out, int32_t* pred_pose_out, int32_t* reached_out,
+                        double* ms);
+int lrm_dbg_pose_routes_plan(size_t nedges, uint64_t out[4]);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

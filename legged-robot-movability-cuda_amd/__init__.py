@@ -19,8 +19,9 @@ from ._capi import (  # noqa: F401
     leg_clearance_posed_cpu, leg_joints_posed_cpu,
     stance_stability_cpu, stance_lift,
     stance_loads_posed_cpu, LOADS_DEAD, LOADS_ALL, LOADS_DROPPED, LOADS_TRIPOD, LOADS_NONE,
+    pose_routes_cpu, dbg_pose_routes_plan,
     self_clearance_posed_cpu, trunk_clearance_posed_cpu, edge_transit_posed_cpu, swing_transit_posed_cpu, dbg_link_pair_dist_host, dbg_trunk_link_dist_host, dbg_edge_transit_samples_host,
 )
 from . import device  # noqa: F401
-from .device import PoseSet, ik, fk, edge_transit, swing_transit, stance_loads, swing_layout, foothold_offsets, foothold_edges_layout, foothold_support_layout, dbg_link_pair_dist, dbg_trunk_link_dist, dbg_edge_transit_samples  # noqa: F401
+from .device import PoseSet, ik, fk, edge_transit, swing_transit, stance_loads, pose_routes, route_path, swing_layout, foothold_offsets, foothold_edges_layout, foothold_support_layout, dbg_link_pair_dist, dbg_trunk_link_dist, dbg_edge_transit_samples  # noqa: F401
 from . import shard  # noqa: F401

@@ -98,7 +98,7 @@ def load():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_", "lrm_edge_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_", "lrm_edge_", "lrm_pose_routes_"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes, fn.restype = argtypes, restype
@@ -842,6 +842,52 @@ def edge_transit_posed_cpu(targets, quats, body, legs, edge_a, edge_b, foot, nsa
                                             _ptr(reached), _ptr(first_miss), _ptr(worst), _ptr(worst_d2), _ptr(planted), _ptr(clear),
                                             _ptr(advance), C.addressof(ms)))
     return mask, reached, first_miss, worst, worst_d2, planted, clear, advance, ms.value
+
+
+def _routes_host(nposes, edge_a, edge_b, sources, edge_live, pose_live, edge_cost):
+    """the host inputs of pose_routes_cpu -> (nposes, edge_a, edge_b, sources, edge_live, pose_live, edge_cost)"""
+    nposes = int(nposes)
+    edge_a, edge_b = _edges(edge_a, edge_b)
+    ne = len(edge_a)
+    sources = np.ascontiguousarray(sources, np.int32).reshape(-1)
+    edge_live = _u8_per(edge_live, ne, "edge_live: one byte per edge")
+    pose_live = _u8_per(pose_live, nposes, "pose_live: one byte per pose")
+    if edge_cost is not None:
+        edge_cost = np.ascontiguousarray(edge_cost, np.int32).reshape(-1)
+        if len(edge_cost) != ne:
+            raise ValueError("edge_cost: one int32 per edge")
+    return nposes, edge_a, edge_b, sources, edge_live, pose_live, edge_cost
+
+
+def pose_routes_cpu(nposes, edge_a, edge_b, sources, edge_live=None, pose_live=None, edge_cost=None, direction=0, want_cost=True,
+                    want_hops=True, want_pred_edge=True, want_pred_pose=True):
+    """lrm_pose_routes_cpu: shortest routes over the pose graph with integer costs, from the poses in `sources`.  edge_a / edge_b
+    int32 [nedges]; edge_live uint8 [nedges] and pose_live uint8 [nposes] or None (0 = dead); edge_cost int32 [nedges] or None
+    (1 per edge: cost equals hops; a negative cost makes the edge dead); direction 0 both ways, 1 a -> b, 2 b -> a.  An edge is
+    usable iff it is live, both ends are live poses in range and its cost is >= 0; a source counts iff it is in range and live.
+    The key of a pose is the lexicographic minimum of (sum of costs, number of arcs) over the walks from a source whose sum of
+    costs is <= 4 294 967 294.  cost (-1 unreachable), hops (-1 unreachable), pred_edge (the smallest usable edge with a tight
+    arc into the pose; -1 for a source or an unreachable pose), pred_pose (that arc's tail, or -1).  A binary-heap Dijkstra;
+    want_* False pass NULL (not all four).  -> (cost int64, hops int32, pred_edge int32, pred_pose int32, each [nposes] or None;
+    reached int; ms)"""
+    nposes, edge_a, edge_b, sources, edge_live, pose_live, edge_cost = _routes_host(nposes, edge_a, edge_b, sources, edge_live, pose_live,
+                                                                                    edge_cost)
+    cost = np.zeros(nposes, np.int64) if want_cost else None
+    hops = np.zeros(nposes, np.int32) if want_hops else None
+    pred_edge = np.zeros(nposes, np.int32) if want_pred_edge else None
+    pred_pose = np.zeros(nposes, np.int32) if want_pred_pose else None
+    reached, ms = C.c_int32(0), C.c_double(0)
+    check(load().lrm_pose_routes_cpu(nposes, _ptr(edge_a), _ptr(edge_b), len(edge_a), _ptr(edge_live), _ptr(pose_live), _ptr(edge_cost),
+                                     _ptr(sources), len(sources), int(direction), _ptr(cost), _ptr(hops), _ptr(pred_edge), _ptr(pred_pose),
+                                     C.addressof(reached), C.addressof(ms)))
+    return cost, hops, pred_edge, pred_pose, int(reached.value), ms.value
+
+
+def dbg_pose_routes_plan(nedges):
+    """lrm_dbg_pose_routes_plan: the launch arithmetic of a relax launch of lrm_pose_routes_dev on nedges edges.  Host only."""
+    out = np.zeros(4, np.uint64)
+    check(load().lrm_dbg_pose_routes_plan(int(nedges), _ptr(out)))
+    return dict(zip(("chunk", "grid_cap", "sweeps", "workgroups"), (int(v) for v in out)))
 
 
 def _swing_scalars(lift, up, foot_radius, margin, skip):

@@ -28,6 +28,7 @@
 #include "lrm_edge_transit.h"
 #include "lrm_swing.h"
 #include "lrm_stance_loads.h"
+#include "lrm_pose_routes.h"
 #include "lrm_ik.h"
 #include "lrm_dbg_math.h"
 #include "lrm_launch.h"
@@ -2652,6 +2653,138 @@ int lrm_stance_loads_posed_cpu(const float* quats, size_t nposes, const LrmLegDi
                 for (size_t j = 0; tau_out && j < 3; j++) tau_out[((m * nlegs + l) * 3 + j) * nsets + s] = tau_o[l][j];
             }
         }
+    }
+    return LRM_OK;
+}
+
+// ---- pose-graph routes: cost, hops and predecessor per pose (lrm_pose_routes.hip) -----------
+namespace {
+// the refusals both forms share, in the documented order (rounds and resume are the device form's: the host form passes 1, 0)
+int pose_routes_ranges(int direction, size_t rounds, int resume, size_t nposes, size_t nedges, size_t nsources) {
+    if (direction < 0 || direction > 2) return fail(LRM_EINVAL, "pose routes: direction must be 0 (both ways), 1 (a to b) or 2 (b to a)");
+    if (rounds < 1 || rounds > LRM_ROUTES_MAX_ROUNDS) return fail(LRM_EINVAL, "pose routes: rounds must be 1..4096");
+    if (resume < 0 || resume > 1) return fail(LRM_EINVAL, "pose routes: resume must be 0 or 1");
+    if (nposes > (size_t)INT32_MAX || nedges > (size_t)INT32_MAX || nsources > (size_t)INT32_MAX)
+        return fail(LRM_EINVAL, "pose routes: nposes, nedges and nsources must not exceed INT32_MAX");
+    return LRM_OK;
+}
+int pose_routes_pointers(const int32_t* edge_a, const int32_t* edge_b, size_t nedges, const int32_t* sources, size_t nsources,
+                         const int64_t* cost_out, const int32_t* hops_out, const int32_t* pred_edge_out, const int32_t* pred_pose_out) {
+    if (nedges && (!edge_a || !edge_b)) return fail(LRM_EINVAL, "null argument");
+    if (nsources && !sources) return fail(LRM_EINVAL, "null argument");
+    if (!cost_out && !hops_out && !pred_edge_out && !pred_pose_out) return fail(LRM_EINVAL, "pose routes: no output");
+    return LRM_OK;
+}
+} // namespace
+
+size_t lrm_pose_routes_workspace_bytes(size_t nposes, size_t rounds) { return lrm_routes_workspace_bytes(nposes, rounds); }
+
+int lrm_dbg_pose_routes_plan(size_t nedges, uint64_t out[4]) {
+    if (!out || nedges > (size_t)INT32_MAX) return fail(LRM_EINVAL, "pose routes plan: null output or nedges > INT32_MAX");
+    lrm_routes_plan(nedges, out);
+    return LRM_OK;
+}
+
+int lrm_pose_routes_dev(size_t nposes, const int32_t* edge_a, const int32_t* edge_b, size_t nedges, const uint8_t* edge_live,
+                        const uint8_t* pose_live, const int32_t* edge_cost, const int32_t* sources, size_t nsources, int direction,
+                        void* workspace, size_t rounds, int resume, int64_t* cost_out, int32_t* hops_out, int32_t* pred_edge_out,
+                        int32_t* pred_pose_out, int32_t* reached_out, int32_t* done_out, void* stream) {
+    int rc = pose_routes_ranges(direction, rounds, resume, nposes, nedges, nsources);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) {
+        if (reached_out || done_out) HIP_TRY(lrm_launch_pose_routes_empty(reached_out, done_out, (hipStream_t)stream), "pose routes launch");
+        return LRM_OK;
+    }
+    if (!workspace) return fail(LRM_EINVAL, "pose routes: null workspace");
+    if ((uintptr_t)workspace & 7) return fail(LRM_EINVAL, "pose routes: the workspace must be 8-byte aligned");
+    rc = pose_routes_pointers(edge_a, edge_b, nedges, sources, nsources, cost_out, hops_out, pred_edge_out, pred_pose_out);
+    if (rc != LRM_OK) return rc;
+    const LrmRoutesArgs A{(uint32_t)nposes, (uint32_t)nedges, (uint32_t)nsources, edge_a, edge_b, edge_cost, sources, edge_live, pose_live,
+                          direction, cost_out, hops_out, pred_edge_out, pred_pose_out, reached_out, done_out};
+    HIP_TRY(lrm_launch_pose_routes(A, workspace, (uint32_t)rounds, resume, (hipStream_t)stream), "pose routes launch");
+    return LRM_OK;
+}
+
+// The host loop: a binary-heap Dijkstra on the 64-bit keys over the arcs counting-sorted by their tail, then the predecessor
+// by the definition's rule in a loop over the edges.  The fixed point is unique, so this is what the kernels converge to.
+int lrm_pose_routes_cpu(size_t nposes, const int32_t* edge_a, const int32_t* edge_b, size_t nedges, const uint8_t* edge_live,
+                        const uint8_t* pose_live, const int32_t* edge_cost, const int32_t* sources, size_t nsources, int direction,
+                        int64_t* cost_out, int32_t* hops_out, int32_t* pred_edge_out, int32_t* pred_pose_out, int32_t* reached_out,
+                        double* ms) {
+    int rc = pose_routes_ranges(direction, 1, 0, nposes, nedges, nsources);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) {
+        if (reached_out) *reached_out = 0;
+        return LRM_OK;
+    }
+    rc = pose_routes_pointers(edge_a, edge_b, nedges, sources, nsources, cost_out, hops_out, pred_edge_out, pred_pose_out);
+    if (rc != LRM_OK) return rc;
+    const ScopeMs timer{ms};
+    const uint32_t np = (uint32_t)nposes;
+    // the arcs of the usable edges, counting-sorted by tail: first[u] .. first[u + 1]
+    struct Arc {
+        int32_t head;
+        uint32_t w;
+    };
+    std::vector<uint32_t> first(nposes + 1, 0u);
+    auto each_arc = [&](auto&& f) {
+        for (size_t e = 0; e < nedges; e++) {
+            int32_t u, v;
+            const uint32_t w = lrm_routes_edge(e, edge_a, edge_b, edge_live, pose_live, edge_cost, np, direction, &u, &v);
+            if (w == LRM_ROUTES_DEAD) continue;
+            f(e, u, v, w);
+            if (direction == 0) f(e, v, u, w);
+        }
+    };
+    each_arc([&](size_t, int32_t u, int32_t, uint32_t) { first[(size_t)u + 1]++; });
+    for (size_t p = 0; p < nposes; p++) first[p + 1] += first[p];
+    std::vector<Arc> arcs(first[nposes]);
+    {
+        std::vector<uint32_t> at(first.begin(), first.end() - 1);
+        each_arc([&](size_t, int32_t u, int32_t v, uint32_t w) { arcs[at[u]++] = Arc{v, w}; });
+    }
+    std::vector<uint64_t> key(nposes, LRM_ROUTES_UNREACHED);
+    typedef std::pair<uint64_t, int32_t> Item;
+    std::vector<Item> heap;
+    auto later = [](const Item& x, const Item& y) { return x.first > y.first; };
+    for (size_t i = 0; i < nsources; i++) {
+        const int32_t s = sources[i];
+        if (!lrm_routes_pose(s, np, pose_live) || key[s] == 0ull) continue;
+        key[s] = 0ull;
+        heap.push_back(Item(0ull, s));
+    }
+    while (!heap.empty()) { // every key is 0 so far: any order is a heap
+        std::pop_heap(heap.begin(), heap.end(), later);
+        const Item top = heap.back();
+        heap.pop_back();
+        if (top.first != key[top.second]) continue; // a lower key was pushed since
+        for (uint32_t i = first[top.second]; i < first[(size_t)top.second + 1]; i++) {
+            const uint64_t c = lrm_routes_step(top.first, arcs[i].w);
+            if (c < key[arcs[i].head]) {
+                key[arcs[i].head] = c;
+                heap.push_back(Item(c, arcs[i].head));
+                std::push_heap(heap.begin(), heap.end(), later);
+            }
+        }
+    }
+    int32_t reached = 0;
+    for (size_t p = 0; p < nposes; p++) {
+        const bool in = key[p] != LRM_ROUTES_UNREACHED;
+        reached += in ? 1 : 0;
+        if (cost_out) cost_out[p] = in ? (int64_t)(key[p] >> 32) : (int64_t)-1;
+        if (hops_out) hops_out[p] = in ? (int32_t)(uint32_t)key[p] : -1;
+        if (pred_edge_out) pred_edge_out[p] = -1;
+        if (pred_pose_out) pred_pose_out[p] = -1;
+    }
+    if (reached_out) *reached_out = reached;
+    if (pred_edge_out || pred_pose_out) {
+        std::vector<uint8_t> has(nposes, 0); // edges in ascending order: the first tight arc into a pose is the smallest edge's
+        each_arc([&](size_t e, int32_t u, int32_t v, uint32_t w) {
+            if (has[v] || key[v] == LRM_ROUTES_UNREACHED || lrm_routes_step(key[u], w) != key[v]) return;
+            has[v] = 1;
+            if (pred_edge_out) pred_edge_out[v] = (int32_t)e;
+            if (pred_pose_out) pred_pose_out[v] = u;
+        });
     }
     return LRM_OK;
 }

@@ -463,6 +463,109 @@ def stance_loads(workspace, ik_workspace, quats, nlegs, angles, tau_max, pose_id
     return status, holdable, peak, peak_at, load, tau
 
 
+def pose_routes_workspace(nposes, rounds, device):
+    """a workspace for pose_routes(): the 64-bit keys and one flag per launch (uint8 tensor; torch aligns it)"""
+    nbytes = _capi.load().lrm_pose_routes_workspace_bytes(int(nposes), int(rounds))
+    return _torch().empty(max(int(nbytes), 8), dtype=_torch().uint8, device=device)
+
+
+def pose_routes(nposes, edge_a, edge_b, sources, edge_live=None, pose_live=None, edge_cost=None, direction=0, rounds=64, sync=True,
+                workspace=None, cost=None, hops=None, pred_edge=None, pred_pose=None, reached=None, done=None, want_cost=True,
+                want_hops=True, want_pred_edge=True, want_pred_pose=True, resume=False):
+    """lrm_pose_routes_dev: shortest routes over the pose graph with integer costs -- which poses can be reached from `sources`,
+    in how many steps, at what cost and through which transition.  edge_a / edge_b int32 device tensors (the arrays of the
+    edge calls); sources int32 on the device; edge_live uint8 [nedges] (a clear or all_legs byte as it stands), pose_live uint8
+    [nposes] (a free, stable or holdable row) and edge_cost int32 [nedges] on the device or None (no cost: 1 per edge, cost
+    equals hops; a negative cost makes the edge dead); direction 0 an edge serves both ways, 1 a -> b only, 2 b -> a only (with
+    the goal as source: the cost to go and the next edge towards the goal).  Any index is safe: an edge with an end out of range
+    is dead, such a source is ignored.  cost[p] int64 and hops[p] int32 (-1 unreachable), pred_edge[p] int32 (the smallest usable
+    edge with a tight arc into p; -1 for a source or an unreachable pose), pred_pose[p] int32 (that arc's other end, or -1);
+    reached int32 [1] (poses with hops >= 0); done int32 [1] (>= 1: the fixed point was proven within `rounds` relaxation
+    launches; -1: not yet, the per-pose outputs are unspecified and the workspace holds the state).
+    sync=True: the call READS done ON THE HOST (one host synchronisation per call of the library) and calls again with resume = 1
+    until the fixed point is proven; the answer is the same bits however the work was cut.  sync=False: ONE call of the library,
+    no host synchronisation, done comes back as a tensor for the caller to look at: this form can be captured in a graph (a
+    linear chain of init, seed, `rounds` relax and up to three finish launches; pass the workspace and the outputs; the number of
+    launches a call needs varies from call to call, rounds >= the deepest route's hops + 1 always suffices, and done tells).  resume=True continues from the workspace's state (sync=False only needs
+    it; every other argument as before).  workspace: a uint8 tensor of lrm_pose_routes_workspace_bytes(nposes, rounds) bytes
+    (pose_routes_workspace()), allocated when None; calls on different streams need different workspaces and outputs.
+    -> (cost, hops, pred_edge, pred_pose, reached, done); want_* False (and no tensor given) pass NULL, not all four.  Every
+    tensor must be contiguous.  All atomics are integer min / add: bit-deterministic."""
+    torch = _torch()
+    nposes, rounds, direction = int(nposes), int(rounds), int(direction)
+    if nposes < 0:
+        raise ValueError("nposes: >= 0")
+    if not 1 <= rounds <= 4096:
+        raise ValueError("rounds: 1 to 4096 relaxation launches per call")
+    if not edge_a.is_cuda:
+        raise ValueError("edge_a: expected an int32 CUDA tensor")
+    ref = edge_a
+    ne = _check_edges(ref, edge_a, edge_b)
+    ns = sources.numel()
+    _check_in(sources, ref, torch.int32, ns, "sources")
+    _check_in(edge_live, ref, torch.uint8, ne, "edge_live")
+    _check_in(edge_cost, ref, torch.int32, ne, "edge_cost")
+    _one_per(ne, "edge_live / edge_cost: one entry per edge", edge_live, edge_cost)
+    _check_in(pose_live, ref, torch.uint8, nposes, "pose_live")
+    _one_per(nposes, "pose_live: one byte per pose", pose_live)
+    cost = _out(cost, ref, nposes, torch.int64, "route costs", want_cost)
+    hops = _out(hops, ref, nposes, torch.int32, "route hops", want_hops)
+    pred_edge = _out(pred_edge, ref, nposes, torch.int32, "predecessor edges", want_pred_edge)
+    pred_pose = _out(pred_pose, ref, nposes, torch.int32, "predecessor poses", want_pred_pose)
+    if cost is None and hops is None and pred_edge is None and pred_pose is None:
+        raise ValueError("pose_routes: no output")
+    reached = _out(reached, ref, 1, torch.int32, "reached count")
+    done = _out(done, ref, 1, torch.int32, "done word")
+    need = _capi.load().lrm_pose_routes_workspace_bytes(nposes, rounds)
+    if workspace is None:
+        workspace = pose_routes_workspace(nposes, rounds, ref.device)
+    _check_out(workspace, ref, torch.uint8, need, "workspace")
+
+    def call(resume):
+        _launch("lrm_pose_routes_dev", ref, nposes, _dp(edge_a), _dp(edge_b), ne, _dp(edge_live), _dp(pose_live), _dp(edge_cost),
+                _dp(sources), ns, direction, _dp(workspace), rounds, int(resume), _dp(cost), _dp(hops), _dp(pred_edge), _dp(pred_pose),
+                _dp(reached), _dp(done))
+
+    call(bool(resume))
+    if sync:
+        # after relax launch i every pose holds at most the best key over walks of i arcs: nposes launches reach the fixed
+        # point and one more proves it
+        for _ in range(nposes + 1):
+            if int(done.item()) >= 1:
+                break
+            call(True)
+        else:
+            raise RuntimeError("pose_routes: no fixed point after nposes + 1 calls")
+    return cost, hops, pred_edge, pred_pose, reached, done
+
+
+def route_path(pred_pose, pred_edge, goal, hops=None):
+    """The route to `goal` from pose_routes()'s predecessors, as host lists (poses from the source to the goal, the edges between
+    them: len(poses) == len(edges) + 1).  Copies the arrays to the host (a synchronisation).  hops: pose_routes()'s hops; with
+    it an unreached goal raises ValueError (the predecessors alone are -1 for a source and for an unreached pose alike, so
+    without it a goal with no predecessor counts as a source) and the length is checked."""
+    pp = pred_pose.detach().cpu().numpy() if hasattr(pred_pose, "detach") else np.asarray(pred_pose)
+    pe = pred_edge.detach().cpu().numpy() if hasattr(pred_edge, "detach") else np.asarray(pred_edge)
+    goal = int(goal)
+    if not 0 <= goal < len(pp) or len(pe) != len(pp):
+        raise ValueError("route_path: goal outside the poses, or predecessor arrays of different lengths")
+    want = None
+    if hops is not None:
+        want = int(hops[goal].item() if hasattr(hops, "detach") else hops[goal])
+        if want < 0:
+            raise ValueError(f"route_path: pose {goal} is not reached")
+    poses, edges, p = [goal], [], goal
+    while pp[p] >= 0:
+        if len(edges) >= len(pp):
+            raise ValueError("route_path: the predecessors form a cycle (an unfinished answer?)")
+        edges.append(int(pe[p]))
+        p = int(pp[p])
+        poses.append(p)
+    if want is not None and want != len(edges):
+        raise ValueError("route_path: the predecessors do not match hops (an unfinished answer?)")
+    return poses[::-1], edges[::-1]
+
+
 def edge_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot, nsamples=9, live_in=None, mask=None, reached=None,
                  first_miss=None, worst=None, worst_d2=None, planted=None, clear=None, advance=None):
     """lrm_edge_transit_posed_dev: does a planted foot stay reachable while the body moves from pose edge_a[e] to pose edge_b[e].
@@ -926,6 +1029,17 @@ class PoseSet:
         return swing_transit(tx, ty, tz, quats, body, self.legs, edge_a, edge_b, foot_from, foot_to, nsamples, lift, up, foot_radius,
                              margin, skip, live_in, mask, reached, first_miss, worst, worst_d2, hits, hit_seg, near, pen, swinging,
                              clear)
+
+    def routes(self, edge_a, edge_b, sources, **kw):
+        """device.pose_routes() over the poses of the last update(): nposes is this set's, every other argument is that
+        call's (edge_live, pose_live, edge_cost, direction, rounds, sync, workspace, the outputs).  No table is read: the call
+        composes the bytes of the other calls -- the capstone of the chain
+        update -> footholds -> foothold_edges -> edge_transit -> swing_transit -> routes(edge_live = clear, pose_live = all_legs).
+        -> (cost, hops, pred_edge, pred_pose, reached, done)"""
+        self._need()
+        if edge_a.device != self.workspace.device:
+            raise ValueError("edges and poses must live on one device")
+        return pose_routes(self.nposes, edge_a, edge_b, sources, **kw)
 
     def _check_angles(self, angles):
         torch = _torch()
