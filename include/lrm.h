@@ -1218,6 +1218,75 @@ int lrm_pose_routes_cpu(size_t nposes, const int32_t* edge_a, const int32_t* edg
                         int64_t* cost_out, int32_t* hops_out, int32_t* pred_edge_out, int32_t* pred_pose_out, int32_t* reached_out,
                         double* ms);
 int lrm_dbg_pose_routes_plan(size_t nedges, uint64_t out[4]);
+
+/* ---- pose-graph edges: neighbour poses within a step and a turn, in CSR ---------------------------------------------------
+ * New capability: every edge call above takes edge_a / edge_b from the caller; these calls build them on the device from the
+ * poses alone -- which pose can step to which -- so the chain update -> edges -> footholds -> foothold_edges -> edge_transit
+ * -> swing_transit -> routes starts on the device and can be captured in a graph.  The answer is bit-deterministic and the
+ * same on device and host (csrc/lrm_pose_edges.h is the one source of both); it does not depend on the order of the poses
+ * beyond their labels.  The reference has no such query.
+ * Inputs (device pointers for _dev, host pointers for _cpu):
+ *   quats (float32, nposes x 4, in storage order q[0..3]);  body (float32, nposes x 3, may be NULL = 0 for every pose);
+ *   pose_live (uint8, nposes, may be NULL): 0 = dead;
+ *   max_step (host float, mm, >= 0, may be +inf);  min_dot (host float in [0, 1]): the cosine of half the largest turn, 0
+ *     disables the turn test.  step2 = max_step*max_step and dot2 = min_dot*min_dot, one float32 product each.
+ * All arithmetic is float32 without contraction in the order written here.
+ * VALID: pose p is valid iff it is live, its three body coordinates are finite, and
+ *   n_p = ((q0*q0 + q1*q1) + q2*q2) + q3*q3 is finite and > 0.
+ * NEIGHBOURS: (p, q) with p != q are neighbours iff both are valid and
+ *   d2 = (dx*dx + dy*dy) + dz*dz <= step2, with dx = body[q].x - body[p].x and so on, and
+ *   c*c >= dot2 * (n_p * n_q), with c = ((p0*q0 + p1*q1) + p2*q2) + p3*q3.
+ *   Every comparison with a NaN is false (so two poses whose n_p * n_q overflows are never neighbours).  q and -q are the
+ *   same orientation: the test uses c*c.  The relation is SYMMETRIC BIT FOR BIT: x_q - x_p is the exact negative of
+ *   x_p - x_q, and c and n_p * n_q do not depend on which pose is named first; d2 and cos2 of (p, q) are those of (q, p).
+ * form: 0 row p holds the neighbours q > p, so every unordered pair appears once (what lrm_pose_routes_dev with
+ *   direction = 0 wants); 1 row p holds all neighbours q != p, an adjacency list: the exact symmetrisation of form 0.
+ * The two-step CSR: lrm_pose_edge_counts_dev -> lrm_foothold_offsets_dev -> lrm_pose_edges_dev.
+ *   count_out    (int32, nposes) the number of entries of row p;
+ *   segment      base = offsets[p]; room = min(offsets[p+1], (int64)capacity) - base, and 0 if that is negative or base < 0
+ *                (lrm_foothold_lists_posed_dev's rule);
+ *   edge_a_out, edge_b_out (int32, capacity) row p's neighbours in ASCENDING q, the first min(count, room) of them at
+ *                base + k: edge_a_out = p, edge_b_out = q;
+ *   d2_out       (float32, capacity, may be NULL) at the same positions the d2 above;
+ *   cos2_out     (float32, capacity, may be NULL) (c*c) / (n_p*n_q), one IEEE division: the squared cosine of half the turn;
+ *   written_out  (int32, nposes, may be NULL) written_out[p] = min(count, room).
+ * No element outside [base, base + room) is ever written, and every other element keeps its value.  ANY offsets array is
+ * memory-safe: decreasing, negative and overlapping offsets never cause a write outside the buffers, only a shorter row.
+ * With offsets made from count_out and capacity >= offsets[nposes] every row is whole and the edge list is sorted by (a, b).
+ * THE LAUNCH-ONLY IDIOM: prefill edge_a_out with -1, pass a fixed capacity to lrm_pose_edges_dev, and pass that capacity as
+ * nedges to the edge calls: every one of them treats an end outside [0, nposes) as a dead edge, so the tail beyond
+ * offsets[nposes] is inert and the chain needs no read-back of offsets[nposes].
+ * lrm_pose_edges_workspace_bytes(nposes): the bytes of `workspace` (device, 16-byte aligned): one bounding box per chunk of
+ *   64 consecutive poses and one per 64 chunks.  Both device calls launch their own box kernels, so neither depends on the
+ *   other having run; they make no allocation and no host synchronisation, no workgroup waits for another, there are no
+ *   atomics, and both can be captured in a graph.  Calls on different streams need different workspaces.  The cull by the boxes is exact (the gap of
+ *   two boxes, squared and summed in d2's order, is a lower bound of every pair's computed d2), so the answer does not depend
+ *   on how tight the boxes are; a cloud in Morton order (lrm_morton_order) makes them tight and the call fast.
+ * Checked first, in this order (all LRM_EINVAL): form outside 0..1; nposes > INT32_MAX; max_step NaN or negative; min_dot NaN
+ *   or outside [0, 1].  Then nposes == 0 is a no-op.  Then NULL quats, workspace (or one not 16-byte aligned), count_out
+ *   (counts call), offsets, edge_a_out or edge_b_out (fill call) give LRM_EINVAL.  Then capacity == 0 writes written_out = 0
+ *   everywhere and nothing else.
+ * lrm_pose_edges_cpu: the same with host pointers and no workspace, counts and lists in one call: count_out may be NULL;
+ *   offsets may be NULL when only the counts are asked for (then count_out must not be NULL and the list arguments are not
+ *   read); with offsets, edge_a_out and edge_b_out must not be NULL.  A serial loop over every pair with no culling: the
+ *   reference the GPU tests compare with bit for bit; *ms = the loop's time.
+ * lrm_dbg_pose_edges_plan: the launch arithmetic of the count and fill kernels on nposes poses, from the function the launch
+ *   itself consumes (host only): out = {poses per chunk, boxes per walk round, workgroups, block}.
+ * Chain: update -> pose_edges -> footholds -> foothold_edges -> edge_transit -> swing_transit -> routes. */
+size_t lrm_pose_edges_workspace_bytes(size_t nposes);
+int lrm_pose_edge_counts_dev(const float* quats, const float* body /* may be NULL */, size_t nposes,
+                             const uint8_t* pose_live /* may be NULL */, float max_step, float min_dot, int form, void* workspace,
+                             int32_t* count_out, void* stream);
+int lrm_pose_edges_dev(const float* quats, const float* body /* may be NULL */, size_t nposes,
+                       const uint8_t* pose_live /* may be NULL */, float max_step, float min_dot, int form, void* workspace,
+                       const int64_t* offsets /* device, nposes + 1 */, size_t capacity, int32_t* edge_a_out, int32_t* edge_b_out,
+                       float* d2_out /* may be NULL */, float* cos2_out /* may be NULL */, int32_t* written_out /* may be NULL */,
+                       void* stream);
+int lrm_pose_edges_cpu(const float* quats, const float* body, size_t nposes, const uint8_t* pose_live, float max_step, float min_dot,
+                       int form, int32_t* count_out /* may be NULL */, const int64_t* offsets /* host, may be NULL: counts only */,
+                       size_t capacity, int32_t* edge_a_out, int32_t* edge_b_out, float* d2_out, float* cos2_out,
+                       int32_t* written_out, double* ms);
+int lrm_dbg_pose_edges_plan(size_t nposes, uint64_t out[4]);
 /* host-buffer form of robot_full_struct's pipeline (several_leg.cu:326-877; AoS in, as its
  * Array<float3> arguments); quats is nquat x 4; body_mask_out[b] = 1 iff for SOME orientation
  * EVERY leg (limits rotated per orientation, bodies and targets rotated by the quaternion) has a

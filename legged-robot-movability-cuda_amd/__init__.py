@@ -20,8 +20,9 @@ from ._capi import (  # noqa: F401
     stance_stability_cpu, stance_lift,
     stance_loads_posed_cpu, LOADS_DEAD, LOADS_ALL, LOADS_DROPPED, LOADS_TRIPOD, LOADS_NONE,
     pose_routes_cpu, dbg_pose_routes_plan,
+    pose_edges_cpu, pose_edges_min_dot, dbg_pose_edges_plan,
     self_clearance_posed_cpu, trunk_clearance_posed_cpu, edge_transit_posed_cpu, swing_transit_posed_cpu, dbg_link_pair_dist_host, dbg_trunk_link_dist_host, dbg_edge_transit_samples_host,
 )
 from . import device  # noqa: F401
-from .device import PoseSet, ik, fk, edge_transit, swing_transit, stance_loads, pose_routes, route_path, swing_layout, foothold_offsets, foothold_edges_layout, foothold_support_layout, dbg_link_pair_dist, dbg_trunk_link_dist, dbg_edge_transit_samples  # noqa: F401
+from .device import PoseSet, ik, fk, edge_transit, swing_transit, stance_loads, pose_routes, route_path, pose_edges, pose_edge_counts, pose_edges_workspace, swing_layout, foothold_offsets, foothold_edges_layout, foothold_support_layout, dbg_link_pair_dist, dbg_trunk_link_dist, dbg_edge_transit_samples  # noqa: F401
 from . import shard  # noqa: F401

@@ -98,7 +98,7 @@ def load():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_", "lrm_edge_", "lrm_pose_routes_"))):
+            if name.startswith("lrm_dbg_") or (os.environ.get("LRM_LIB_PATH") and name.startswith(("lrm_foothold_", "lrm_body_clearance_", "lrm_leg_", "lrm_stance_", "lrm_self_", "lrm_trunk_", "lrm_edge_", "lrm_pose_routes_", "lrm_pose_edge"))):
                 continue  # an older library variant in an A/B run (LRM_LIB_PATH): diagnostics and the newest calls may be missing
             raise
         fn.argtypes, fn.restype = argtypes, restype
@@ -888,6 +888,70 @@ def dbg_pose_routes_plan(nedges):
     out = np.zeros(4, np.uint64)
     check(load().lrm_dbg_pose_routes_plan(int(nedges), _ptr(out)))
     return dict(zip(("chunk", "grid_cap", "sweeps", "workgroups"), (int(v) for v in out)))
+
+
+def pose_edges_min_dot(max_turn):
+    """min_dot of the pose edge calls from the largest turn in radians: float32(cos(max_turn / 2)); None = 0, no turn test"""
+    if max_turn is None:
+        return 0.0
+    max_turn = float(max_turn)
+    if not 0.0 <= max_turn <= np.pi:
+        raise ValueError("max_turn: radians in [0, pi] (None: no turn test)")
+    return float(np.float32(max(np.cos(max_turn / 2.0), 0.0)))
+
+
+def pose_edges_cpu(quats, body, max_step, min_dot=0.0, pose_live=None, form=0, offsets=None, capacity=None, edge_a=None, edge_b=None,
+                   d2=None, cos2=None, written=None, want_d2=True, want_cos2=True, counts_only=False):
+    """lrm_pose_edges_cpu: which pose can step to which, as counts and as a CSR edge list.  quats float32 [nposes, 4] in storage
+    order, body float32 [nposes, 3] or None (0), pose_live uint8 [nposes] or None; max_step in mm (>= 0, inf allowed), min_dot
+    in [0, 1] (pose_edges_min_dot(max_turn); 0: no turn test); form 0: row p holds the neighbours q > p, 1: all q != p.  Poses
+    p != q are neighbours iff both are valid (live, finite body, squared quaternion norm finite and > 0),
+    d2 = (dx*dx + dy*dy) + dz*dz <= max_step*max_step and c*c >= min_dot*min_dot * (n_p*n_q), all in float32 (include/lrm.h).
+    offsets=None: the counts are taken first and offsets = their exclusive sum, capacity = offsets[-1] unless given; with
+    offsets (int64 [nposes + 1], any contents) the segment rule of foothold_lists applies.  edge_a / edge_b / d2 / cos2 /
+    written: buffers to write into (views of longer ones are fine), allocated when None.  A serial loop over every pair.
+    -> (count int32 [nposes], offsets int64 [nposes + 1], edge_a, edge_b int32 [capacity], d2, cos2 float32 [capacity] or
+    None, written int32 [nposes], ms); counts_only=True -> (count, ms)."""
+    quats = _f32(quats).reshape(-1, 4)
+    nposes = len(quats)
+    body = None if body is None else _f32(body, (nposes, 3))
+    pose_live = _u8_per(pose_live, nposes, "pose_live: one byte per pose")
+    count = np.zeros(nposes, np.int32)
+    ms = C.c_double(0)
+    fn = load().lrm_pose_edges_cpu
+    if counts_only or offsets is None:
+        check(fn(_ptr(quats), _ptr(body), nposes, _ptr(pose_live), float(max_step), float(min_dot), int(form), _ptr(count), None, 0, None,
+                 None, None, None, None, C.addressof(ms)))
+        if counts_only:
+            return count, ms.value
+        offsets = np.concatenate([[0], np.cumsum(np.maximum(count, 0), dtype=np.int64)]).astype(np.int64)
+    offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    if len(offsets) != nposes + 1:
+        raise ValueError("offsets: nposes + 1 entries")
+    capacity = max(int(offsets[-1]), 0) if capacity is None else int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity >= 0")
+
+    def buf(a, dtype, n, want=True):
+        if a is None:
+            return np.zeros(n, dtype) if want else None
+        if not (isinstance(a, np.ndarray) and a.dtype == dtype and a.ndim == 1 and a.flags.c_contiguous and len(a) >= n):
+            raise ValueError(f"expected a contiguous {np.dtype(dtype).name} array of >= {n} entries")
+        return a
+
+    edge_a, edge_b = buf(edge_a, np.int32, capacity), buf(edge_b, np.int32, capacity)
+    d2, cos2 = buf(d2, np.float32, capacity, want_d2), buf(cos2, np.float32, capacity, want_cos2)
+    written = buf(written, np.int32, nposes)
+    check(fn(_ptr(quats), _ptr(body), nposes, _ptr(pose_live), float(max_step), float(min_dot), int(form), _ptr(count), _ptr(offsets),
+             capacity, _ptr(edge_a), _ptr(edge_b), _ptr(d2), _ptr(cos2), _ptr(written), C.addressof(ms)))
+    return count, offsets, edge_a, edge_b, d2, cos2, written, ms.value
+
+
+def dbg_pose_edges_plan(nposes):
+    """lrm_dbg_pose_edges_plan: the launch arithmetic of the pose edge kernels on nposes poses.  Host only."""
+    out = np.zeros(4, np.uint64)
+    check(load().lrm_dbg_pose_edges_plan(int(nposes), _ptr(out)))
+    return dict(zip(("chunk", "round", "workgroups", "block"), (int(v) for v in out)))
 
 
 def _swing_scalars(lift, up, foot_radius, margin, skip):

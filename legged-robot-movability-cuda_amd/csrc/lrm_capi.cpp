@@ -29,6 +29,7 @@
 #include "lrm_swing.h"
 #include "lrm_stance_loads.h"
 #include "lrm_pose_routes.h"
+#include "lrm_pose_edges.h"
 #include "lrm_ik.h"
 #include "lrm_dbg_math.h"
 #include "lrm_launch.h"
@@ -2785,6 +2786,110 @@ int lrm_pose_routes_cpu(size_t nposes, const int32_t* edge_a, const int32_t* edg
             if (pred_edge_out) pred_edge_out[v] = (int32_t)e;
             if (pred_pose_out) pred_pose_out[v] = u;
         });
+    }
+    return LRM_OK;
+}
+
+// ---- pose-graph edges: neighbour poses within a step and a turn, in CSR (lrm_pose_edges.hip) -----------
+namespace {
+// the refusals all three forms share, in the documented order
+int pose_edges_ranges(int form, size_t nposes, float max_step, float min_dot) {
+    if (form < 0 || form > 1) return fail(LRM_EINVAL, "pose edges: form must be 0 (q > p) or 1 (q != p)");
+    if (nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "pose edges: nposes must not exceed INT32_MAX");
+    if (!(max_step >= 0.f)) return fail(LRM_EINVAL, "pose edges: max_step must be >= 0 (mm; +inf allowed)");
+    if (!(min_dot >= 0.f && min_dot <= 1.f)) return fail(LRM_EINVAL, "pose edges: min_dot must lie in [0, 1]");
+    return LRM_OK;
+}
+int64_t pose_edges_capacity(size_t capacity) { return capacity > (size_t)INT64_MAX ? INT64_MAX : (int64_t)capacity; }
+} // namespace
+
+size_t lrm_pose_edges_workspace_bytes(size_t nposes) { return lrm_edges_workspace_bytes(nposes); }
+
+int lrm_dbg_pose_edges_plan(size_t nposes, uint64_t out[4]) {
+    if (!out || nposes > (size_t)INT32_MAX) return fail(LRM_EINVAL, "pose edges plan: null output or nposes > INT32_MAX");
+    lrm_edges_plan(nposes, out);
+    return LRM_OK;
+}
+
+int lrm_pose_edge_counts_dev(const float* quats, const float* body, size_t nposes, const uint8_t* pose_live, float max_step, float min_dot,
+                             int form, void* workspace, int32_t* count_out, void* stream) {
+    const int rc = pose_edges_ranges(form, nposes, max_step, min_dot);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!quats || !workspace || !count_out) return fail(LRM_EINVAL, "null argument");
+    if ((uintptr_t)workspace & 15) return fail(LRM_EINVAL, "pose edges: the workspace must be 16-byte aligned");
+    const LrmEdgesArgs A{quats, body, pose_live, (uint32_t)nposes, max_step * max_step, min_dot * min_dot, form};
+    HIP_TRY(lrm_launch_pose_edge_counts(A, static_cast<float*>(workspace), count_out, (hipStream_t)stream), "pose edge counts launch");
+    return LRM_OK;
+}
+
+int lrm_pose_edges_dev(const float* quats, const float* body, size_t nposes, const uint8_t* pose_live, float max_step, float min_dot, int form,
+                       void* workspace, const int64_t* offsets, size_t capacity, int32_t* edge_a_out, int32_t* edge_b_out, float* d2_out,
+                       float* cos2_out, int32_t* written_out, void* stream) {
+    const int rc = pose_edges_ranges(form, nposes, max_step, min_dot);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!quats || !workspace || !offsets || !edge_a_out || !edge_b_out) return fail(LRM_EINVAL, "null argument");
+    if ((uintptr_t)workspace & 15) return fail(LRM_EINVAL, "pose edges: the workspace must be 16-byte aligned");
+    if (capacity == 0) { // no row has room: nothing but written_out
+        if (written_out) HIP_TRY(hipMemsetAsync(written_out, 0, nposes * sizeof(int32_t), (hipStream_t)stream), "hipMemsetAsync written_out");
+        return LRM_OK;
+    }
+    const LrmEdgesArgs A{quats, body, pose_live, (uint32_t)nposes, max_step * max_step, min_dot * min_dot, form};
+    HIP_TRY(lrm_launch_pose_edges(A, static_cast<float*>(workspace), offsets, pose_edges_capacity(capacity), edge_a_out, edge_b_out, d2_out,
+                                  cos2_out, written_out, (hipStream_t)stream), "pose edges launch");
+    return LRM_OK;
+}
+
+// The host loop: every ordered pair (p, q) in ascending q, no culling; the validity and n_p of every pose are computed once,
+// by the function the kernels use.
+int lrm_pose_edges_cpu(const float* quats, const float* body, size_t nposes, const uint8_t* pose_live, float max_step, float min_dot, int form,
+                       int32_t* count_out, const int64_t* offsets, size_t capacity, int32_t* edge_a_out, int32_t* edge_b_out, float* d2_out,
+                       float* cos2_out, int32_t* written_out, double* ms) {
+    const int rc = pose_edges_ranges(form, nposes, max_step, min_dot);
+    if (rc != LRM_OK) return rc;
+    if (nposes == 0) return LRM_OK;
+    if (!quats || (!offsets && !count_out) || (offsets && (!edge_a_out || !edge_b_out))) return fail(LRM_EINVAL, "null argument");
+    if (offsets && capacity == 0) {
+        if (written_out) std::memset(written_out, 0, nposes * sizeof(int32_t));
+        if (!count_out) {
+            if (ms) *ms = 0.0;
+            return LRM_OK;
+        }
+        offsets = nullptr; // the counts are still asked for
+    }
+    const float step2 = max_step * max_step, dot2 = min_dot * min_dot;
+    const int64_t cap = pose_edges_capacity(capacity);
+    const ScopeMs timer{ms};
+    struct Pose {
+        float v[8];
+    };
+    std::vector<Pose> poses(nposes);
+    std::vector<uint8_t> valid(nposes);
+    for (size_t p = 0; p < nposes; p++) valid[p] = lrm_edges_pose(quats, body, pose_live, p, poses[p].v);
+    for (size_t p = 0; p < nposes; p++) {
+        int64_t base = 0, room = 0, n = 0;
+        if (offsets) room = lrm_edges_room(offsets, p, cap, &base);
+        if (valid[p]) {
+            const float* const a = poses[p].v;
+            for (size_t q = form ? 0 : p + 1; q < nposes; q++) {
+                if (q == p || !valid[q]) continue;
+                const float* const b = poses[q].v;
+                const float d2 = lrm_edges_d2(a[0], a[1], a[2], b[0], b[1], b[2]);
+                if (!(d2 <= step2)) continue;
+                const float c = lrm_edges_dot(a + 4, b + 4);
+                if (!lrm_edges_turn(c, a[3], b[3], dot2)) continue;
+                if (n < room) {
+                    edge_a_out[base + n] = (int32_t)p;
+                    edge_b_out[base + n] = (int32_t)q;
+                    if (d2_out) d2_out[base + n] = d2;
+                    if (cos2_out) cos2_out[base + n] = lrm_edges_cos2(c, a[3], b[3]);
+                }
+                n++;
+            }
+        }
+        if (count_out) count_out[p] = (int32_t)n;
+        if (offsets && written_out) written_out[p] = (int32_t)(n < room ? n : room);
     }
     return LRM_OK;
 }

@@ -566,6 +566,95 @@ def route_path(pred_pose, pred_edge, goal, hops=None):
     return poses[::-1], edges[::-1]
 
 
+def pose_edges_workspace(nposes, device):
+    """a workspace for pose_edge_counts() / pose_edges(): one bounding box per chunk of 64 poses and one per 64 chunks (uint8
+    tensor; torch aligns it)"""
+    nbytes = _capi.load().lrm_pose_edges_workspace_bytes(int(nposes))
+    return _torch().empty(int(nbytes), dtype=_torch().uint8, device=device)
+
+
+_EDGE_FORMS = {"upper": 0, "full": 1}
+
+
+def _pose_edges_args(quats, body, max_step, max_turn, pose_live, form, workspace):
+    """what pose_edge_counts() and pose_edges() take alike -> (nposes, max_step, min_dot, form 0 / 1, workspace)"""
+    torch = _torch()
+    nposes = _check_poses(quats, body)
+    if form not in _EDGE_FORMS:
+        raise ValueError('form: "upper" (q > p: every pair once) or "full" (q != p: an adjacency list)')
+    max_step = float(max_step)
+    if not max_step >= 0.0:
+        raise ValueError("max_step: mm, >= 0 (inf allowed)")
+    _check_in(pose_live, quats, torch.uint8, nposes, "pose_live")
+    _one_per(nposes, "pose_live: one byte per pose", pose_live)
+    need = _capi.load().lrm_pose_edges_workspace_bytes(nposes)
+    if workspace is None:
+        workspace = pose_edges_workspace(nposes, quats.device)
+    _check_out(workspace, quats, torch.uint8, need, "workspace")
+    return nposes, max_step, _capi.pose_edges_min_dot(max_turn), _EDGE_FORMS[form], workspace
+
+
+def pose_edge_counts(quats, body, max_step, max_turn=None, pose_live=None, form="upper", workspace=None, count=None):
+    """lrm_pose_edge_counts_dev: count[p] = the neighbour poses of pose p within a step and a turn (pose_edges() has the
+    relation); form "upper" counts the neighbours q > p, "full" all q != p.  quats float32 (nposes, 4) and body float32
+    (nposes, 3) or None on the device, as PoseSet.update() takes them; pose_live uint8 [nposes] or None.  Three launches (the
+    chunk boxes, the group boxes, the walk), no allocation with a workspace and count given, no host synchronisation.  -> count int32 [nposes]"""
+    torch = _torch()
+    nposes, max_step, min_dot, form, workspace = _pose_edges_args(quats, body, max_step, max_turn, pose_live, form, workspace)
+    count = _out(count, quats, nposes, torch.int32, "per-pose counts")
+    _launch("lrm_pose_edge_counts_dev", quats, _dp(quats), _dp(body), nposes, _dp(pose_live), max_step, min_dot, form, _dp(workspace),
+            _dp(count))
+    return count
+
+
+def pose_edges(quats, body, max_step, max_turn=None, pose_live=None, form="upper", count=None, offsets=None, capacity=None, workspace=None,
+               edge_a=None, edge_b=None, d2=None, cos2=None, written=None, want_d2=True, want_cos2=True):
+    """lrm_pose_edges_dev: which pose can step to which -- the edge_a / edge_b every edge call takes, built on the device from
+    the poses alone, in CSR form.  Poses p != q are NEIGHBOURS iff both are valid (live, finite body, squared quaternion norm
+    finite and > 0), their bodies are at most max_step mm apart and their orientations at most max_turn radians (None: no turn
+    test; q and -q are one orientation); the float32 arithmetic is include/lrm.h's, symmetric bit for bit, and the answer is the
+    host loop's bit for bit.  form "upper": row p holds the neighbours q > p, every unordered pair once (what routes() with
+    direction = 0 wants); "full": all q != p, an adjacency list.  Row p lies at offsets[p] in ascending q, as far as
+    min(offsets[p + 1], capacity) leaves room (foothold_lists()'s segment rule: any offsets are memory-safe, nothing outside a
+    segment is written); edge_a = p, edge_b = q, d2 = the squared distance, cos2 = the squared cosine of half the turn,
+    written[p] = the entries stored.  With offsets from the counts and room for all, the list is sorted by (a, b).
+      * offsets=None: count=None runs pose_edge_counts() first, then foothold_offsets(count).
+      * capacity=None and edge_a=None: offsets[-1] is read back to allocate exactly that -- ONE host synchronisation.
+      * with a capacity (or a preallocated edge_a: capacity = its length) the call ONLY LAUNCHES, and an edge_a it allocates
+        comes back prefilled with -1 beyond the written part: pass edge_a, edge_b and nedges = capacity to the edge calls, which
+        treat an end outside [0, nposes) as a dead edge -- no read-back of offsets[-1], and counts -> offsets -> edges can be
+        captured in a graph (pass the workspace and every output; prefill edge_a yourself).  A row that does not fit is cut short and written says so.
+    Calls on different streams need different workspaces (pose_edges_workspace()).  Clouds in Morton order make the chunk boxes
+    tight and the call fast; the answer does not depend on the order.
+    -> (edge_a int32, edge_b int32, offsets int64 [nposes + 1], d2, cos2 float32 or None, written int32 [nposes])"""
+    torch = _torch()
+    form_name = form
+    nposes, max_step, min_dot, form, workspace = _pose_edges_args(quats, body, max_step, max_turn, pose_live, form, workspace)
+    if offsets is None:
+        if count is None:
+            count = pose_edge_counts(quats, body, max_step, max_turn, pose_live, form_name, workspace)
+        _check_in(count, quats, torch.int32, nposes, "per-pose counts")
+        offsets = foothold_offsets(count.view(-1)[:nposes])
+    _check_in(offsets, quats, torch.int64, nposes + 1, "offsets")
+    if capacity is None:
+        capacity = edge_a.numel() if edge_a is not None else max(int(offsets[nposes].item()), 0)  # the one synchronisation
+    capacity = int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity >= 0")
+    if edge_a is None:
+        edge_a = torch.full((capacity,), -1, dtype=torch.int32, device=quats.device)
+    _check_out(edge_a, quats, torch.int32, capacity, "edge_a")
+    edge_b = _out(edge_b, quats, capacity, torch.int32, "edge_b")
+    d2 = _out(d2, quats, capacity, torch.float32, "edge squared distances", want_d2)
+    cos2 = _out(cos2, quats, capacity, torch.float32, "edge squared half-turn cosines", want_cos2)
+    written = _out(written, quats, nposes, torch.int32, "per-pose written counts")
+    # capacity 0: nothing but written is stored, but the C ABI refuses NULL lists first and an empty tensor has no address
+    pa, pb = (_dp(edge_a), _dp(edge_b)) if capacity else (_dp(workspace), _dp(workspace))
+    _launch("lrm_pose_edges_dev", quats, _dp(quats), _dp(body), nposes, _dp(pose_live), max_step, min_dot, form, _dp(workspace),
+            _dp(offsets), capacity, pa, pb, _dp(d2), _dp(cos2), _dp(written))
+    return edge_a, edge_b, offsets, d2, cos2, written
+
+
 def edge_transit(tx, ty, tz, quats, body, legs, edge_a, edge_b, foot, nsamples=9, live_in=None, mask=None, reached=None,
                  first_miss=None, worst=None, worst_d2=None, planted=None, clear=None, advance=None):
     """lrm_edge_transit_posed_dev: does a planted foot stay reachable while the body moves from pose edge_a[e] to pose edge_b[e].
@@ -1040,6 +1129,15 @@ class PoseSet:
         if edge_a.device != self.workspace.device:
             raise ValueError("edges and poses must live on one device")
         return pose_routes(self.nposes, edge_a, edge_b, sources, **kw)
+
+    def edges(self, quats, body, max_step, max_turn=None, **kw):
+        """device.pose_edges() on the poses of the last update(): quats (and body) must be that call's tensors, every other
+        argument is pose_edges()'s (pose_live, form, count, offsets, capacity, workspace, the outputs).  No table is read: the
+        call builds the edge_a / edge_b the edge calls take -- the first link of the chain
+        update -> edges -> footholds -> foothold_edges -> edge_transit -> swing_transit -> routes.
+        -> (edge_a, edge_b, offsets, d2, cos2, written)"""
+        self._last_update(quats)
+        return pose_edges(quats, body, max_step, max_turn, **kw)
 
     def _check_angles(self, angles):
         torch = _torch()

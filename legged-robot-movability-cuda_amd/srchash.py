@@ -9,7 +9,7 @@ import os
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # every file the timed kernels are compiled from (the .hip translation units and the headers they include)
 KERNEL_SOURCES = ("lrm_tol_kernels.hip", "lrm_point_tol.h", "lrm_point_xtab.h", "lrm_kernels.hip", "lrm_point_fast.h", "lrm_point.h",
-                  "lrm_exact_math.h", "lrm_types.h", "lrm_launch.h", "lrm_toltab.cpp", "lrm_toltab_build.h", "lrm_toltab_dev.hip", "lrm_edge_transit.hip", "lrm_edge_transit.h", "lrm_swing.hip", "lrm_swing.h", "lrm_stance_loads.hip", "lrm_stance_loads.h", "lrm_pose_routes.hip", "lrm_pose_routes.h", "lrm_dbg_math.hip", "lrm_dbg_math.h", "Makefile")
+                  "lrm_exact_math.h", "lrm_types.h", "lrm_launch.h", "lrm_toltab.cpp", "lrm_toltab_build.h", "lrm_toltab_dev.hip", "lrm_edge_transit.hip", "lrm_edge_transit.h", "lrm_swing.hip", "lrm_swing.h", "lrm_stance_loads.hip", "lrm_stance_loads.h", "lrm_pose_routes.hip", "lrm_pose_routes.h", "lrm_pose_edges.hip", "lrm_pose_edges.h", "lrm_dbg_math.hip", "lrm_dbg_math.h", "Makefile")
 
 
 def kernel_src_sha():

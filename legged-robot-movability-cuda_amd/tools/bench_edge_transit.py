@@ -24,7 +24,8 @@ from bench_footholds_posed import median_ms  # noqa: E402
 
 
 def plus_x_edges(bodies, step=50.0):
-    """(a, b): every body with a body one lattice step further in x at the same y and z"""
+    """(a, b): every body with a body one lattice step further in x at the same y and z.  Host numpy on a lattice with a known
+    step; device.pose_edges() / PoseSet.edges() now builds edges on the device from any poses (tools/bench_pose_edges.py)."""
     key = np.round((bodies.astype(np.float64) - bodies.min(0)) / step).astype(np.int64)
     code = lambda k: (k[:, 0] * 100003 + k[:, 1]) * 100003 + k[:, 2]
     order = np.argsort(code(key))

@@ -28,7 +28,9 @@ PLANE8 = [(1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1)]
 
 
 def lattice_neighbours(bodies, steps):
-    """[len(steps), nb] int32: the index of the body at (ix + dx, iy + dy, iz), or the body's own index without one"""
+    """[len(steps), nb] int32: the index of the body at (ix + dx, iy + dy, iz), or the body's own index without one.  Host numpy
+    on a lattice with a known step; device.pose_edges() / PoseSet.edges() now builds edges on the device from any poses
+    (tools/bench_pose_edges.py)."""
     ijk = np.rint((bodies.astype(np.float64) - bodies.min(0)) / STEP).astype(np.int64)
     dim = ijk.max(0) + 3
     key = lambda a: ((a[:, 2] + 1) * dim[1] + (a[:, 1] + 1)) * dim[0] + (a[:, 0] + 1)
