@@ -924,7 +924,7 @@ int lrm_reach_dist_posed_cpu(const float* xyz, size_t n, const int32_t* pose_idx
             continue;
         }
         const LrmPoseRecord& R = recs[(size_t)pi * nlegs + li];
-        const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+        const LrmLegHead& L = R.head;
         LrmVec3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
         p.x -= R.body_pos[0];
         p.y -= R.body_pos[1];
@@ -1149,7 +1149,7 @@ int lrm_ik_posed_cpu(const float* xyz, size_t nt, const int32_t* target_idx, siz
         p.z -= R.body_pos[2];
         const LrmVec3 s = seed ? LrmVec3{seed[3 * i], seed[3 * i + 1], seed[3 * i + 2]} : LrmVec3{K.seed[0], K.seed[1], K.seed[2]};
         LrmVec3 a;
-        status[i] = lrm_ik_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), &R.head.lists[0][0], K, p, s, a);
+        status[i] = lrm_ik_point(R.head, &R.head.lists[0][0], K, p, s, a);
         angles[3 * i] = a.x;
         angles[3 * i + 1] = a.y;
         angles[3 * i + 2] = a.z;
@@ -1179,7 +1179,7 @@ int lrm_fk_posed_cpu(const float* angles, size_t n, const int32_t* pose_idx, con
             continue;
         }
         const LrmPoseRecord& R = recs[(size_t)pi * nlegs + li];
-        LrmVec3 p = lrm_fk_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[(size_t)pi * nlegs + li], angles[3 * i],
+        LrmVec3 p = lrm_fk_point(R.head, iks[(size_t)pi * nlegs + li], angles[3 * i],
                                  angles[3 * i + 1], angles[3 * i + 2]);
         p.x += R.body_pos[0];
         p.y += R.body_pos[1];
@@ -1473,7 +1473,7 @@ int lrm_footholds_posed_cpu(const float* targets, size_t nt, const float* quats,
         bool all = true;
         for (size_t l = 0; l < nlegs; l++) {
             const LrmPoseRecord& R = recs[p * nlegs + l];
-            const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+            const LrmLegHead& L = R.head;
             const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
             int32_t count = 0;
             uint64_t best = kLrmFootholdNone;
@@ -1550,7 +1550,7 @@ int lrm_foothold_lists_posed_cpu(const float* targets, size_t nt, const float* q
     for (size_t p = 0; p < nposes; p++) {
         for (size_t l = 0; l < nlegs; l++) {
             const LrmPoseRecord& R = recs[p * nlegs + l];
-            const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+            const LrmLegHead& L = R.head;
             const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
             const size_t o = l * nposes + p;
             const int64_t base = offsets[o], end = offsets[o + 1] < cap ? offsets[o + 1] : cap;
@@ -1629,8 +1629,8 @@ int lrm_foothold_edges_posed_cpu(const float* targets, size_t nt, const float* q
             if (valid) {
                 const LrmPoseRecord& RA = recs[(size_t)a * nlegs + l];
                 const LrmPoseRecord& RB = recs[(size_t)b * nlegs + l];
-                const LrmCompiledLeg& LA = reinterpret_cast<const LrmCompiledLeg&>(RA.head); // lrm_point.h reads the head only
-                const LrmCompiledLeg& LB = reinterpret_cast<const LrmCompiledLeg&>(RB.head);
+                const LrmLegHead& LA = RA.head;
+                const LrmLegHead& LB = RB.head;
                 const LrmVec3 ba{RA.body_pos[0], RA.body_pos[1], RA.body_pos[2]}, bb{RB.body_pos[0], RB.body_pos[1], RB.body_pos[2]};
                 for (size_t t = 0; t < nt; t++) { // every target: no sphere is consulted
                     const LrmVec3 tg{targets[3 * t], targets[3 * t + 1], targets[3 * t + 2]};
@@ -1705,7 +1705,7 @@ int lrm_foothold_misses_posed_cpu(const float* targets, size_t nt, const float* 
         for (size_t l = 0; l < nlegs; l++) {
             const size_t o = l * nposes + p;
             const LrmPoseRecord& R = recs[p * nlegs + l];
-            const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+            const LrmLegHead& L = R.head;
             const LrmPoseFootEntry& E = ent[p * nlegs + l];
             const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
             int32_t near = 0;
@@ -1794,7 +1794,7 @@ int lrm_foothold_support_posed_cpu(const float* targets, size_t nt, const float*
             for (size_t p = 0; p < nposes; p++) { // every pose: no sphere and no box is consulted
                 if (pose_live && !pose_live[p]) continue;
                 const LrmPoseRecord& R = recs[p * nlegs + l];
-                const LrmCompiledLeg& L = reinterpret_cast<const LrmCompiledLeg&>(R.head); // lrm_point.h reads the head only
+                const LrmLegHead& L = R.head;
                 const LrmVec3 b{R.body_pos[0], R.body_pos[1], R.body_pos[2]};
                 const LrmVec3 rel{tg.x - b.x, tg.y - b.y, tg.z - b.z};
                 if (!lrm_reach_global(L, &R.head.lists[0][0], rel)) continue;
@@ -1960,7 +1960,7 @@ int lrm_leg_clearance_posed_cpu(const float* targets, size_t nt, const float* qu
             unsigned links = 0u;
             uint64_t best = kLrmLegClearanceNone;
             LrmVec3 J[4];
-            if (live) lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
+            if (live) lrm_leg_joints(R.head, iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
                                      angles[3 * o + 2], tip_clear, J);
             if (live && lrm_leg_joints_finite(J)) { // a skipped pose and a skipped leg keep the empty answer
                 LrmLegLinks S;
@@ -2020,7 +2020,7 @@ int lrm_leg_joints_posed_cpu(const float* angles, const float* quats, const floa
             const LrmPoseRecord& R = recs[p * nlegs + l];
             const size_t o = l * nposes + p;
             LrmVec3 J[4];
-            lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
+            lrm_leg_joints(R.head, iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
                            angles[3 * o + 2], tip_clear, J);
             for (int k = 0; k < 4; k++) {
                 joints_out[o * 12 + 3 * k] = lrm_leg_joint_out(J[k].x, R.body_pos[0]);
@@ -2197,7 +2197,7 @@ int lrm_self_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLeg
         uint32_t legs_ok = 0u;
         for (size_t l = 0; live && l < nlegs; l++) { // the joints once per (set, leg)
             const size_t o = l * nsets + s;
-            lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(recs[p * nlegs + l].head), iks[p * nlegs + l], angles[3 * o],
+            lrm_leg_joints(recs[p * nlegs + l].head, iks[p * nlegs + l], angles[3 * o],
                            angles[3 * o + 1], angles[3 * o + 2], tip_clear, J[l]);
             if (lrm_leg_joints_finite(J[l])) legs_ok |= 1u << l;
         }
@@ -2288,7 +2288,7 @@ int lrm_trunk_clearance_posed_cpu(const float* quats, size_t nposes, const LrmLe
             if (live) {
                 const LrmPoseRecord& rec = recs[p * nlegs + l];
                 LrmVec3 J[4];
-                lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(rec.head), iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
+                lrm_leg_joints(rec.head, iks[p * nlegs + l], angles[3 * o], angles[3 * o + 1],
                                angles[3 * o + 2], tip_clear, J);
                 if (lrm_leg_joints_finite(J)) A = lrm_trunk_leg(C, R, rec.head.inv_rot, J);
             }
@@ -2359,7 +2359,7 @@ int lrm_edge_transit_posed_cpu(const float* targets, size_t nt, const float* qua
     if (!quats || !legs || !edge_a || !edge_b || !foot || !reached_out || !first_miss_out || (nt && !targets))
         return fail(LRM_EINVAL, "null argument");
     const uint32_t S = (uint32_t)nsamples;
-    LrmCompiledLeg H; // only its head is written and read
+    LrmLegHead H;
     const ScopeMs timer{ms};
     for (size_t e = 0; e < nedges; e++) {
         const int64_t a = edge_a[e], b = edge_b[e];
@@ -2474,7 +2474,7 @@ int lrm_swing_transit_posed_cpu(const float* targets, size_t nt, const float* qu
     const LrmSwingRange range = lrm_swing_range(S, skip);
     const bool terrain = foot_radius > 0.f && range.k0 < range.k1;
     const float reach = foot_radius + margin;
-    LrmCompiledLeg H; // only its head is written and read
+    LrmLegHead H;
     LrmVec3 P[LRM_TRANSIT_MAX_SAMPLES];
     LrmSwingSeg seg[LRM_TRANSIT_MAX_SAMPLES];
     const ScopeMs timer{ms};
@@ -2632,7 +2632,7 @@ int lrm_stance_loads_posed_cpu(const float* quats, size_t nposes, const LrmLegDi
         for (size_t l = 0; live && l < nlegs; l++) { // the joints and the lever arms once per (set, leg)
             const size_t o = l * nsets + s;
             LrmLoadsLeg A;
-            if (!lrm_loads_leg(P, reinterpret_cast<const LrmCompiledLeg&>(recs[p * nlegs + l].head), iks[p * nlegs + l], c, angles[3 * o],
+            if (!lrm_loads_leg(P, recs[p * nlegs + l].head, iks[p * nlegs + l], c, angles[3 * o],
                                angles[3 * o + 1], angles[3 * o + 2], &A))
                 continue;
             xi[l] = A.xi, eta[l] = A.eta;

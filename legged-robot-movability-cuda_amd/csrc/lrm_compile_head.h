@@ -1,9 +1,7 @@
-// lrm_compile_head.h -- the strict head of the leg compiler: everything lrm_point.h reads, built from
-// (LegDimensions, quaternion).  One arithmetic for the host compiler (lrm_compile.cpp, every LrmCompiledLeg)
-// and the device pose compiler (lrm_posed.hip, one record per (pose, leg)); lrm_toltab_build.h is the precedent.
-//
-// The head is the first offsetof(LrmCompiledLeg, flists) = 480 bytes of LrmCompiledLeg; LrmLegHead repeats
-// that prefix field for field (asserted below), so both compilers fill the same bytes with the same floats.
+// lrm_compile_head.h -- the strict head of the leg compiler: LrmLegHead (lrm_types.h), built from
+// (LegDimensions, quaternion).  One arithmetic for the host compiler (lrm_compile.cpp, the base of every
+// LrmCompiledLeg) and the device pose compiler (lrm_posed.hip, one record per (pose, leg)); lrm_toltab_build.h
+// is the precedent.  Both fill the same 480 bytes with the same floats.
 // Libm: the host calls glibc's cosf / sinf / sincosf / asin exactly as before; the device takes cosf, sinf and
 // sincosf from lrm_sincosf (lrm_exact_math.h, glibc's algorithm: tests/test_posed_cpu.py checks it against
 // glibc's separate cosf / sinf) and asin from the device libm, whose double result is then rounded to float
@@ -11,40 +9,8 @@
 // Compile without FMA contraction.
 #pragma once
 #include <math.h>
-#include <stddef.h>
 #include "lrm_exact_math.h"
 #include "lrm_types.h"
-
-// The prefix of LrmCompiledLeg that the strict per-point code (lrm_point.h) reads.
-struct LrmLegHead {
-    LrmCircle lists[4][LRM_N_CIRCLES];
-    float corner_x[LRM_N_CORNERS];
-    float corner_y[LRM_N_CORNERS];
-    int32_t n_corners;
-    float inv_rot[9];
-    float fwd_rot[9];
-    float cos_body, sin_body;
-    float body;
-    float cos_pitch, sin_pitch;
-    float cos_pitch_rev, sin_pitch_rev;
-    float coxa_length;
-    float max_coxa, min_coxa;
-    float mega_hi, mega_lo;
-    float coxa_mid;
-    float region_mid;
-    float full_sat[2];
-    float reach_r2_max;
-};
-#define LRM_HEAD_SAME(f) static_assert(offsetof(LrmLegHead, f) == offsetof(LrmCompiledLeg, f), "head layout: " #f)
-LRM_HEAD_SAME(lists); LRM_HEAD_SAME(corner_x); LRM_HEAD_SAME(corner_y); LRM_HEAD_SAME(n_corners);
-LRM_HEAD_SAME(inv_rot); LRM_HEAD_SAME(fwd_rot); LRM_HEAD_SAME(cos_body); LRM_HEAD_SAME(sin_body);
-LRM_HEAD_SAME(body); LRM_HEAD_SAME(cos_pitch); LRM_HEAD_SAME(sin_pitch); LRM_HEAD_SAME(cos_pitch_rev);
-LRM_HEAD_SAME(sin_pitch_rev); LRM_HEAD_SAME(coxa_length); LRM_HEAD_SAME(max_coxa); LRM_HEAD_SAME(min_coxa);
-LRM_HEAD_SAME(mega_hi); LRM_HEAD_SAME(mega_lo); LRM_HEAD_SAME(coxa_mid); LRM_HEAD_SAME(region_mid);
-LRM_HEAD_SAME(full_sat); LRM_HEAD_SAME(reach_r2_max);
-#undef LRM_HEAD_SAME
-static_assert(sizeof(LrmLegHead) == offsetof(LrmCompiledLeg, flists), "the head ends where the filter constants begin");
-static_assert(sizeof(LrmLegHead) == 480, "head size");
 
 // One record of the posed queries (lrm_posed.hip): the head of lrm_compile_leg(leg, quat, 1) and the pose's body position.
 struct alignas(16) LrmPoseRecord {
@@ -221,10 +187,9 @@ LRM_HD int lrm_corner_points(const LrmLegDimensions& l, float* xs, float* ys) {
     return n;
 }
 
-// The head of lrm_compile_leg(leg_in, quat, apply_leg_rotation): every field of LrmLegHead, written into `out`
-// (an LrmCompiledLeg or an LrmLegHead).  *leg_out (may be null) receives the leg the rest of the compiler works on.
-template <class Head>
-LRM_HD void lrm_compile_head(const LrmLegDimensions& leg_in, const float quat[4], int apply_leg_rotation, Head* out,
+// The head of lrm_compile_leg(leg_in, quat, apply_leg_rotation): every field of LrmLegHead, written into `out`.
+// *leg_out (may be null) receives the leg the rest of the compiler works on.
+LRM_HD void lrm_compile_head(const LrmLegDimensions& leg_in, const float quat[4], int apply_leg_rotation, LrmLegHead* out,
                              LrmLegDimensions* leg_out) {
     const float kPi = 3.14159265358979323846264338327950288419716939937510582097f;
     LrmLegDimensions l = leg_in;

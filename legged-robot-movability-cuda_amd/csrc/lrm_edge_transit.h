@@ -47,21 +47,15 @@ LRM_HD LrmTransitSample lrm_transit_sample(const float qa[4], const float qb[4],
 // (e, l) of a live edge with both ends in range is planted iff its foot names a target of the cloud
 LRM_HD bool lrm_transit_foot_in_cloud(int32_t ft, uint32_t nt) { return ft >= 0 && (uint32_t)ft < nt; }
 
-// lrm_point.h reads the head only: a bare head (the device's LDS slot or local) stands for the leg, as a pose record does
-LRM_HD const LrmCompiledLeg& lrm_transit_leg_of(const LrmCompiledLeg& L) { return L; }
-LRM_HD const LrmCompiledLeg& lrm_transit_leg_of(const LrmLegHead& H) { return reinterpret_cast<const LrmCompiledLeg&>(H); }
-
 // The strict evaluation of p = target - body_s on the head of lrm_compile_head(leg, q_s, 1), compiled into *H (the caller's
-// storage: an LrmLegHead in an LDS slot or in private memory, or the host's LrmCompiledLeg, of which only the head is written).
+// storage: an LDS slot or private memory on the device, a local on the host).
 // Returns r_s; where r_s is false *d2 receives the squared norm of distance_global's vector (its validity byte is not
 // consulted), a nan as +inf.  Where r_s is true *d2 is left alone.
-template <class Head>
-LRM_HD bool lrm_transit_eval(const LrmLegDimensions& leg, const float q[4], LrmVec3 p, Head* H, float* d2) {
+LRM_HD bool lrm_transit_eval(const LrmLegDimensions& leg, const float q[4], LrmVec3 p, LrmLegHead* H, float* d2) {
     lrm_compile_head(leg, q, 1, H, (LrmLegDimensions*)nullptr);
-    const LrmCompiledLeg& L = lrm_transit_leg_of(*H);
     const LrmCircle* lists = &H->lists[0][0];
-    if (lrm_reach_global(L, lists, p)) return true;
-    lrm_dist_global(L, lists, p);
+    if (lrm_reach_global(*H, lists, p)) return true;
+    lrm_dist_global(*H, lists, p);
     const float d = (p.x * p.x + p.y * p.y) + p.z * p.z;
     *d2 = d != d ? INFINITY : d;
     return false;

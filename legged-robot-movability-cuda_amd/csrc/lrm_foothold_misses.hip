@@ -148,14 +148,14 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                 if (__ballot(cand) == 0ull) continue;
                 const LrmPoseRecord& R = lrm_fresh(recs[r0 + l]);
                 bool miss = false;
-                if (cand) miss = !lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists[l], rel);
+                if (cand) miss = !lrm_reach_global(R.head, my_lists[l], rel);
                 const unsigned long long mm = __ballot(miss);
                 if (mm == 0ull) continue; // wave-uniform: nobody needs the distance
                 if ((uint32_t)lane == l) near_n += (uint32_t)__builtin_popcountll(mm);
                 uint64_t kk = kLrmFootholdNone;
                 if (miss) {
                     LrmVec3 d = rel;
-                    lrm_dist_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists[l], d);
+                    lrm_dist_global(R.head, my_lists[l], d);
                     const float m2 = lrm_foothold_miss_m2(d);
                     if (m2 < inf) kk = lrm_foothold_key(m2, ti);
                 }
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_MISSES_MIN_WAVES) void foothol
                     // the winner's vector once more, from this lane's own record: strict code, the same bits
                     const LrmPoseRecord& R = recs[r0 + lane];
                     d = LrmVec3{tx[wi] - body.x, ty[wi] - body.y, tz[wi] - body.z};
-                    lrm_dist_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists[lane], d);
+                    lrm_dist_global(R.head, my_lists[lane], d);
                 }
                 shift_x[o] = d.x;
                 shift_y[o] = d.y;

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_SUPPORT_MIN_WAVES) void footho
             bool hit = false;
             if ((in_legs >> l) & 1u) {
                 const LrmPoseRecord& R = lrm_fresh(recs[r0 + l]);
-                hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists[l], rel);
+                hit = lrm_reach_global(R.head, my_lists[l], rel);
             }
             if (__ballot(hit) == 0ull) continue; // wave-uniform
             const LrmPoseFootEntry& E = lrm_fresh(fh[r0 + l]);

@@ -149,7 +149,7 @@ __device__ __forceinline__ void footholds_posed_traverse(
                 bool hit = false;
                 if (inside) {
                     const LrmPoseRecord& R = lrm_fresh(recs[r0 + l]);
-                    hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists[l], rel);
+                    hit = lrm_reach_global(R.head, my_lists[l], rel);
                 }
                 const unsigned long long hm = __ballot(hit);
                 if (hm == 0ull) continue; // wave-uniform
@@ -465,12 +465,12 @@ __global__ __launch_bounds__(kBlock, LRM_FOOTHOLD_EDGES_MIN_WAVES) void foothold
                 bool hit = false;
                 if (inside) {
                     const LrmPoseRecord& R = lrm_fresh(recs[ra0 + l]);
-                    hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), lists_a[l], rel_a);
+                    hit = lrm_reach_global(R.head, lists_a[l], rel_a);
                 }
                 if (__ballot(hit) == 0ull) continue; // nobody reaches it under a: b is not asked
                 if (hit) {
                     const LrmPoseRecord& R = lrm_fresh(recs[rb0 + l]);
-                    hit = lrm_reach_global(reinterpret_cast<const LrmCompiledLeg&>(R.head), lists_b[l], rel_b);
+                    hit = lrm_reach_global(R.head, lists_b[l], rel_b);
                 }
                 const unsigned long long hm = __ballot(hit);
                 if (hm == 0ull) continue; // wave-uniform

@@ -120,7 +120,7 @@ LRM_HD void lrm_ik_compile_pose(const LrmLegDimensions& leg, const float quat[4]
 }
 
 // p (caller's frame) -> coxa frame: the operations of lrm_reach_global + lrm_reach_circles, in their order
-LRM_HD LrmVec3 lrm_ik_to_coxa(const LrmCompiledLeg& L, LrmVec3 p) {
+LRM_HD LrmVec3 lrm_ik_to_coxa(const LrmLegHead& L, LrmVec3 p) {
     LrmVec3 u = lrm_qrot(L.inv_rot, p);
     const float buffer = u.x * L.sin_body;
     u.x = u.x * L.cos_body - u.y * L.sin_body;
@@ -133,7 +133,7 @@ LRM_HD LrmVec3 lrm_ik_to_coxa(const LrmCompiledLeg& L, LrmVec3 p) {
 }
 
 // coxa frame -> caller's frame: the inverse of lrm_ik_to_coxa
-LRM_HD LrmVec3 lrm_ik_from_coxa(const LrmCompiledLeg& L, const LrmIkLeg& K, LrmVec3 u) {
+LRM_HD LrmVec3 lrm_ik_from_coxa(const LrmLegHead& L, const LrmIkLeg& K, LrmVec3 u) {
     // place_over_coxa<Reverse>, one_leg.cu:9-24
     const float buffer = u.x * L.sin_pitch_rev;
     u.x = u.x * L.cos_pitch_rev - u.z * L.sin_pitch_rev;
@@ -149,7 +149,7 @@ LRM_HD LrmVec3 lrm_ik_from_coxa(const LrmCompiledLeg& L, const LrmIkLeg& K, LrmV
 }
 
 // forward kinematics: joint angles -> tip in the caller's frame
-LRM_HD LrmVec3 lrm_fk_point(const LrmCompiledLeg& L, const LrmIkLeg& K, float c, float f, float t) {
+LRM_HD LrmVec3 lrm_fk_point(const LrmLegHead& L, const LrmIkLeg& K, float c, float f, float t) {
     float sc, cc, sf, cf, sa, ca;
     lrm_sincosf(c, &sc, &cc);
     lrm_sincosf(f, &sf, &cf);
@@ -260,7 +260,7 @@ LRM_HD bool lrm_ik_finite(float v) { return (lrm_f2u(v) & 0x7f800000u) != 0x7f80
 
 // IK of one point.  seed = (coxa, femur, tibia) (K.seed for "no seed").  Writes the angles to ang (x coxa, y femur,
 // z tibia) and returns the LRM_IK_* status.
-LRM_HD uint8_t lrm_ik_point(const LrmCompiledLeg& L, const LrmCircle* lists, const LrmIkLeg& K, LrmVec3 p, LrmVec3 seed,
+LRM_HD uint8_t lrm_ik_point(const LrmLegHead& L, const LrmCircle* lists, const LrmIkLeg& K, LrmVec3 p, LrmVec3 seed,
                             LrmVec3& ang) {
     const bool reach = lrm_reach_global(L, lists, p);
     LrmVec3 g = p;

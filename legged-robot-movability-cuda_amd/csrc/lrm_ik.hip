@@ -1,7 +1,7 @@
 // lrm_ik.hip -- gfx950 kernels of the joint-angle queries (lrm_ik_dev, lrm_fk_dev): one point per lane, SoA in and out.
 //
-// The per-(leg, orientation) constants are two kernel arguments by value: the strict head of the compiled leg (480 B,
-// the part lrm_point.h reads) and LrmIkLeg (128 B).  No allocation, no host synchronisation: graph-capturable.  Both
+// The per-(leg, orientation) constants are two kernel arguments by value: the strict head of the compiled leg (LrmLegHead,
+// 480 B) and LrmIkLeg (128 B).  No allocation, no host synchronisation: graph-capturable.  Both
 // are read through the kernarg pointer (lrm_kernarg, as lrm_kernels.hip does) so that their loads stay s_loads at the
 // point of use; the head's 4 x 4 circle table is staged in LDS (per-lane indexed by the region).
 //
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kBlock, LRM_IK_MIN_WAVES) void ik_kernel(
     const LrmIkLeg K_kernarg, const float* __restrict__ seed_c, const float* __restrict__ seed_f, const float* __restrict__ seed_t,
     float* __restrict__ coxa, float* __restrict__ femur, float* __restrict__ tibia, uint8_t* __restrict__ status) {
     __shared__ LrmCircle s_lists[4 * LRM_N_CIRCLES];
-    const LrmCompiledLeg& L = lrm_kernarg<LrmCompiledLeg>(kHeadArg); // lrm_point.h reads the head only
+    const LrmLegHead& L = lrm_kernarg<LrmLegHead>(kHeadArg);
     const LrmIkLeg& K = lrm_kernarg<LrmIkLeg>(kIkArg);
     if (threadIdx.x < 64) reinterpret_cast<float*>(s_lists)[threadIdx.x] = reinterpret_cast<const float*>(&L.lists[0][0])[threadIdx.x];
     __syncthreads();
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void fk_kernel(const float* __restrict__ co
                                                     const float* __restrict__ tibia, size_t n, const LrmLegHead H_kernarg,
                                                     const LrmIkLeg K_kernarg, float* __restrict__ x, float* __restrict__ y,
                                                     float* __restrict__ z) {
-    const LrmCompiledLeg& L = lrm_kernarg<LrmCompiledLeg>(kHeadArg);
+    const LrmLegHead& L = lrm_kernarg<LrmLegHead>(kHeadArg);
     const LrmIkLeg& K = lrm_kernarg<LrmIkLeg>(kIkArg);
     const size_t stride = (size_t)gridDim.x * kBlock;
     for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
@@ -76,24 +76,18 @@ int grid_for(size_t n, size_t cap) {
     return (int)(g < 1 ? 1 : g);
 }
 
-LrmLegHead head_of(const LrmCompiledLeg& L) {
-    LrmLegHead H;
-    memcpy(&H, &L, sizeof H);
-    return H;
-}
-
 } // namespace
 
 hipError_t lrm_launch_ik(const float* x, const float* y, const float* z, size_t n, const LrmCompiledLeg& L, const LrmIkLeg& K,
                          const float* seed_c, const float* seed_f, const float* seed_t, float* coxa, float* femur, float* tibia,
                          uint8_t* status, hipStream_t st) {
-    hipLaunchKernelGGL(ik_kernel, dim3(grid_for(n, 256 * LRM_IK_MIN_WAVES * 8)), dim3(kBlock), 0, st, x, y, z, n, head_of(L), K,
+    hipLaunchKernelGGL(ik_kernel, dim3(grid_for(n, 256 * LRM_IK_MIN_WAVES * 8)), dim3(kBlock), 0, st, x, y, z, n, LrmLegHead(L), K,
                        seed_c, seed_f, seed_t, coxa, femur, tibia, status);
     return hipGetLastError();
 }
 
 hipError_t lrm_launch_fk(const float* coxa, const float* femur, const float* tibia, size_t n, const LrmCompiledLeg& L,
                          const LrmIkLeg& K, float* x, float* y, float* z, hipStream_t st) {
-    hipLaunchKernelGGL(fk_kernel, dim3(grid_for(n, 256 * 32)), dim3(kBlock), 0, st, coxa, femur, tibia, n, head_of(L), K, x, y, z);
+    hipLaunchKernelGGL(fk_kernel, dim3(grid_for(n, 256 * 32)), dim3(kBlock), 0, st, coxa, femur, tibia, n, LrmLegHead(L), K, x, y, z);
     return hipGetLastError();
 }

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kBlock, LRM_IK_POSED_MIN_WAVES) void ik_posed_kerne
             p.y -= R.body_pos[1];
             p.z -= R.body_pos[2];
             if (!seed_c) seed = LrmVec3{K.seed[0], K.seed[1], K.seed[2]};
-            st = lrm_ik_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists, K, p, seed, ang);
+            st = lrm_ik_point(R.head, my_lists, K, p, seed, ang);
         } else {
             const LrmPoseRecord& R = recs[r];
             const LrmIkLeg& K = iks[r];
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kBlock, LRM_IK_POSED_MIN_WAVES) void ik_posed_kerne
             p.y -= R.body_pos[1];
             p.z -= R.body_pos[2];
             if (!seed_c) seed = LrmVec3{K.seed[0], K.seed[1], K.seed[2]};
-            st = lrm_ik_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), &R.head.lists[0][0], K, p, seed, ang);
+            st = lrm_ik_point(R.head, &R.head.lists[0][0], K, p, seed, ang);
         }
         if (act) {
             if (!in_range) {
@@ -151,13 +151,13 @@ __global__ __launch_bounds__(kBlock) void fk_posed_kernel(const float* __restric
         if (uniform) {
             const LrmPoseRecord& R = lrm_fresh(recs[r0]);
             const LrmIkLeg& K = lrm_fresh(iks[r0]);
-            p = lrm_fk_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), K, c, f, t);
+            p = lrm_fk_point(R.head, K, c, f, t);
             p.x += R.body_pos[0];
             p.y += R.body_pos[1];
             p.z += R.body_pos[2];
         } else {
             const LrmPoseRecord& R = recs[r];
-            p = lrm_fk_point(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[r], c, f, t);
+            p = lrm_fk_point(R.head, iks[r], c, f, t);
             p.x += R.body_pos[0];
             p.y += R.body_pos[1];
             p.z += R.body_pos[2];

@@ -10,7 +10,7 @@
 // The four joints of (pose, leg) under angles (c, f, t), in the caller's frame RELATIVE TO body[p] (no body added):
 // J[0] the coxa joint, J[1] the femur joint, J[2] the knee, J[3] the tibia's end, tip_clear short of the foot.  The chain
 // is lrm_fk_point's: with tip_clear == 0 and T > 0, J[3] has the bits of its tip (the same grouping of h and z).
-LRM_HD void lrm_leg_joints(const LrmCompiledLeg& L, const LrmIkLeg& K, float c, float f, float t, float tip_clear, LrmVec3 J[4]) {
+LRM_HD void lrm_leg_joints(const LrmLegHead& L, const LrmIkLeg& K, float c, float f, float t, float tip_clear, LrmVec3 J[4]) {
     float sc, cc, sf, cf, sa, ca;
     lrm_sincosf(c, &sc, &cc);
     lrm_sincosf(f, &sf, &cf);

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kBlock, LRM_LEG_CLEARANCE_MIN_WAVES) void leg_clear
             {
                 const LrmPoseRecord& R = lrm_fresh(recs[rp + l]);
                 const LrmIkLeg& K = lrm_fresh(iks[rp + l]);
-                lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(R.head), K, coxa[o], femur[o], tibia[o], tip_clear, J);
+                lrm_leg_joints(R.head, K, coxa[o], femur[o], tibia[o], tip_clear, J);
             }
 #pragma unroll
             for (int k = 0; k < 4; k++) J[k] = uni(J[k]);
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void leg_joints_posed_kernel(const float* _
         const uint32_t r = p * nlegs + l;
         const LrmPoseRecord& R = recs[r];
         LrmVec3 J[4];
-        lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(R.head), iks[r], coxa[i], femur[i], tibia[i], tip_clear, J);
+        lrm_leg_joints(R.head, iks[r], coxa[i], femur[i], tibia[i], tip_clear, J);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             joints_out[i * 12 + 3 * k] = lrm_leg_joint_out(J[k].x, R.body_pos[0]);

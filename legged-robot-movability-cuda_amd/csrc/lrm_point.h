@@ -4,7 +4,8 @@
 // same with its `__host__ __device__` functions).  Compile with -ffp-contract=off: every
 // float operation below is a separate IEEE operation in the order the reference performs
 // it, so that together with lrm_exact_math.h the result is bit-identical to the
-// reference's host path.  All leg-only quantities come precomputed in LrmCompiledLeg.
+// reference's host path.  All leg-only quantities come precomputed in LrmLegHead: a
+// compiled leg's base, or the head of a pose record.
 //
 // `lists` points at the 4x4 circle table (LDS copy on the device, L.lists on the host).
 #pragma once
@@ -46,7 +47,7 @@ LRM_HD bool lrm_all_valid(const LrmCircle* list, float x, float y) {
 }
 
 // find_region, circles.cu.h:48-78 -> index of the circle list
-LRM_HD int lrm_region(const LrmCompiledLeg& L, float x, float y) {
+LRM_HD int lrm_region(const LrmLegHead& L, float x, float y) {
     const float angle = lrm_atan2f(y, x);
     const bool upper = angle > L.region_mid;
     const bool more = angle > (upper ? L.full_sat[1] : L.full_sat[0]);
@@ -55,7 +56,7 @@ LRM_HD int lrm_region(const LrmCompiledLeg& L, float x, float y) {
 }
 
 // reachability_circles, one_leg.cu:280-319 (point already in "leg 0" body frame)
-LRM_HD bool lrm_reach_circles(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3 p) {
+LRM_HD bool lrm_reach_circles(const LrmLegHead& L, const LrmCircle* lists, LrmVec3 p) {
     // place_over_coxa, one_leg.cu:9-24
     p.x -= L.body;
     float buffer = p.x * L.sin_pitch;
@@ -78,7 +79,7 @@ LRM_HD bool lrm_reach_circles(const LrmCompiledLeg& L, const LrmCircle* lists, L
 }
 
 // reachability_global, one_leg_global.cu:103-130
-LRM_HD bool lrm_reach_global(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3 p) {
+LRM_HD bool lrm_reach_global(const LrmLegHead& L, const LrmCircle* lists, LrmVec3 p) {
     LrmVec3 u = lrm_qrot(L.inv_rot, p);
     const float buffer = u.x * L.sin_body; // z_rotateInPlace, one_leg_global.cu:25-31
     u.x = u.x * L.cos_body - u.y * L.sin_body;
@@ -87,7 +88,7 @@ LRM_HD bool lrm_reach_global(const LrmCompiledLeg& L, const LrmCircle* lists, Lr
 }
 
 // reachable_rotate_leg, several_leg.cu:48-67
-LRM_HD bool lrm_reachable_rotate_leg(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3 t,
+LRM_HD bool lrm_reachable_rotate_leg(const LrmLegHead& L, const LrmCircle* lists, LrmVec3 t,
                                      LrmVec3 body) {
     t.x -= body.x;
     t.y -= body.y;
@@ -121,7 +122,7 @@ LRM_HD void lrm_clamp_on(float cx, float cy, float cr, bool attract, float& x, f
 }
 
 // eval_plane_circles<DIST> + multi_circle_clamp, one_leg.cu:91-145, :167-208
-LRM_HD bool lrm_plane_dist(const LrmCompiledLeg& L, const LrmCircle* lists, float& x, float& y) {
+LRM_HD bool lrm_plane_dist(const LrmLegHead& L, const LrmCircle* lists, float& x, float& y) {
     x -= L.coxa_length;
     const LrmCircle* list = lists + lrm_region(L, x, y) * LRM_N_CIRCLES;
     bool overall = true;
@@ -161,7 +162,7 @@ LRM_HD bool lrm_plane_dist(const LrmCompiledLeg& L, const LrmCircle* lists, floa
 LRM_HD float lrm_norm3(LrmVec3 v) { return lrm_sqrtf(v.x * v.x + v.y * v.y + v.z * v.z); }
 
 // finish_finding_closest<bool>, one_leg.cu:215-278
-LRM_HD bool lrm_finish_closest(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3& p,
+LRM_HD bool lrm_finish_closest(const LrmLegHead& L, const LrmCircle* lists, LrmVec3& p,
                                float angle) {
     const bool mega = (angle > L.mega_hi) || (angle < L.mega_lo);
     float sat;
@@ -200,7 +201,7 @@ LRM_HD bool lrm_finish_closest(const LrmCompiledLeg& L, const LrmCircle* lists, 
 }
 
 // distance_circles, one_leg.cu:321-341
-LRM_HD bool lrm_dist_circles(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3& r) {
+LRM_HD bool lrm_dist_circles(const LrmLegHead& L, const LrmCircle* lists, LrmVec3& r) {
     LrmVec3 a = r;
     a.x -= L.body;
     float buffer = a.x * L.sin_pitch;
@@ -221,7 +222,7 @@ LRM_HD bool lrm_dist_circles(const LrmCompiledLeg& L, const LrmCircle* lists, Lr
 }
 
 // distance_global, one_leg_global.cu:74-101
-LRM_HD bool lrm_dist_global(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3& p) {
+LRM_HD bool lrm_dist_global(const LrmLegHead& L, const LrmCircle* lists, LrmVec3& p) {
     LrmVec3 u = lrm_qrot(L.inv_rot, p);
     float buffer = u.x * L.sin_body;
     u.x = u.x * L.cos_body - u.y * L.sin_body;

@@ -57,11 +57,10 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The strict evaluation of one query against a record seen as an LrmCompiledLeg: lrm_point.h reads nothing beyond
-// the head (the first offsetof(LrmCompiledLeg, flists) bytes), which is what a record holds in that place.
+// The strict evaluation of one query against a record's head.
 // p: the body-relative target in, the distance vector out (kDist)
 template <bool kReach, bool kDist>
-__device__ __forceinline__ void eval_query(const LrmCompiledLeg& L, const LrmCircle* lists, LrmVec3& p, bool& reach, bool& valid) {
+__device__ __forceinline__ void eval_query(const LrmLegHead& L, const LrmCircle* lists, LrmVec3& p, bool& reach, bool& valid) {
     if (kReach) reach = lrm_reach_global(L, lists, p);
     if (kDist) valid = lrm_dist_global(L, lists, p);
     else (void)valid;
@@ -108,13 +107,13 @@ __global__ __launch_bounds__(kBlock, LRM_POSED_MIN_WAVES) void posed_kernel(
             p.x -= R.body_pos[0];
             p.y -= R.body_pos[1];
             p.z -= R.body_pos[2];
-            eval_query<kReach, kDist>(reinterpret_cast<const LrmCompiledLeg&>(R.head), my_lists, p, reach, v);
+            eval_query<kReach, kDist>(R.head, my_lists, p, reach, v);
         } else {
             const LrmPoseRecord& R = recs[r];
             p.x -= R.body_pos[0];
             p.y -= R.body_pos[1];
             p.z -= R.body_pos[2];
-            eval_query<kReach, kDist>(reinterpret_cast<const LrmCompiledLeg&>(R.head), &R.head.lists[0][0], p, reach, v);
+            eval_query<kReach, kDist>(R.head, &R.head.lists[0][0], p, reach, v);
         }
         if (act) {
             if (!in_range) {

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void self_clearance_posed_kernel(
                 const size_t rec = (size_t)p * nlegs + lane;
                 const size_t o = (size_t)lane * nsets + s;
                 LrmVec3 Jl[4];
-                lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(recs[rec].head), iks[rec], coxa[o], femur[o], tibia[o], tip_clear, Jl);
+                lrm_leg_joints(recs[rec].head, iks[rec], coxa[o], femur[o], tibia[o], tip_clear, Jl);
                 valid = lrm_leg_joints_finite(Jl);
 #pragma unroll
                 for (int k = 0; k < 4; k++) {

@@ -37,7 +37,7 @@ LRM_HD float lrm_loads_nan() { return lrm_u2f(0x7fc00000u); }
 LRM_HD float lrm_loads_out(float x) { return x != x ? lrm_loads_nan() : x + 0.f; }
 
 // The linear part of lrm_ik_from_coxa: a DIRECTION of the coxa frame in the caller's frame (no `u.x += L.body`).
-LRM_HD LrmVec3 lrm_loads_lin(const LrmCompiledLeg& L, const LrmIkLeg& K, LrmVec3 u) {
+LRM_HD LrmVec3 lrm_loads_lin(const LrmLegHead& L, const LrmIkLeg& K, LrmVec3 u) {
     const float buffer = u.x * L.sin_pitch_rev;
     u.x = u.x * L.cos_pitch_rev - u.z * L.sin_pitch_rev;
     u.z = buffer + u.z * L.cos_pitch_rev;
@@ -57,7 +57,7 @@ struct LrmLoadsLeg {
 };
 LRM_HD float lrm_loads_dot_up(const float up[3], LrmVec3 a) { return (up[0] * a.x + up[1] * a.y) + up[2] * a.z; }
 // The columns of the tip's Jacobian in the coxa frame, with lrm_leg_joints' sincos arguments and its T (tip_clear == 0).
-LRM_HD void lrm_loads_levers(const LrmCompiledLeg& L, const LrmIkLeg& K, const float up[3], float c, float f, float t, float g[3]) {
+LRM_HD void lrm_loads_levers(const LrmLegHead& L, const LrmIkLeg& K, const float up[3], float c, float f, float t, float g[3]) {
     float sc, cc, sf, cf, sa, ca;
     lrm_sincosf(c, &sc, &cc);
     lrm_sincosf(f, &sf, &cf);
@@ -70,7 +70,7 @@ LRM_HD void lrm_loads_levers(const LrmCompiledLeg& L, const LrmIkLeg& K, const f
     g[2] = lrm_loads_dot_up(up, lrm_loads_lin(L, K, LrmVec3{-cc * ts, -sc * ts, tc}));
 }
 // Leg l of a live set with centre of mass c: false = the leg is not valid (nothing of *A is then read)
-LRM_HD bool lrm_loads_leg(const LrmLoadsParams& P, const LrmCompiledLeg& L, const LrmIkLeg& K, LrmStancePt c, float coxa, float femur,
+LRM_HD bool lrm_loads_leg(const LrmLoadsParams& P, const LrmLegHead& L, const LrmIkLeg& K, LrmStancePt c, float coxa, float femur,
                           float tibia, LrmLoadsLeg* A) {
     LrmVec3 J[4];
     lrm_leg_joints(L, K, coxa, femur, tibia, 0.f, J);

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void stance_loads_posed_kernel(
         if (live && lane < nlegs) {
             const size_t rec = (size_t)p * nlegs + lane;
             const size_t o = (size_t)lane * nsets + s;
-            valid = lrm_loads_leg(P, reinterpret_cast<const LrmCompiledLeg&>(recs[rec].head), iks[rec], c, coxa[o], femur[o], tibia[o], &A);
+            valid = lrm_loads_leg(P, recs[rec].head, iks[rec], c, coxa[o], femur[o], tibia[o], &A);
         }
         const uint32_t feet = (uint32_t)__ballot(valid) & 0xffu; // wave-uniform
         // lane = triple code: the triple's barycentric loads, once per set
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void stance_loads_lane_kernel(
             if (live && (uint32_t)l < nlegs) {
                 const size_t rec = (size_t)p * nlegs + l;
                 const size_t o = (size_t)l * nsets + s;
-                if (lrm_loads_leg(P, reinterpret_cast<const LrmCompiledLeg&>(recs[rec].head), iks[rec], c, coxa[o], femur[o], tibia[o], &A))
+                if (lrm_loads_leg(P, recs[rec].head, iks[rec], c, coxa[o], femur[o], tibia[o], &A))
                     feet |= 1u << l;
             }
             xi[l] = A.xi, eta[l] = A.eta, g[l][0] = A.g[0], g[l][1] = A.g[1], g[l][2] = A.g[2];

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void trunk_clearance_posed_kernel(
             const size_t rec = (size_t)p * nlegs + slot;
             const size_t o = (size_t)slot * nsets + s;
             LrmVec3 J[4];
-            lrm_leg_joints(reinterpret_cast<const LrmCompiledLeg&>(recs[rec].head), iks[rec], coxa[o], femur[o], tibia[o], tip_clear, J);
+            lrm_leg_joints(recs[rec].head, iks[rec], coxa[o], femur[o], tibia[o], tip_clear, J);
             if (lrm_leg_joints_finite(J)) A = lrm_trunk_leg(C, R, recs[rec].head.inv_rot, J);
         }
         if (have) {

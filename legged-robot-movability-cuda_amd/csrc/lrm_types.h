@@ -1,6 +1,8 @@
 // lrm_types.h -- host/device shared plain-old-data of the MI355X reach/distance path.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/lrm.h"
 
 #if defined(__HIPCC__)
@@ -46,12 +48,12 @@ struct alignas(16) LrmCircle {
     float x, y, r, attract;
 };
 
-// Everything the per-point code needs that depends only on (leg, body orientation).
+// Everything the strict per-point code (lrm_point.h, lrm_ik.h) needs that depends only on (leg, body orientation).
 // The reference rebuilds all of it for every point (insert_circles circles.cu.h:337-383,
 // insert_intersecv2 :417-476, rotate_leg_data one_leg_global.cu:48-60, the sincosf of
 // coxa_pitch / body_angle); here the host computes it once per (leg, quaternion) with the
 // reference's own expressions and libm calls, so the values are the same floats.
-struct LrmCompiledLeg {
+struct LrmLegHead {
     // circle list for region (upper, fully_extended): lists[upper*2 + fe][0..3]
     LrmCircle lists[4][LRM_N_CIRCLES];
     // corner points that survive the joint-limit filter, in reference order
@@ -73,6 +75,12 @@ struct LrmCompiledLeg {
     float region_mid;                   // circles.cu.h:52-54
     float full_sat[2];                  // circles.cu.h:68, indexed by UpperRegion
     float reach_r2_max;                 // (body-frame) squared radius beyond which nothing is reachable
+};
+
+// The head, then the constants of the filtered and tolerance evaluations (lrm_point_fast.h and what builds on it).  A base,
+// not a member: code written for a whole leg says L.lists or L.cos_body as before, and the strict layer, declared on
+// const LrmLegHead&, takes a compiled leg or the head of a pose record (lrm_compile_head.h) alike but cannot name a tail field.
+struct LrmCompiledLeg : LrmLegHead {
     // ---- constants of the filtered (LRM_MODE_FAST) evaluation: lrm_point_fast.h ----
     // squared-domain validity test of circle lists[k][i]:  valid <=> sg*(m - T) < 0 with
     // m = |p - c|^2;  T = (r + margin)^2, sg = +1 (attractive) or T = (r - margin)^2, sg = -1;
@@ -128,6 +136,15 @@ struct LrmCompiledLeg {
     float band_q;                        // LRM_BAND_DIST * 2 * fast_scale: clamp points live on the circles
     float pad3_[3];
 };
+// The layout both compilers, the kernarg structs and the 512-byte pose record rely on.
+static_assert(sizeof(LrmLegHead) == 480, "head size");
+static_assert(sizeof(LrmCompiledLeg) == 2480, "compiled leg size");
+static_assert(alignof(LrmCompiledLeg) == 16, "compiled leg alignment");
+static_assert(std::is_trivially_copyable<LrmCompiledLeg>::value, "a compiled leg travels by memcpy and as a kernel argument");
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof" // a base makes the leg non-standard-layout; the offset is what is pinned here
+static_assert(offsetof(LrmCompiledLeg, flists) == sizeof(LrmLegHead), "the tail begins where the head ends");
+#pragma GCC diagnostic pop
 
 // ---- tolerance mode (LRM_MODE_TOL, lrm_point_tol.h) -------------------------------------------
 // Everything the contract-tolerance evaluation reads, compiled from an LrmCompiledLeg (lrm_compile_tol).
