@@ -267,11 +267,17 @@ int lrm_reach_dist_posed_cpu(const float* xyz_aos, size_t n, const int32_t* pose
  *   LRM_IK_NEAREST   2  not reachable (mask 0); the tip is at most |d| + 2e-3 mm (+ 2^-22 |d|, the float32
  *                       resolution of |d|: 1.2e-4 mm at 500 mm) from p
  *   LRM_IK_MODEL_GAP 3  mask 1, but no candidate is within 2e-3 mm of p: the circle model calls p reachable where the
- *                       joint limits do not reach (DESIGN.md); the angles are the best in-limit candidate
- *   LRM_IK_FAR_GAP   4  mask 0, and no candidate is within that distance: the model's distance is shorter than any
- *                       in-limit configuration's (with a unit quaternion; see above); the angles are the best in-limit
- *                       candidate
+ *                       joint limits do not reach (DESIGN.md 3.8); the angles are the best in-limit candidate
+ *   LRM_IK_FAR_GAP   4  mask 0, and the best in-limit candidate aimed at p - d is further than that from p (with a unit
+ *                       quaternion; see above); the angles are that candidate
  *   LRM_IK_NONE      0  non-finite input (or coordinates beyond ~1e18 mm, where float32 overflows): nan angles
+ * Where 3 and 4 occur and what they claim (tests/test_ik_boundary_cpu.py against a float64 search of the limit set):
+ * they are reported only where no in-limit tip lies within 1e-3 mm of p.  On the M2 and moonbot legs they occur only
+ * within about 1e-2 mm outside a limit face: the circle model's margin calls such a p reachable (3), or puts p - d
+ * outside the limit set (4); the returned tip is then the nearest in-limit one to float32 rounding.  Legs of other
+ * proportions get them at scale, and there the returned tip need not be the nearest.  Status 4 does not promise that no in-limit configuration is
+ * nearer than |d|: where a rotated limit passes +-pi the limit set holds configurations the circle model does not,
+ * and an in-limit tip can be nearer than |d| (by 29 mm on the test leg random10).
  * So status in {1, 3} <=> reachability_global's mask.  Decided in float32; the device entry points equal the CPU ones
  * bit for bit (angles, status bytes, FK positions).
  * lrm_fk_*: the tip of (coxa, femur, tibia) in the caller's frame, the exact inverse of the chain above (the
@@ -570,8 +576,9 @@ int lrm_foothold_misses_posed_cpu(const float* targets_aos, size_t nt, const flo
  * Consequences: with pose_live NULL the sum over t of count_out[l, t] equals the sum over p of
  * lrm_footholds_posed_dev's count[l, p]; count_out[l, t] > 0 iff t occurs in some list of leg l of
  * lrm_foothold_lists_posed_dev; for p* = best_pose_out[l, t] the list of (p*, l) contains t with exactly best_d2_out's
- * bits; lrm_ik_posed_dev on (t, p*, l) reports a mask-1 status: LRM_IK_REACHED, or LRM_IK_MODEL_GAP at the few boundary
- * points where the joint model does not follow the circle model (see the IK section), never LRM_IK_NONE / NEAREST /
+ * bits; lrm_ik_posed_dev on (t, p*, l) reports a mask-1 status: LRM_IK_REACHED, or LRM_IK_MODEL_GAP at the few
+ * points just outside a limit face (M2 and moonbot: within about 1e-2 mm) that the circle model's margin still calls
+ * reachable while no in-limit tip is within 1e-3 mm (see the IK section), never LRM_IK_NONE / NEAREST /
  * FAR_GAP; with pose_live = all_legs_out of lrm_footholds_posed_dev only positionable bodies count.
  * A nan or infinite target reaches nothing.  A pose with a nan body or a non-unit quaternion is handled as in
  * lrm_footholds_posed_dev: its sphere excludes nothing and it is tested against every target.

@@ -168,7 +168,8 @@ struct LrmIkCand {
 // One knee of the 2-link solve in the yaw plane: goal (px, pz) relative to the femur joint, phi = atan2(pz, px),
 // (f, t) the unclamped solution.  A violated femur limit: the femur goes to it and the tibia aims at the goal; then a
 // violated tibia limit: the tibia goes to it and the femur is re-solved; then a violated absolute limit: f + t goes
-// to it and the femur is re-solved.  Last, the clamp into the limits (femur into [f_lo, f_hi], tibia into its limits
+// to it and the femur is re-solved on that face (clamped to where the femur and tibia limits leave it: a corner there).
+// Last, the clamp into the limits (femur into [f_lo, f_hi], tibia into its limits
 // and [aneg - f, apos - f]) and the residual, with w2 the squared distance of the goal to the plane.
 LRM_HD void lrm_ik_knee(const LrmIkLeg& K, float px, float pz, float phi, float w2, float f, float t, LrmIkCand& o) {
     if (f < K.fmin || f > K.fmax) {
@@ -189,6 +190,10 @@ LRM_HD void lrm_ik_knee(const LrmIkLeg& K, float px, float pz, float phi, float 
         float s, c;
         lrm_sincosf(a, &s, &c);
         f = lrm_atan2f(pz - K.T * s, px - K.T * c);
+        // stay ON the absolute face where the femur or the tibia limit cuts it: the nearest point is then the corner.
+        // Clamping f and t separately afterwards (below) would keep the t of the unclamped f and leave the face.
+        const float flo = a - K.tmax, fhi = a - K.tmin;
+        f = lrm_ik_clampf(f, (K.f_lo > flo) ? K.f_lo : flo, (K.f_hi < fhi) ? K.f_hi : fhi);
         t = a - f;
     }
     f = lrm_ik_clampf(f, K.f_lo, K.f_hi);
