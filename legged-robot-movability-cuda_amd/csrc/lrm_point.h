@@ -159,7 +159,38 @@ LRM_HD bool lrm_plane_dist(const LrmLegHead& L, const LrmCircle* lists, float& x
     return overall;
 }
 
-LRM_HD float lrm_norm3(LrmVec3 v) { return lrm_sqrtf(v.x * v.x + v.y * v.y + v.z * v.z); }
+// norm(v) of the reference (Eigen's / the kernels' sqrt of the sum in this order) = lrm_sqrtf(lrm_norm3_sum(v))
+LRM_HD float lrm_norm3_sum(LrmVec3 v) { return v.x * v.x + v.y * v.y + v.z * v.z; }
+LRM_HD float lrm_norm3(LrmVec3 v) { return lrm_sqrtf(lrm_norm3_sum(v)); }
+
+// lrm_sqrtf(A) < lrm_sqrtf(B) for two sums of lrm_norm3_sum, bit for bit, without the roots wherever the sums decide.
+// lrm_sqrtf is correctly rounded (round to nearest) on host and device, hence monotone: A >= B gives sqrt(A) >= sqrt(B), the
+// comparison is false (this covers equal sums).  For A < B the roots may still round to the SAME float (two to three
+// neighbouring sums share a root), so A < B alone does not decide; a relative gap does.  With c = 1 - 2^-20 (exact in float),
+// B a normal float and t = fl(B * c) <= B c (1 + 2^-24):  A < t  gives  A < B (1 - 2^-20)(1 + 2^-24) < B (1 - 2^-21), so for
+// the real roots a = sqrt(A), b = sqrt(B):  a < b sqrt(1 - 2^-21) < b (1 - 2^-22).  Rounding moves a normal number by at most
+// half an ulp, and an ulp of x is at most 2^-23 x:  RN(a) <= a (1 + 2^-24) < b (1 - 2^-22)(1 + 2^-24) < b (1 - 2^-24) <= RN(b).
+// So  A < fl(B * c)  gives  lrm_sqrtf(A) < lrm_sqrtf(B)  strictly.  Both claims need A, B and B * c normal and the roots free of
+// underflow: taken for sums in [2^-96, 2^96) only (the interval of lrm_sqrtf's own short sequence).  Every other pair -- zero,
+// denormal, huge, inf, nan, negative, or A inside the gap below B -- is decided by the two roots as before; on the device
+// behind one wave-uniform branch, so that a wave without such a lane issues no root at all.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LRM_WAVE_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0ull)
+#else
+#define LRM_WAVE_ANY(c) (c)
+#endif
+#define LRM_NORM_GAP 0.99999904632568359375f // 1 - 2^-20
+LRM_HD bool lrm_norm_sums_less(float A, float B) {
+    const bool plain = ((lrm_f2u(A) - 0x0f800000u) < 0x60000000u) && ((lrm_f2u(B) - 0x0f800000u) < 0x60000000u);
+    const bool less = A < B * LRM_NORM_GAP; // roots differ
+    const bool hard = !(plain && (less || A >= B));
+    bool r = less;
+    if (LRM_WAVE_ANY(hard)) {
+        const bool roots = lrm_sqrtf(A) < lrm_sqrtf(B);
+        r = hard ? roots : r;
+    }
+    return r;
+}
 
 // finish_finding_closest<bool>, one_leg.cu:215-278
 LRM_HD bool lrm_finish_closest(const LrmLegHead& L, const LrmCircle* lists, LrmVec3& p,

@@ -439,7 +439,7 @@ LRM_HD bool lrm_finish_closest_fast(const LrmCompiledLeg& L, const LrmDistTables
             if (th != 0.f) lrm_sincosf(th, &s2, &c2);
             const float sy = save.x * s2 + save.y * c2;
             LrmVec3 lim = {0.f, sy, 0.f};
-            if (lrm_norm3(p) > lrm_norm3(lim)) {
+            if (lrm_norm_sums_less(lrm_norm3_sum(lim), lrm_norm3_sum(p))) { // d_clamped > d_limit, bit for bit (lrm_point.h)
                 const float b2 = lim.y * s2;
                 lim.y = -lim.x * s2 + lim.y * c2;
                 lim.x = lim.x * c2 + b2;

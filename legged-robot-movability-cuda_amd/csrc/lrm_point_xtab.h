@@ -114,8 +114,16 @@ LRM_HD void lrm_xtab_plane(const LrmTolTabView& G, uint32_t code, float x, float
 //   wl      the point's offset from the yaw-limit plane `limit` (decision arithmetic): |wl| is d_limit up to rounding
 // Returns the candidate's vector in the coxa frame; valid = eval_plane_circles' result (the point passes its circles);
 // (tx, ty, tr) = the clamp target that won (for the twin of an invalid candidate, lrm_xtab_twin).
+//   twin_pre  the candidate has a twin if it turns out invalid (lrm_xtab_point), ang_ff the twin's yaw
+//   twin      out: twin_pre && !valid;  (s2, c2) out: for a twin lane sincosf(-ang_ff), what lrm_xtab_twin rotates by
+// The second sincosf of a point.  The yaw-limit alternative needs sincosf(th) and belongs to a VALID candidate, the twin needs
+// sincosf(-ang_ff) and belongs to an INVALID one: no lane needs both, and nearly every wave holds lanes of both kinds.  So the
+// wave evaluates the polynomial once, every lane on its own angle (sincosf is a function of its argument: the same bits as two
+// separate calls), instead of once in the alternative's branch and once in the twin's.
 LRM_HD LrmVec3 lrm_xtab_chain(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVec3 p, float s, float c, float th, uint32_t cell, bool mega,
-                              float wl, float band, float tau, bool& valid, float& tx, float& ty, float& tr, uint32_t& doubt) {
+                              float wl, float band, float tau, bool& valid, float& tx, float& ty, float& tr, uint32_t& doubt,
+                              bool twin_pre, float ang_ff, bool& twin, float& s2, float& c2) {
+    LRM_PHASE("x4_rotate_plane_clamp");
     float buffer = p.x * s; // cancel_coxa_rotation
     p.x = p.x * c - p.y * s;
     p.y = buffer + p.y * c;
@@ -129,23 +137,31 @@ LRM_HD LrmVec3 lrm_xtab_chain(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVe
         p.x = x - cx;
         p.z = p.z - cy;
     }
+    bool alt = false;
     if (valid && !mega) { // one_leg.cu:258-274: the nearer yaw-limit plane wins when it is closer than the in-plane boundary
         const float n2 = __builtin_fmaf(p.x, p.x, __builtin_fmaf(p.y, p.y, p.z * p.z));
         const float dl = fabsf(wl), dl2 = dl * dl;
         const bool near = !(fabsf(n2 - dl2) > band * __builtin_fmaf(2.0f, dl, band));
-        if (near || n2 > dl2) { // strict arithmetic decides when `near`, and produces the output
-            float s2 = th, c2 = 1.0f; // sincosf(+-0) = (+-0, 1): a candidate clamped to the limit itself
-            if (th != 0.f) lrm_sincosf(th, &s2, &c2);
-            const float sy = save.x * s2 + save.y * c2;
-            LrmVec3 lim = {0.f, sy, 0.f};
-            if (lrm_norm3(p) > lrm_norm3(lim)) {
-                const float b2 = lim.y * s2;
-                lim.y = -lim.x * s2 + lim.y * c2;
-                lim.x = lim.x * c2 + b2;
-                p = lim;
-            }
+        alt = near || n2 > dl2; // strict arithmetic decides when `near`, and produces the output
+    }
+    twin = twin_pre && !valid;
+    LRM_PHASE("x5_second_sincosf");
+    s2 = th, c2 = 1.0f; // sincosf(+-0) = (+-0, 1): a candidate clamped to the limit itself
+    if (twin || (alt && th != 0.f)) lrm_sincosf(twin ? -ang_ff : th, &s2, &c2);
+    if (alt) {
+        LRM_PHASE("x5_alternative");
+        const float sy = save.x * s2 + save.y * c2;
+        LrmVec3 lim = {0.f, sy, 0.f};
+        // d_clamped > d_limit (one_leg.cu:268) from the two sums: lrm_norm_sums_less (lrm_point.h) is that comparison of the
+        // roots bit for bit, and takes the roots only for a lane whose sums lie inside its gap (a wave-uniform branch)
+        if (lrm_norm_sums_less(lrm_norm3_sum(lim), lrm_norm3_sum(p))) {
+            const float b2 = lim.y * s2;
+            lim.y = -lim.x * s2 + lim.y * c2;
+            lim.x = lim.x * c2 + b2;
+            p = lim;
         }
     }
+    LRM_PHASE("x7_pick_back_transform");
     buffer = p.y * s; // restore_coxa_rotation
     p.y = -p.x * s + p.y * c;
     p.x = p.x * c + buffer;
@@ -156,9 +172,8 @@ LRM_HD LrmVec3 lrm_xtab_chain(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVe
 // plane with sat = (yaw -+ pi) +- pi, the yaw up to rounding.  Same cell, same decisions (the plane point moves by less than an
 // ulp of its coordinates, far inside every band the first candidate had to clear), no yaw-limit alternative (mega): its own
 // sincosf, rotation, strict clamp onto the SAME target, rotation back.
-LRM_HD LrmVec3 lrm_xtab_twin(const LrmXtabLeg& X, LrmVec3 p, float sat, float tx, float ty, float tr) {
-    float s, c;
-    lrm_sincosf(-sat, &s, &c);
+// (s, c) = sincosf(-sat) of its yaw (lrm_xtab_chain evaluated it next to the alternative's).
+LRM_HD LrmVec3 lrm_xtab_twin(const LrmXtabLeg& X, LrmVec3 p, float s, float c, float tx, float ty, float tr) {
     float buffer = p.x * s;
     p.x = p.x * c - p.y * s;
     p.y = buffer + p.y * c;
@@ -181,6 +196,7 @@ inline thread_local unsigned long long lrm_xtab_host_seconds = 0; // host statis
 // is in doubt, see lrm_reach_from_dist).  doubt != 0: do not use the outputs.
 LRM_HD bool lrm_xtab_point(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVec3& p, uint32_t& doubt) {
     // ---- strict: into the coxa frame, the yaw ----
+    LRM_PHASE("x1_prologue_atan2f");
     const float band = __builtin_fmaf(fabsf(p.x) + fabsf(p.y) + fabsf(p.z), X.band_slope, X.band_base);
     const float tau = band * LRM_TOL_TIE;
     LrmVec3 a = lrm_qrot(X.inv_rot, p);
@@ -194,6 +210,7 @@ LRM_HD bool lrm_xtab_point(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVec3&
     const float ang = lrm_atan2f(a.y, a.x);
     const float ang_flip = (ang > 0) ? ang - LRM_PI_F : ang + LRM_PI_F;
     // ---- decisions, as lrm_tab_point, on the strict coxa-frame point ----
+    LRM_PHASE("x2_decisions_lookups");
     const float x = a.x, y = a.y, z = a.z;
     const float r = LRM_FAST_SQRT(__builtin_fmaf(y, y, x * x));
     const float cM = X.yaw_cs[0], sM = X.yaw_cs[1], cm = X.yaw_cs[2], sm = X.yaw_cs[3];
@@ -238,13 +255,17 @@ LRM_HD bool lrm_xtab_point(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVec3&
     const float limit = (angle > X.coxa_mid) ? X.max_coxa : X.min_coxa;
     const float sat = lim ? (mn ? X.min_coxa : X.max_coxa) : ((code == 1u) ? ang_flip : (flip ? ang_ff : ang));
     float s = mn ? X.lim_sc[2] : X.lim_sc[0], c = mn ? X.lim_sc[3] : X.lim_sc[1];
+    LRM_PHASE("x3_sincosf");
     if (!lim) lrm_sincosf(-sat, &s, &c);
+    LRM_PHASE("x2_decisions_lookups");
     const float th = -(limit - sat);
     const uint32_t cell = lrm_toltab_resolve(G, flip ? cF : cD, flip ? sF : sD, fbase);
     const float wl = (limit == X.max_coxa) ? wM : wm;
-    bool valid;
-    float tx, ty, tr;
-    LrmVec3 rv = lrm_xtab_chain(X, G, a, s, c, th, cell, mega, wl, band, tau, valid, tx, ty, tr, lu);
+    bool valid, twin;
+    float tx, ty, tr, s1, c1;
+    // The twin of an invalid direct candidate in front of the coxa (below): known but for the candidate's validity
+    const bool twin_pre = !two && firstD && inD && (ang_ff != ang);
+    LrmVec3 rv = lrm_xtab_chain(X, G, a, s, c, th, cell, mega, wl, band, tau, valid, tx, ty, tr, lu, twin_pre, ang_ff, twin, s1, c1);
     const bool flag = valid && in0;
     // A DIFFERENT second candidate can still win when the first one is not below its lower bound by more than the tie band
     // (0.3 % of a random cloud): left to the filtered code.
@@ -254,9 +275,11 @@ LRM_HD bool lrm_xtab_point(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVec3&
     }
     // The twin of an invalid direct candidate in front of the coxa: distance_circles' pick (one_leg.cu:334) with
     // res == resflip == false: the strictly shorter DIRECT candidate, else the flipped one.
-    const bool twin = !two && firstD && inD && !valid && (ang_ff != ang);
     if (LRM_TOL_ANY(twin)) {
-        const LrmVec3 fb = lrm_xtab_twin(X, a, ang_ff, tx, ty, tr);
+        LRM_PHASE("x6_twin");
+        const LrmVec3 fb = lrm_xtab_twin(X, a, s1, c1, tx, ty, tr);
+        // (The two vectors differ by rounding: their sums are neighbours, which lrm_norm_sums_less hands to the roots anyway.
+        // Routing this pick through it cost 0.8 us per 1e7 points, profiles/xtab_diet_ab.txt: the roots stay.)
         const bool take = twin && !(lrm_norm3(rv) < lrm_norm3(fb));
         rv.x = take ? fb.x : rv.x;
         rv.y = take ? fb.y : rv.y;
@@ -266,6 +289,7 @@ LRM_HD bool lrm_xtab_point(const LrmXtabLeg& X, const LrmTolTabView& G, LrmVec3&
 #endif
     }
     // place_over_coxa<Reverse>, z_unrotateInPlace, qtRotate
+    LRM_PHASE("x7_pick_back_transform");
     buffer = rv.x * X.sin_pitch_rev;
     rv.x = rv.x * X.cos_pitch_rev - rv.z * X.sin_pitch_rev;
     rv.z = buffer + rv.z * X.cos_pitch_rev;
@@ -313,9 +337,13 @@ LRM_HD void lrm_xtab_replay(const LrmXtabLeg& X, const LrmTabRow* rows, LrmVec3&
     // This function is a latency chain run by one wave at the end of its workgroup (the workgroup's LDS and wave slots wait for it):
     // the twin's value chain -- independent of the candidate's once the yaw is known -- is written next to it, not behind a branch,
     // so that the two sincosf / clamp chains interleave (a wave of short vectors nearly always holds a lane that needs the twin).
+    // The second sincosf is ONE evaluation as in lrm_xtab_chain: a lane whose vector is the offset from the yaw-limit plane (`off`:
+    // a valid candidate, or one clamped to the limit -- never code 0 with the flag down, which is what a twin needs) takes
+    // sincosf(th), every other lane the twin's sincosf(-ang_ff).  (th = +-0 gives (+-0, 1) out of lrm_sincosf itself.)
+    const float th = -(limit - sat);
     float s1, c1;
     if (!lim) lrm_sincosf(-sat, &s, &c);
-    lrm_sincosf(-ang_ff, &s1, &c1);
+    lrm_sincosf(off ? th : -ang_ff, &s1, &c1);
     LrmVec3 q = a, q1 = a;
     buffer = q.x * s; // cancel_coxa_rotation
     q.x = q.x * c - q.y * s;
@@ -332,9 +360,7 @@ LRM_HD void lrm_xtab_replay(const LrmXtabLeg& X, const LrmTabRow* rows, LrmVec3&
         q1.z = q1.z - cy;
     }
     if (LRM_TOL_ANY(off)) { // the offset from the yaw-limit plane (one_leg.cu:258-274 decided `d_clamped > d_limit`)
-        const float th = -(limit - sat);
-        float s2 = th, c2 = 1.0f;
-        if (th != 0.f) lrm_sincosf(th, &s2, &c2);
+        const float s2 = s1, c2 = c1;
         const float sy = q.x * s2 + q.y * c2;
         LrmVec3 l = {0.f, sy, 0.f};
         const float b2 = l.y * s2;

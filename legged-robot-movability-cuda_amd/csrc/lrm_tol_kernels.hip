@@ -389,7 +389,9 @@ __global__ __launch_bounds__(kBlock, kShort ? LRM_SHORT_MIN_WAVES : LRM_TAB_MIN_
             const uint32_t* r = segment + 5u * k;
             const size_t i = r[0];
             LrmVec3 q{lrm_u2f(r[1]), lrm_u2f(r[2]), lrm_u2f(r[3])};
+            LRM_PHASE("replay_value_chain");
             lrm_xtab_replay(lrm_fresh(X), s_tab.rows, q, r[4]);
+            LRM_PHASE("replay_store");
             if (kAoS) {
                 dx[3 * i] = q.x;
                 dx[3 * i + 1] = q.y;
@@ -564,6 +566,7 @@ __global__ __launch_bounds__(kBlock, LRM_XTAB_MIN_WAVES) void dist_xtab_kernel(
     const uint32_t toff0 = threadIdx.x * 4u;
     uint32_t round = 0;
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_pad; i += stride, round++) {
+        LRM_PHASE("x0_loop_head_prefetch");
         const bool live = i < n32;
         const size_t rbase = (size_t)blockIdx.x * kBlock + (size_t)round * stride;
         const uint32_t toff = lrm_opaque(toff0), tid_o = lrm_opaque(threadIdx.x);
@@ -576,6 +579,7 @@ __global__ __launch_bounds__(kBlock, LRM_XTAB_MIN_WAVES) void dist_xtab_kernel(
         }
         uint32_t doubt = 0;
         const bool m = lrm_xtab_point(lrm_fresh(X), G, p, doubt) && live;
+        LRM_PHASE("x8_stores_queues");
         doubt = live ? ((doubt & 0xffffu) | (selftest & 1u)) : 0u;
         if (live) {
             store_field<kAoS, true>(dx, dy, dz, rbase, toff, p);
@@ -587,6 +591,7 @@ __global__ __launch_bounds__(kBlock, LRM_XTAB_MIN_WAVES) void dist_xtab_kernel(
         }
         const uint64_t dm = __ballot(doubt != 0);
         if (dm) { // the point is re-loaded by the pushing lanes (it comes back from the L2): three registers fewer in the chain above
+            LRM_PHASE("rare_doubt_push");
             uint32_t qb = 0;
             if (lane == 0) qb = atomicAdd(&s_qn, (uint32_t)__popcll(dm));
             qb = (uint32_t)__builtin_amdgcn_readfirstlane((int)qb);
@@ -597,8 +602,10 @@ __global__ __launch_bounds__(kBlock, LRM_XTAB_MIN_WAVES) void dist_xtab_kernel(
                     seg[qs] = QueueRec{i, q.x, q.y, q.z};
                 }
             }
+            LRM_PHASE("x8_stores_queues");
         }
     }
+    LRM_PHASE("end_of_loop");
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = s_qn;
 }
@@ -650,7 +657,8 @@ __device__ __forceinline__ bool lrm_redo_pair(const LrmCompiledLeg& L, const Lrm
     const uint32_t u_other = lrm_pair_swap(u_mine);
     const LrmVec3 a = cand ? other : mine, b = cand ? mine : other;
     const bool res = cand ? r_other : r_mine, resflip = cand ? r_mine : r_other;
-    const bool use_direct = (res == resflip) ? (lrm_norm3(a) < lrm_norm3(b)) : res;
+    // (the pick of two different configurations: their sums decide, lrm_norm_sums_less is the comparison of the roots bit for bit)
+    const bool use_direct = (res == resflip) ? lrm_norm_sums_less(lrm_norm3_sum(a), lrm_norm3_sum(b)) : res;
     LrmVec3 r = use_direct ? a : b;
     const LrmCompiledLeg& Le = LRM_FRESH(L);
     buffer = r.x * Le.sin_pitch_rev;

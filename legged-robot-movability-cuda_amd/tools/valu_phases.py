@@ -9,7 +9,12 @@ lanes, the second candidate, the in-loop flush, the doubt push.  An instruction 
 the assembly text; the scheduler may move instructions across a mark, so the split is a guide (a few instructions either
 way), the totals are what counts.  The marks themselves perturb the code: the tool prints whole-kernel totals of both builds.
 
+--xtab prints the same for the bit-exact side instead: the loop of dist_xtab_kernel<2,false> (LRM_MODE_FAST; its alternative and
+twin phases are run by every wave and belong to the common path), the replay tail of dist_tab_kernel<2,false,true> (the text
+between its replay_* marks, behind the loop) and the whole of tol_fixup_kernel<2,false> (one latency chain, no phases).
+
     python tools/valu_phases.py [--src DIR] > profiles/valu_phases.txt
+    python tools/valu_phases.py --xtab [--src DIR] > profiles/valu_phases_xtab.txt
 """
 import argparse
 import os
@@ -21,6 +26,9 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 KERNELS = [("dist_tab_kernel<2,false,true>  (tol_rel)", "dist_tab_kernelILi2ELb0ELb1EE"),
            ("dist_tab_kernel<2,false,false> (tol)", "dist_tab_kernelILi2ELb0ELb0EE")]
+XTAB = ("dist_xtab_kernel<2,false> (fast)", "dist_xtab_kernelILi2ELb0EE")
+REPLAY = ("dist_tab_kernel<2,false,true>: replay tail (tol_rel)", "dist_tab_kernelILi2ELb0ELb1EE")
+FIXUP = ("tol_fixup_kernel<2,false> (fix-up of every mode)", "tol_fixup_kernelILi2ELb0E")
 CLASSES = ["vop12_vgpr", "v_cndmask", "v_cmp", "vop3_sgpr_lit", "trans_cvt", "SALU", "s_load", "LDS", "global", "s_waitcnt"]
 VALU = CLASSES[:5]
 TRANS = re.compile(r"v_(rsq|sqrt|rcp|exp|log|sin|cos|cvt)_")
@@ -89,14 +97,19 @@ def totals(body):
 
 
 def phases(body):
-    """{phase: {class: count}} of the text between the first loop mark and the end-of-loop mark"""
-    out, phase = {}, None
+    """{phase: {class: count}} of the text behind a mark; the end-of-loop mark ends its phase without opening another.
+    The replay_* marks only count behind the loop: the copy of the replay inside the loop stays with the loop's own phase."""
+    out, phase, in_loop = {}, None, False
     for l in body:
         m = re.search(r"LRM_PHASE (\w+)", l)
         if m:
-            phase = m.group(1)
-            if phase == "end_of_loop":
-                break
+            name = m.group(1)
+            if name == "end_of_loop":
+                phase, in_loop = None, False
+            elif not name.startswith("replay_"):
+                phase, in_loop = name, True
+            elif not in_loop:
+                phase = name
             continue
         c = classify(l)
         if phase and c:
@@ -108,9 +121,31 @@ def row(name, t):
     return f"{name:<32}" + "".join(f"{t[c]:>14}" for c in CLASSES) + f"{sum(t[c] for c in VALU):>8}"
 
 
+def table(title, ph, skip, head):
+    print(f"\n== {title} (build with phase marks) ==")
+    print(head)
+    common = dict.fromkeys(CLASSES, 0)
+    for name in sorted(ph):
+        if name.startswith(skip[0]):
+            continue
+        print(row(name, ph[name]))
+        if not name.startswith(skip[1:]):
+            for c in CLASSES:
+                common[c] += ph[name][c]
+    return common
+
+
+def whole(fm, fp):
+    tm, tp = totals(fm), totals(fp)
+    print(row("whole kernel, with marks", tm))
+    print(row("whole kernel, as shipped", tp))
+    print(f"the marks moved {sum(tm[c] for c in VALU) - sum(tp[c] for c in VALU):+d} VALU and {tm['SALU'] - tp['SALU']:+d} SALU instructions in the whole kernel")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default=os.path.join(HERE, "..", "csrc"), help="directory of lrm_tol_kernels.hip and the Makefile")
+    ap.add_argument("--xtab", action="store_true", help="the bit-exact side: dist_xtab_kernel, the replay tail, tol_fixup_kernel")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         plain = assembly(args.src, [], os.path.join(tmp, "plain.s"))
@@ -118,22 +153,24 @@ def main():
     head = f"{'':<32}" + "".join(f"{c:>14}" for c in CLASSES) + f"{'VALU':>8}"
     print("static instruction counts, gfx950; classes: vop12_vgpr = VOP1/VOP2 with VGPR operands only; vop3_sgpr_lit = other VOP3 and")
     print("SGPR-operand / literal forms; trans_cvt = transcendental and conversion; VALU = the first five columns")
+    if args.xtab:
+        fm, fp = function(marked, XTAB[1]), function(plain, XTAB[1])
+        common = table(XTAB[0] + ": one round of the loop", phases(fm), ("replay_", "rare_"), head)
+        print(row("COMMON PATH (without rare_*)", common))
+        whole(fm, fp)
+        fm = function(marked, REPLAY[1])
+        ph = {k: v for k, v in phases(fm).items() if k.startswith("replay_")}
+        table(REPLAY[0] + ": one pass of 64 records", ph, ("\0",), head)
+        fm, fp = function(marked, FIXUP[1]), function(plain, FIXUP[1])
+        print(f"\n== {FIXUP[0]}: no marks inside ==")
+        print(head)
+        whole(fm, fp)
+        return 0
     for title, tag in KERNELS:
         fm, fp = function(marked, tag), function(plain, tag)
-        ph = phases(fm)
-        print(f"\n== {title}: common path of one round of the loop (build with phase marks) ==")
-        print(head)
-        common = dict.fromkeys(CLASSES, 0)
-        for name in sorted(ph):
-            print(row(name, ph[name]))
-            if not name.startswith("rare_"):
-                for c in CLASSES:
-                    common[c] += ph[name][c]
+        common = table(title + ": common path of one round of the loop", phases(fm), ("replay_", "rare_"), head)
         print(row("COMMON PATH (without rare_*)", common))
-        tm, tp = totals(fm), totals(fp)
-        print(row("whole kernel, with marks", tm))
-        print(row("whole kernel, as shipped", tp))
-        print(f"the marks moved {sum(tm[c] for c in VALU) - sum(tp[c] for c in VALU):+d} VALU and {tm['SALU'] - tp['SALU']:+d} SALU instructions in the whole kernel")
+        whole(fm, fp)
     return 0
 
 
